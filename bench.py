@@ -14,9 +14,15 @@ processes itself (before anything touches HIP); under torch.distributed.run
 WORLD_SIZE must equal N.  Timing: barrier + synchronize on both sides of K
 steps, max over ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the K steps, write the outputs (`--dump-outputs DIR`), print the result
+line.  Everything else the benchmark measures or checks takes `--full`: the
+oracle comparison of the bench outputs, the one-at-a-time latency, the
+event-instrumented per-kernel times and roofline, the CPU baseline, `--e2e`.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
                     [--config c3|c2|c5|cz|c4|cm|c1] [--mode full|index]
-                    [--no-cpu] [--no-verify] [--e2e]
+                    [--full [--no-cpu] [--no-verify] [--e2e]]
 """
 from __future__ import annotations
 
@@ -290,9 +296,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--mode", default="full", choices=["full", "index"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the oracle comparison of the bench "
+                         "outputs, the one-at-a-time latency, per-kernel event times and "
+                         "roofline, the CPU baseline (and --e2e)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to "
+                         "DIR/<name>.npy (float32/float64; rank 0; large arrays as a fixed "
+                         "seeded sample)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle comparison of the bench outputs")
+                    help="with --full: skip the oracle comparison of the bench outputs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--c4-inflight", type=int, default=3,
                     help="c4: segments in flight (the Closes of two overlap the next's kernels)")
@@ -303,7 +318,8 @@ def main():
                          "C3 (one box: 2 / 3 / 4 in flight 2694 / 2765 / 2789 GiB/s), 2 for the "
                          "others (C2 at 4: 48.3 vs 55.3 GiB/s; DESIGN.md 13.11)")
     ap.add_argument("--e2e", action="store_true",
-                    help="also time the pinned, pipelined host-buffer path (PCIe both ways)")
+                    help="with --full: also time the pinned, pipelined host-buffer path (PCIe "
+                         "both ways)")
     ap.add_argument("--dist-backend", default="gloo",
                     help="control-plane backend (barrier, gather of the ranks' times).  The "
                          "data path has no collective (each rank owns its segments), so the "
@@ -318,6 +334,12 @@ def main():
     ap.add_argument("--device-mod", type=int, default=0,
                     help="rehearsal only: map LOCAL_RANK -> LOCAL_RANK %% N (ranks share a GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.e2e and not args.full:
+        ap.error("--e2e is a --full measurement: pass --full --e2e")
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_cpu = args.no_verify = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
 
@@ -342,6 +364,82 @@ def main():
 def emit(D, line):
     if D.rank == 0:
         print(json.dumps(line), flush=True)
+
+
+# ---- --dump-outputs ------------------------------------------------------------------
+
+DUMP_CAP = 1 << 20  # elements kept of one array (a larger one is sampled)
+DUMP_ROWS = 1024    # rows whose key/value bytes are kept of a decode's arenas
+_UNSIGNED = {"int16": np.uint16, "int32": np.uint32, "int64": np.uint64}
+
+
+def _dump_sample(torch, t, seed):
+    """t (device tensor, flattened) whole if it holds at most DUMP_CAP elements,
+    else its elements at DUMP_CAP sorted positions drawn from a fixed seed."""
+    t = t.reshape(-1)
+    if t.numel() <= DUMP_CAP:
+        return t.cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), DUMP_CAP))
+    return t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+
+def _arena_rows(torch, arena, off, length, rows):
+    """The bytes of the given rows (device index tensor) of a packed arena,
+    concatenated in row order."""
+    o, n = off[rows], length[rows].to(torch.int64)
+    n = torch.where(n < 0, n + (1 << 16 if length.dtype == torch.int16 else 1 << 32), n)
+    total = int(n.sum().item())
+    if total == 0:
+        return np.zeros(0, np.uint8)
+    start = torch.cumsum(n, 0) - n
+    idx = torch.arange(total, device=arena.device) + torch.repeat_interleave(o - start, n)
+    return arena[idx].cpu().numpy()
+
+
+def dump_outputs(D, torch, path, arrays, hashes=(), signed=("status",)):
+    """--dump-outputs: arrays {name: device tensor, trimmed to what the step
+    wrote} -> path/<name>.npy on rank 0.  Integer outputs that are unsigned on
+    the device (u16 / u32 / u64 held in signed torch tensors) are written with
+    their unsigned values; up to 24 bits as float32, wider as float64 (offsets
+    and sizes stay below 2^53).  64-bit hashes (names in `hashes`) do not fit a
+    float64: written as <name>_lo / <name>_hi, their 32-bit halves.  Arrays
+    over DUMP_CAP elements are sampled at fixed seeded positions (at most
+    8 MiB per file, under 64 MB in all for every config)."""
+    if D.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for i, (name, t) in enumerate(sorted(arrays.items())):
+        a = t if isinstance(t, np.ndarray) else _dump_sample(torch, t, 0x0B5E + i)
+        if a.dtype.name in _UNSIGNED and name not in signed:
+            a = a.view(_UNSIGNED[a.dtype.name])
+        if name in hashes:
+            np.save(os.path.join(path, name + "_lo.npy"),
+                    (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+            np.save(os.path.join(path, name + "_hi.npy"), (a >> np.uint64(32)).astype(np.float64))
+            continue
+        small = a.dtype.itemsize <= 2
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if small else np.float64))
+
+
+def decode_dump_arrays(torch, o, rows, nblk, index_only):
+    """What a caller of the decode receives (out dict o of `rows` rows in
+    `nblk` blocks): the block and row index arrays, and the key / value bytes
+    of DUMP_ROWS rows at fixed seeded positions (the arenas are padded between
+    blocks: only row bytes are defined)."""
+    arr = {k: o[k][:nblk] for k in ("status", "key_base", "val_base")}
+    arr["row_start"] = o["row_start"][:nblk + 1]
+    for k in ("key_off", "key_len", "val_off", "val_len"):
+        arr[k] = o[k][:rows]
+    if index_only:  # no arenas; the bases are not written
+        del arr["key_base"], arr["val_base"]
+    elif rows:
+        pick = np.sort(np.random.default_rng(0x0B5E).integers(0, rows, min(rows, DUMP_ROWS)))
+        pick = torch.from_numpy(pick).to(o["key_off"].device)
+        arr["key_arena_rows"] = _arena_rows(torch, o["key_arena"], o["key_off"], o["key_len"],
+                                            pick)
+        arr["val_arena_rows"] = _arena_rows(torch, o["val_arena"], o["val_off"], o["val_len"],
+                                            pick)
+    return arr
 
 
 # ---- decode (C2 / C3 / C5 / CZ) ---------------------------------------------------
@@ -438,8 +536,8 @@ def run_decode(args, torch, okv, D):
         return dec.decode_device(seg_t, seg.nbytes, d_t, nblk, out, compression=comp,
                                  index_only=index_only, sync=sync)
 
-    # correctness guard on the bench path itself: totals, statuses, and the
-    # outputs against the oracle (every array on rank 0, sampled blocks elsewhere)
+    # correctness guard on the bench path itself: totals, statuses, and (--full)
+    # the outputs against the oracle (every array on rank 0, sampled blocks elsewhere)
     o = step(sync=True)
     assert o.n_rows == rows and o.n_bad_blocks == 0, (o.n_rows, rows, o.n_bad_blocks)
     ver = None
@@ -468,7 +566,7 @@ def run_decode(args, torch, okv, D):
         torch.cuda.synchronize(dev)  # the copy (current stream) before the decode (its stream)
         decs[i].decode_device(segs[i], seg.nbytes, d_t, nblk, outs[i], compression=comp,
                               index_only=index_only, sync=True)
-        for k, v in out.items():  # each context's outputs == the verified ones
+        for k, v in out.items() if args.full else ():  # each context's outputs == the verified
             if index_only and k in ("key_arena", "val_arena", "key_base", "val_base"):
                 continue
             assert torch.equal(outs[i][k], v), k
@@ -500,9 +598,40 @@ def run_decode(args, torch, okv, D):
     # the stream, 40 % of a C2 step) -----------------------------------------------
     t_max, per = D.timed(step_inflight, args.steps)
     ms_per_step = 1e3 * t_max / args.steps
+    if args.dump_outputs:  # the last timed step's output set
+        dump_outputs(D, torch, args.dump_outputs,
+                     decode_dump_arrays(torch, outs[(turn[0] - 1) % inflight], rows, nblk,
+                                        index_only))
     if chained:
         for d in decs:
             d.chain(None)
+    total_in = in_bytes * world
+    total_rows = rows * world
+    value = total_in / (t_max / args.steps) / 2**30
+    line = {
+        "metric": METRIC, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": desc + (", full decode (arenas + SoA)" if not index_only
+                                       else ", index-only spans"),
+                   "blocks_per_gpu": nblk, "segment_bytes_per_gpu": int(seg.nbytes),
+                   "block_bytes_per_gpu": in_bytes, "original_bytes_per_gpu": orig_bytes,
+                   "rows_per_gpu": int(rows), "mode": args.mode,
+                   "parallelism": f"{world} independent segments (no collective)"},
+        "rows_per_s": round(total_rows / (t_max / args.steps)),
+        "mrows_per_s": round(total_rows / (t_max / args.steps) / 1e6, 3),
+        "original_GiB_s": round(orig_bytes * world / (t_max / args.steps) / 2**30, 3),
+        "per_rank_ms_per_step": [round(1e3 * p / args.steps, 4) for p in per],
+        "decodes_in_flight": inflight,
+        "pass3_chained": chained,
+        "dist": D.info(),
+    }
+    if not args.full:
+        emit(D, line)
+        for d in decs:
+            d.close()
+        return
     t_one, _ = D.timed(step, args.steps) if inflight > 1 else (t_max, per)
     for d in decs[1:]:
         d.close()
@@ -548,26 +677,7 @@ def run_decode(args, torch, okv, D):
         dec.close()
         e2e = run_e2e(args.config, torch=torch)
 
-    total_in = in_bytes * world
-    total_rows = rows * world
-    value = total_in / (t_max / args.steps) / 2**30
-    line = {
-        "metric": METRIC, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": desc + (", full decode (arenas + SoA)" if not index_only
-                                       else ", index-only spans"),
-                   "blocks_per_gpu": nblk, "segment_bytes_per_gpu": int(seg.nbytes),
-                   "block_bytes_per_gpu": in_bytes, "original_bytes_per_gpu": orig_bytes,
-                   "rows_per_gpu": int(rows), "mode": args.mode,
-                   "parallelism": f"{world} independent segments (no collective)"},
-        "rows_per_s": round(total_rows / (t_max / args.steps)),
-        "mrows_per_s": round(total_rows / (t_max / args.steps) / 1e6, 3),
-        "original_GiB_s": round(orig_bytes * world / (t_max / args.steps) / 2**30, 3),
-        "per_rank_ms_per_step": [round(1e3 * p / args.steps, 4) for p in per],
-        "decodes_in_flight": inflight,
-        "pass3_chained": chained,
+    line.update({
         "latency_ms_per_step": round(1e3 * t_one / args.steps, 4),
         "kernel_ms": {k: round(v, 4) for k, v in ms.items()},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
@@ -592,8 +702,7 @@ def run_decode(args, torch, okv, D):
                                if world == 1 else None)},
         "cpu_baseline": cpu,
         "verify": ver,
-        "dist": D.info(),
-    }
+    })
     if e2e:
         line["e2e"] = e2e
     emit(D, line)
@@ -685,11 +794,12 @@ def run_encode(args, torch, okv, D):
     # count/sizes and device-rehashed blocks on every rank
     eo = step()
     assert eo.n_blocks == nb and eo.data_bytes == nb * bs, (eo.n_blocks, nb)
-    hv = torch.empty(nb, dtype=torch.int64, device=dev)
-    enc._check(okv._lib.lib().okv_hash_blocks(enc._ctx, out["seg"].data_ptr(), eo.data_bytes,
-                                               out["desc"].data_ptr(), nb, hv.data_ptr(),
-                                               okv._lib.F_DEVICE_PTRS), "hash")
-    assert torch.equal(hv, out["hash"][:nb])  # the fused block hashes == a separate rehash
+    if args.full:
+        hv = torch.empty(nb, dtype=torch.int64, device=dev)
+        enc._check(okv._lib.lib().okv_hash_blocks(enc._ctx, out["seg"].data_ptr(), eo.data_bytes,
+                                                   out["desc"].data_ptr(), nb, hv.data_ptr(),
+                                                   okv._lib.F_DEVICE_PTRS), "hash")
+        assert torch.equal(hv, out["hash"][:nb])  # the fused block hashes == a separate rehash
     ver = None
     if rank == 0 and not args.no_verify:
         from oracle import coracle
@@ -713,22 +823,27 @@ def run_encode(args, torch, okv, D):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    enc.profile(True)
-    enc.profile_reset_encode()
-    t_lat, per_lat = D.timed(step, args.steps)  # one segment at a time: encode + Close latency
-    ph, calls = enc.profile_read_encode()
-    enc.profile(False)
-    ph = {k: v / max(calls, 1) for k, v in ph.items()}
-    # device-only step (no Close), for reference
-    t_dev, _ = D.timed(lambda: enc.encode_device(rows, n, out, threshold=th, block_size=bs,
-                                                 strict_go=False, close=False), args.steps)
+    inflight = max(1, args.c4_inflight)
+    if args.full:
+        enc.profile(True)
+        enc.profile_reset_encode()
+        t_lat, per_lat = D.timed(step, args.steps)  # one segment at a time: encode + Close latency
+        ph, calls = enc.profile_read_encode()
+        enc.profile(False)
+        ph = {k: v / max(calls, 1) for k, v in ph.items()}
+        # device-only step (no Close), for reference
+        t_dev, _ = D.timed(lambda: enc.encode_device(rows, n, out, threshold=th, block_size=bs,
+                                                     strict_go=False, close=False), args.steps)
+    elif inflight == 1:
+        t_lat, per_lat = D.timed(step, args.steps)
+    else:  # (the pipeline below is the timed path)
+        t_lat, per_lat = 0.0, []
     # Throughput: a writer producing consecutive segments keeps `inflight` of
     # them open -- segment k's Close (meta-block D2H + its single sequential
     # XXH64 on a host core) runs while segment k+1's cut/pack/hash/meta kernels
     # run.  Each in-flight segment has its own context, stream and output
     # buffers; a token serialises the device phases; every timed step is one
     # whole segment file, Close included.
-    inflight = max(1, args.c4_inflight)
     t_step, per = t_lat / args.steps, per_lat
     if inflight > 1:
         import threading
@@ -752,25 +867,17 @@ def run_encode(args, torch, okv, D):
                 for f in futs:
                     f.result()
         pipeline(2 * inflight)  # warm the extra contexts
-        for i in range(1, inflight):  # every in-flight buffer holds the same file
+        for i in range(1, inflight) if args.full else ():  # every buffer holds the same file
             assert torch.equal(outs[i]["seg"][:file_bytes], out["seg"][:file_bytes])
         t_pipe, per = D.timed(lambda: pipeline(args.steps), 1)
         t_step = t_pipe / args.steps
         for e_ in encs[1:]:
             e_.close()
         del outs
-    # pack kernel: read payload (16+64 B/row) + SoA (22 B/row), write the padded blocks
-    alg = n * (KL + VL) + n * 22 + data_bytes
-    achieved = alg / (ph["pack"] * 1e-3) / 1e9
-    traffic, traffic_src = pmc_traffic("c4", "encode", "okv_enc_pack_lds_kernel", ENCODE_SOURCES)
-
-    # ---- CPU baseline (rank 0, after every rank's timing has finished) ------------
-    cpu = None
-    if rank == 0 and not args.no_cpu:
-        cpu = cpu_encode_baseline(args, rows, n, th, bs)
-        if world > 1:
-            cpu["sample"] += f"; run on rank 0 of {world} after the timed region"
-
+    if args.dump_outputs:  # the segment file of the last step (every step writes the same)
+        dump_outputs(D, torch, args.dump_outputs,
+                     {"seg": out["seg"][:file_bytes], "first_row": out["first_row"][:nb + 1],
+                      "desc": out["desc"][:nb], "hash": out["hash"][:nb]}, hashes=("hash",))
     line = {
         "metric": ENC_METRIC, "value": round(data_bytes * world / t_step / 2**30, 3),
         "unit": "GiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -785,6 +892,25 @@ def run_encode(args, torch, okv, D):
         "mrows_per_s": round(total_rows / t_step / 1e6, 3),
         "per_rank_ms_per_step": [round(1e3 * p / args.steps, 4) for p in per],
         "segments_in_flight": inflight,
+        "dist": D.info(),
+    }
+    if not args.full:
+        emit(D, line)
+        enc.close()
+        return
+    # pack kernel: read payload (16+64 B/row) + SoA (22 B/row), write the padded blocks
+    alg = n * (KL + VL) + n * 22 + data_bytes
+    achieved = alg / (ph["pack"] * 1e-3) / 1e9
+    traffic, traffic_src = pmc_traffic("c4", "encode", "okv_enc_pack_lds_kernel", ENCODE_SOURCES)
+
+    # ---- CPU baseline (rank 0, after every rank's timing has finished) ------------
+    cpu = None
+    if rank == 0 and not args.no_cpu:
+        cpu = cpu_encode_baseline(args, rows, n, th, bs)
+        if world > 1:
+            cpu["sample"] += f"; run on rank 0 of {world} after the timed region"
+
+    line.update({
         "latency_ms_per_segment": round(1e3 * t_lat / args.steps, 4),
         "device_only_ms_per_step": round(1e3 * t_dev / args.steps, 4),
         "kernel_ms": {k: round(v, 4) for k, v in ph.items()},
@@ -796,8 +922,7 @@ def run_encode(args, torch, okv, D):
                      "encode_source_sha": source_sha(ENCODE_SOURCES)},
         "cpu_baseline": cpu,
         "verify": ver,
-        "dist": D.info(),
-    }
+    })
     emit(D, line)
     enc.close()
 
@@ -946,7 +1071,8 @@ def run_compact(args, torch, okv, D):
     torch.cuda.synchronize(dev)
     assert int(mo.n_rows) == n_uniq == int(mo.n_unique), (mo.n_rows, n_uniq)
     from oracle import coracle
-    for b0 in (0, (n // 2) // per_block + 3, (n + n // 4) // per_block, n_uniq // per_block - 4):
+    for b0 in ((0, (n // 2) // per_block + 3, (n + n // 4) // per_block, n_uniq // per_block - 4)
+               if args.full else ()):
         r0 = b0 * per_block
         w = coracle.Writer(th, bs)
         for r in range(r0, r0 + 3 * per_block + 1):  # +1: not Q1
@@ -957,15 +1083,39 @@ def run_compact(args, torch, okv, D):
         got = eout["seg"][b0 * bs:(b0 + 3) * bs].cpu().numpy().tobytes()
         assert got == want[:3 * bs], b0
     out_bytes = int(eo.data_bytes)
-    seg_t0, fb0, d_t0, nb0 = segs[0]  # which decode kernels the stage runs
-    enc.decode_device(seg_t0, fb0, d_t0, nb0, douts[0], sync=True)
-    dec_kernels = path_kernels(okv, enc.last_path())
+    if args.full:
+        seg_t0, fb0, d_t0, nb0 = segs[0]  # which decode kernels the stage runs
+        enc.decode_device(seg_t0, fb0, d_t0, nb0, douts[0], sync=True)
+        dec_kernels = path_kernels(okv, enc.last_path())
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
     t_max, per = D.timed(step, args.steps)  # uninstrumented
     t_step = t_max / args.steps
+    if args.dump_outputs:  # the compacted segment's data blocks and block index
+        nbo = int(eo.n_blocks)
+        dump_outputs(D, torch, args.dump_outputs,
+                     {"seg": eout["seg"][:out_bytes], "first_row": eout["first_row"][:nbo + 1],
+                      "desc": eout["desc"][:nbo], "hash": eout["hash"][:nbo]}, hashes=("hash",))
+    line = {
+        "metric": CMP_METRIC, "value": round(in_bytes * world / t_step / 2**30, 3),
+        "unit": "GiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(t_step * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": desc, "segments_per_gpu": K, "rows_in_per_gpu": n_in,
+                   "rows_out_per_gpu": n_uniq, "input_bytes_per_gpu": in_bytes,
+                   "output_data_bytes_per_gpu": out_bytes,
+                   "parallelism": f"{world} independent compactions (no collective)"},
+        "rows_per_s": round(n_in * world / t_step),
+        "mrows_per_s": round(n_in * world / t_step / 1e6, 3),
+        "per_rank_ms_per_step": [round(1e3 * p / args.steps, 4) for p in per],
+        "dist": D.info(),
+    }
+    if not args.full:
+        emit(D, line)
+        enc.close()
+        return
     enc.profile(True)  # per-pass event timing in a second run
     D.timed(step, args.steps)
     kern_ms, calls = enc.profile_read()  # the K decodes of every step
@@ -990,18 +1140,7 @@ def run_compact(args, torch, okv, D):
         if world > 1:
             cpu["sample"] += f"; run on rank 0 of {world} after the timed region"
 
-    line = {
-        "metric": CMP_METRIC, "value": round(in_bytes * world / t_step / 2**30, 3),
-        "unit": "GiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(t_step * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        "config": {"workload": desc, "segments_per_gpu": K, "rows_in_per_gpu": n_in,
-                   "rows_out_per_gpu": n_uniq, "input_bytes_per_gpu": in_bytes,
-                   "output_data_bytes_per_gpu": out_bytes,
-                   "parallelism": f"{world} independent compactions (no collective)"},
-        "rows_per_s": round(n_in * world / t_step),
-        "mrows_per_s": round(n_in * world / t_step / 1e6, 3),
-        "per_rank_ms_per_step": [round(1e3 * p / args.steps, 4) for p in per],
+    line.update({
         "stage_ms": {"decode": round(ph[0], 4), "merge": round(ph[1], 4),
                      "encode": round(ph[2], 4)},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
@@ -1010,8 +1149,7 @@ def run_compact(args, torch, okv, D):
                      "algorithmic_bytes_per_launch": int(alg / K),
                      "kernel_ms_per_step": round(gather_ms, 4)},
         "cpu_baseline": cpu,
-        "dist": D.info(),
-    }
+    })
     emit(D, line)
     enc.close()
 
@@ -1101,19 +1239,25 @@ def run_roundtrip(args, torch, okv, D):
 
     step()
     torch.cuda.synchronize(dev)
-    assert r == n and torch.equal(dout["key_arena"][:n * 16], rows["key_arena"])
-    assert torch.equal(dout["val_arena"][:n * 64], rows["val_arena"])
-    from oracle import coracle
-    host = {k: v.cpu().numpy() for k, v in rows.items()}
-    for k, dt in (("key_off", np.uint64), ("val_off", np.uint64), ("key_len", np.uint16),
-                  ("val_len", np.uint32)):
-        host[k] = host[k].view(dt)
-    want = coracle.encode_soa(host, n, th, bs)
-    assert want.rc == 0 and out["seg"][:fb].cpu().numpy().tobytes() == want.file.tobytes()
+    assert r == n
+    if args.full:
+        assert torch.equal(dout["key_arena"][:n * 16], rows["key_arena"])
+        assert torch.equal(dout["val_arena"][:n * 64], rows["val_arena"])
+        from oracle import coracle
+        host = {k: v.cpu().numpy() for k, v in rows.items()}
+        for k, dt in (("key_off", np.uint64), ("val_off", np.uint64), ("key_len", np.uint16),
+                      ("val_len", np.uint32)):
+            host[k] = host[k].view(dt)
+        want = coracle.encode_soa(host, n, th, bs)
+        assert want.rc == 0 and out["seg"][:fb].cpu().numpy().tobytes() == want.file.tobytes()
     for _ in range(args.warmup):
         step()
     t_max, per = D.timed(step, args.steps)
     t_step = t_max / args.steps
+    if args.dump_outputs:  # the segment file and its full ascending read
+        arr = decode_dump_arrays(torch, dout, r, nb, False)
+        arr.update(seg=out["seg"][:fb], desc=out["desc"][:nb])
+        dump_outputs(D, torch, args.dump_outputs, arr)
 
     cpu = None
     if rank == 0 and not args.no_cpu:  # (after every rank's timing)
@@ -1136,11 +1280,13 @@ def run_roundtrip(args, torch, okv, D):
                    "parallelism": f"{world} independent round trips (no collective)"},
         "rows_per_s": round(n * world / t_step),
         "per_rank_ms_per_step": [round(1e3 * p / args.steps, 4) for p in per],
-        "roofline": None,
-        "cpu_baseline": cpu,
-        "verify": {"verified": "segment == oracle writer; decoded arenas == input rows"},
         "dist": D.info(),
     }
+    if args.full:
+        line.update({
+            "roofline": None,
+            "cpu_baseline": cpu,
+            "verify": {"verified": "segment == oracle writer; decoded arenas == input rows"}})
     emit(D, line)
     enc.close()
 

@@ -4,7 +4,7 @@ The segment arrives in pinned host memory (as from S3 / the local disk cache
 tier) and the decoded SoA + arenas must land back in pinned host memory (for
 the Go caller).  Blocks are processed in chunks; chunk i's H2D copy, chunk
 i-1's decode and chunk i-2's D2H copies run on three streams so PCIe in both
-directions overlaps the kernels.  bench.py --e2e calls run_e2e(); standalone
+directions overlaps the kernels.  bench.py --full --e2e calls run_e2e(); standalone
 it prints one JSON line.
 
     python tools/e2e.py [--config c3] [--chunk-mib 256]

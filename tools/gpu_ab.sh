@@ -27,7 +27,7 @@ for i in $(seq 1 "$N"); do
   step "ab_A_$i" 200 python3 tools/ab_lib.py "$A" A
   step "ab_B_$i" 200 python3 tools/ab_lib.py "$B" B
 done
-step bench_c3_one 300 python3 bench.py --config c3 --no-cpu --no-verify --decode-inflight 1
-step bench_c3 300 python3 bench.py --config c3 --no-cpu --no-verify
+step bench_c3_one 300 python3 bench.py --full --config c3 --no-cpu --no-verify --decode-inflight 1
+step bench_c3 300 python3 bench.py --full --config c3 --no-cpu --no-verify
 step tile_probe 200 python3 tools/tile_probe.py 16xd7
 echo ab done

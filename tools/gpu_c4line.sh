@@ -12,8 +12,8 @@ step() {
   [ $rc -ne 0 ] && exit $rc
   return 0
 }
-step bench_c4 900 python3 bench.py --config c4
-step bench_c5 600 python3 bench.py --config c5
-step bench_c2 600 python3 bench.py --config c2
-step bench_c1 600 python3 bench.py --config c1
+step bench_c4 900 python3 bench.py --full --config c4
+step bench_c5 600 python3 bench.py --full --config c5
+step bench_c2 600 python3 bench.py --full --config c2
+step bench_c1 600 python3 bench.py --full --config c1
 echo "c4line done"

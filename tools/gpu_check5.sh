@@ -14,5 +14,5 @@ step() {
 }
 step pytest 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-step bench_c4 600 python3 bench.py --config c4 --no-cpu
+step bench_c4 600 python3 bench.py --full --config c4 --no-cpu
 echo "check5 done"

@@ -8,7 +8,7 @@ OKV_ABLATE=1 OKV_SMALL_PIECE_MB=1 timeout -k 10 400 python -u -m pytest tests/te
 rc=$?; echo "[tests, 1 MiB pieces] exit $rc: $(tail -1 $O/tests.log)"; [ $rc -ne 0 ] && exit $rc
 for r in 1 2; do
 for mb in 0 48 96 192 384; do
-  OKV_ABLATE=1 OKV_SMALL_PIECE_MB=$mb timeout -k 10 300 python3 bench.py --config cm --no-cpu --steps 10 --warmup 2 > $O/mb_${mb}_$r.log 2>&1
+  OKV_ABLATE=1 OKV_SMALL_PIECE_MB=$mb timeout -k 10 300 python3 bench.py --full --config cm --no-cpu --steps 10 --warmup 2 > $O/mb_${mb}_$r.log 2>&1
   rc=$?; echo "[piece $mb MiB run $r] exit $rc $(grep -o '"stage_ms": {[^}]*}\|"frac": [0-9.]*\|"value": [0-9.]*' $O/mb_${mb}_$r.log | tr '\n' ' ')"; [ $rc -ne 0 ] && exit $rc
 done
 done

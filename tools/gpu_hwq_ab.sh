@@ -6,9 +6,9 @@ O=gpurun_out/hwq; mkdir -p $O
 for r in 1 2 3; do
   for q in def 8; do
     if [ $q = def ]; then
-      timeout -k 10 300 python3 bench.py --config c3 --no-cpu --no-verify --steps 40 --warmup 5 > $O/${q}_$r.log 2>&1
+      timeout -k 10 300 python3 bench.py --full --config c3 --no-cpu --no-verify --steps 40 --warmup 5 > $O/${q}_$r.log 2>&1
     else
-      GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python3 bench.py --config c3 --no-cpu --no-verify --steps 40 --warmup 5 > $O/${q}_$r.log 2>&1
+      GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python3 bench.py --full --config c3 --no-cpu --no-verify --steps 40 --warmup 5 > $O/${q}_$r.log 2>&1
     fi
     rc=$?; echo "[$q run $r] exit $rc $(grep -o '"ms_per_step": [0-9.]*\|"latency_ms_per_step": [0-9.]*' $O/${q}_$r.log | tr '\n' ' ')"
     [ $rc -ne 0 ] && exit $rc

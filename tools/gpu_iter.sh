@@ -22,7 +22,7 @@ step() {
 }
 step pytest_gpu 600 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 [ $# -gt 0 ] && step ablate 400 python3 tools/ablate_tile.py "$@"
-step bench_c3 300 python3 bench.py --config c3 --no-cpu
-step bench_c3_one 300 python3 bench.py --config c3 --no-cpu --no-verify --decode-inflight 1
+step bench_c3 300 python3 bench.py --full --config c3 --no-cpu
+step bench_c3_one 300 python3 bench.py --full --config c3 --no-cpu --no-verify --decode-inflight 1
 step tile_probe 200 python3 tools/tile_probe.py 16xd7
 echo iter done

@@ -15,7 +15,7 @@ for r in $(seq 1 $ROUNDS); do
   for L in "$@"; do
     cp "$L" objectkv_amd/libokv_sst.so
     n=$(basename "$L" .so)
-    timeout -k 10 300 python3 bench.py $BARGS > $O/${n}_$r.log 2>&1
+    timeout -k 10 300 python3 bench.py --full $BARGS > $O/${n}_$r.log 2>&1
     rc=$?; echo "[$n run $r] exit $rc $(grep -o '"value": [0-9.]*\|"stage_ms": {[^}]*}\|"kernel_ms": {[^}]*}\|"frac": [0-9.]*' $O/${n}_$r.log | head -4 | tr '\n' ' ')"
     [ $rc -ne 0 ] && exit $rc
   done

@@ -13,7 +13,7 @@ mkdir -p "$D"
 P=29517
 for c in ${*:-c3 c5 c4}; do
   timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port $P bench.py --gpus 2 --steps 5 --warmup 1 \
+    --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus 2 --steps 5 --warmup 1 \
     --device-mod 1 --dist-backend gloo --config "$c" > "$D/rehearse_2ranks_1gpu_gloo_$c.log" 2>&1
   rc=$?
   echo "[rehearse $c] exit $rc"

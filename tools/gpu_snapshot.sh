@@ -23,10 +23,10 @@ step() {  # step <name> <seconds> <cmd...>: run, log, stop the script on failure
   return 0
 }
 step c3_trace 300 rocprofv3 --kernel-trace --stats -d "$OUT/c3_trace" -o run --output-format csv \
-  -- python3 "$R/bench.py" --config c3 --steps 20 --warmup 5 --no-cpu --no-verify --decode-inflight 1
+  -- python3 "$R/bench.py" --full --config c3 --steps 20 --warmup 5 --no-cpu --no-verify --decode-inflight 1
 step tile_probe 200 python3 tools/tile_probe.py 16xd7
 for c in c4 cz cm c5; do
-  step "bench_$c" 300 python3 bench.py --config $c --no-cpu
+  step "bench_$c" 300 python3 bench.py --full --config $c --no-cpu
 done
 "$R/tools/gpu_profile.sh" "$TAG/c4prof" c4 --c4-inflight 1 || exit 1
 echo snapshot done

@@ -11,7 +11,7 @@ for L in product "$@"; do
   timeout -k 10 300 python -u -m pytest tests/test_zstd_gpu.py -m gpu -q --timeout 200 > $O/t_$n.log 2>&1
   rc=$?; echo "[$n] tests exit $rc: $(tail -1 $O/t_$n.log)"; [ $rc -gt 1 ] && exit $rc
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/tr_$n -o run --output-format csv \
-    -- python3 "$R/bench.py" --config cz --steps 10 --warmup 2 --no-cpu --no-verify --decode-inflight 1 > $O/b_$n.log 2>&1
+    -- python3 "$R/bench.py" --full --config cz --steps 10 --warmup 2 --no-cpu --no-verify --decode-inflight 1 > $O/b_$n.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "[$n] trace exit $rc"; exit $rc; }
   f=$(find $O/tr_$n -name run_kernel_stats.csv | head -1)
   echo "[$n] $(grep -h 'huf_kernel\|pro_kernel' $f | cut -d, -f1-4 | tr '\n' ' ') | $(grep -o '"zstd": [0-9.]*' $O/b_$n.log)"

@@ -4,7 +4,7 @@
 # only, over any python command; then the 4 GiB calibration kernels of
 # tools/copybw3 cal (known byte counts).  Summarise with tools/pmc_summary.py.
 #   tools/pmc_run.sh <tag> <python args...>
-#   e.g. tools/pmc_run.sh r2_pmc bench.py --steps 3 --warmup 1 --no-cpu
+#   e.g. tools/pmc_run.sh r2_pmc bench.py --full --steps 3 --warmup 1 --no-cpu
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" || exit 1
 export TMPDIR=/tmp

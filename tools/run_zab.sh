@@ -13,6 +13,6 @@ for r in 1 2; do
     ZP_LIB=$L step "prof_$(basename $L .so)_$r" 200 python3 tools/zstd_prof.py 16384
   done
 done
-step bench_cz 300 python3 bench.py --config cz --no-cpu
+step bench_cz 300 python3 bench.py --full --config cz --no-cpu
 [ -n "$FULL" ] && step pytest_gpu 600 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 echo zab done

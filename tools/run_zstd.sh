@@ -7,7 +7,7 @@ T=${1:-r3g}; O=gpurun_out/$T; mkdir -p $O
 step() { local n=$1 s=$2; shift 2; timeout -k 10 $s "$@" > $O/$n.log 2>&1; local rc=$?; echo "[$n] exit $rc"; tail -3 $O/$n.log | cut -c1-400; [ $rc -ne 0 ] && exit $rc; return 0; }
 step pytest_zstd 300 python3 -u -m pytest tests/test_zstd_gpu.py -m gpu -x -q --timeout 200 --timeout-method thread
 step pytest_gpu 600 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
-step bench_cz 300 python3 bench.py --config cz --no-cpu
+step bench_cz 300 python3 bench.py --full --config cz --no-cpu
 OKV_ABLATE=1 step zstd_prof 300 python3 tools/zstd_prof.py 16384
 
 echo r3g done
