@@ -1183,27 +1183,35 @@ __global__ __launch_bounds__(64) void okv_gather_small_kernel(CopyParams P) {
 }
 
 // Single-pass decode for small batches of small blocks (<= kFusedMaxBlocks
-// blocks averaging <= 16 KiB): passes 1-3 in ONE launch.  One wave per block
-// takes the next block index from a counter, DMAs the whole block into LDS,
-// walks its record headers there exactly as the Go loop does (lane 0;
-// statuses as in okv_count_kernel) and publishes the block's (rows, key
-// bytes, value bytes, bad); the block whose arrival is counted last scans all
-// of them and publishes every block's exclusive prefix (sc1 stores and loads,
-// flags tagged with the call's epoch so nothing is reset between calls);
-// every block then gathers its rows from its stage.  (A decoupled look-back
-// measured slower: its chain deepens with the blocks in flight.)  Blocks with more than kRCap rows, or too
-// large to stage, get their counts the same way (a global-memory walk) and go
-// to okv_copy_kernel through the big-block list, with cnt / lp / tile_pre
+// blocks averaging <= 16 KiB): passes 1-3 in ONE launch.  One wave per block,
+// the block index from blockIdx.x: it DMAs the whole block into LDS, walks its
+// record headers there as the Go loop does (walk_staged; statuses as in
+// okv_count_kernel) and publishes the block's counts with the call's epoch
+// tag in one packed 8-byte look-back word (fused_pack; counts that do not fit
+// go through F.agg[b]).  Its exclusive prefix is the sum of the words of all
+// the blocks before it, every lane polling up to kFusedMaxBlocks / 64 of
+// them; then it gathers its rows from its stage.  No arrival counter, no scan
+// by the last arrival, and -- the tag making every call's words fresh -- no
+// reset between calls.  Blocks with more than kRCap rows, or too large to
+// stage, get their counts the same way (a global-memory walk) and go to
+// okv_copy_kernel through the big-block list, with cnt / lp / tile_pre
 // written as passes 1-2 would.
-constexpr uint32_t kFusedMaxBlocks = 512;  // every block of the grid resident at once
+// Precondition (kept by okv_open's fused_max): the whole grid is resident at
+// once and dispatched in index order.  A block spins on the words of lower
+// indices only, which is safe only if those blocks have started: a grid past
+// the device's resident capacity, or dispatched out of order, could leave the
+// resident blocks spinning on ones that never start.
+constexpr uint32_t kFusedMaxBlocks = 512;
 struct FusedParams {
   const int32_t* pre;     // zstd-stage statuses or null
   BlockCount* cnt;        // what passes 1-2 write, for okv_copy_kernel
   Prefix* lp;
   Prefix* tile_pre;
-  uint32_t* flag;         // [nblk] (epoch << 2) | 1 aggregate, | 2 inclusive
+  uint32_t* flag;         // [nblk] 8-byte look-back words (fused_pack); the stream arm's flags:
+                          // (epoch << 2) | 1 aggregate, | 2 inclusive
   Prefix* agg;            // [nblk]
   Prefix* incl;           // [nblk]
+  // (the stream and block arms of the ablation build only; the fused kernel reads none)
   unsigned long long* ctr;  // block-index counter (monotone across calls)
   unsigned long long* arr;  // arrival counter (monotone across calls, same base)
   unsigned long long base;  // its value at this call's start
@@ -1249,11 +1257,11 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
   return v;
 }
 
-// kLB: the form for batches of any size (okv_decode_stream_kernel below):
-// the exclusive prefix by a decoupled look-back instead of the last arrival's
-// scan, so no block waits for blocks that may not be resident.
-// The exclusive prefix by a decoupled look-back: the ablation build's stream
-// kernel (okv_decode_ablate_lb.inc); declared here, defined only there.
+// fused_pass<kLB = true> is the ablation build's stream kernel
+// (okv_decode_ablate_lb.inc), for batches of any size: block indices by
+// arrival and the exclusive prefix by this decoupled look-back, so no block
+// waits for one that may not be resident.  Declared here, defined only there;
+// the product kernel is fused_pass<false>, which never calls it.
 __device__ Prefix fused_prefix_lookback(const CopyParams& P, const FusedParams& F, uint32_t b,
                                         uint32_t lane, uint32_t tag, const Prefix& mine);
 #ifdef OKV_ABLATE
@@ -2261,12 +2269,9 @@ int ensure_blocks(okv_ctx* ctx, uint32_t nblk) {
   const size_t ntiles = (n + kTile - 1) / kTile;
   if (ctx->d_cnt) {
     OKV_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->d_cnt);
-    (void)hipFree(ctx->d_lp);
-    (void)hipFree(ctx->d_tile_tot);
-    (void)hipFree(ctx->d_tile_pre);
-    (void)hipFree(ctx->d_rec);
-    (void)hipFree(ctx->d_big);
+    for (void* p : std::initializer_list<void*>{ctx->d_cnt, ctx->d_lp, ctx->d_tile_tot,
+                                                ctx->d_tile_pre, ctx->d_rec, ctx->d_big})
+      (void)hipFree(p);
   }
   if (!ctx->d_ctr) {
     OKV_HIP(hipMalloc(&ctx->d_ctr, 64));
@@ -2333,10 +2338,9 @@ int prepare(okv_ctx* ctx, const uint8_t* d_seg, uint64_t seg_bytes, const Desc* 
   int rc;
   if (nblk + 1 > ctx->z_cap_blocks || !ctx->z_cap_off) {
     OKV_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->z_cap_off);
-    (void)hipFree(ctx->z_dec_len);
-    (void)hipFree(ctx->z_status);
-    (void)hipFree(ctx->z_desc);
+    for (void* p : std::initializer_list<void*>{ctx->z_cap_off, ctx->z_dec_len, ctx->z_status,
+                                                ctx->z_desc})
+      (void)hipFree(p);
     const size_t n = size_t(nblk) + 1;
     OKV_HIP(hipMalloc(&ctx->z_cap_off, n * 8));
     OKV_HIP(hipMalloc(&ctx->z_dec_len, n * 8));
@@ -2362,19 +2366,31 @@ int prepare(okv_ctx* ctx, const uint8_t* d_seg, uint64_t seg_bytes, const Desc* 
 // nblk: it assumes the blocks tile the segment, which holds for whole-segment
 // decodes; a caller decoding a few blocks of a large segment gets the
 // 256-thread form, which is correct for any block size).
-uint32_t gather_threads(const okv_ctx* ctx, const Work& w, uint32_t nblk) {
-  if (ctx->gather_threads) return ctx->gather_threads;
+uint32_t gather_threads(const Work& w, uint32_t nblk) {
   return nblk && w.seg_bytes / nblk <= 16384 ? 64u : 256u;
 }
 
-// Launch passes 1 and 2 on device inputs.  rt_kl: record key lengths for the
-// tile pass (null: positions only); span_cap: blocks whose walk ends past it
-// go to the big-block list.
+// Tile-pass geometry (okv_tile_kernel): tiles per block from the call's
+// average block span, rounded down to 4 KiB (a segment's meta block and
+// trailer add far less than that per block); blocks whose walk ends past
+// tpb tiles are big blocks (okv_copy_kernel).  Index-only decodes write only
+// the row index: one workgroup per block, no span limit.
+struct TileGeo {
+  uint32_t tpb;
+  uint64_t span_cap;
+};
+constexpr uint32_t kTileBytes = 16384;  // the product tile pass's source tile
+
+// The ablation build's hooks into the functions below (okv_decode_ablate_host.inc).
+[[maybe_unused]] int ablate_count_prefetch(int prefetch, uint32_t nblk);
+[[maybe_unused]] void ablate_launch_tile(okv_ctx* ctx, const CopyParams& P, const TileGeo& g);
+
+// Launch passes 1 and 2 on device inputs (the caller has run ensure_blocks).
+// rt_kl: record key lengths for the tile pass (null: positions only);
+// span_cap: blocks whose walk ends past it go to the big-block list.
 int launch_plan(okv_ctx* ctx, const Work& w, uint32_t nblk, uint64_t* d_row_start,
                 bool timed = false, uint16_t* rt_kl = nullptr, uint64_t span_cap = ~0ull,
                 unsigned long long* span_max = nullptr) {
-  int rc = ensure_blocks(ctx, nblk);
-  if (rc) return rc;
   // one launch: the count walk, and the tile-total scan by its last workgroup
   // (an empty batch still runs one workgroup: it writes the zero totals)
   const uint32_t ntiles = std::max<uint32_t>(1, (nblk + kTile - 1) / kTile);
@@ -2382,7 +2398,7 @@ int launch_plan(okv_ctx* ctx, const Work& w, uint32_t nblk, uint64_t* d_row_star
   // and blocks are small (dense headers); 64 KiB blocks touch ~5 % of their lines
   int prefetch = nblk && w.seg_bytes <= (64ull << 20) && w.seg_bytes / nblk <= 16384;
 #ifdef OKV_ABLATE
-  if (const char* v = getenv("OKV_COUNT_PREFETCH")) prefetch = atoi(v) && nblk;  // A/B
+  prefetch = ablate_count_prefetch(prefetch, nblk);  // OKV_COUNT_PREFETCH A/B
 #endif
   hipLaunchKernelGGL(okv_count_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, w.seg,
                      w.seg_bytes, w.descs, nblk, w.comp, ctx->d_cnt, ctx->d_lp, ctx->d_tile_tot,
@@ -2395,21 +2411,11 @@ int launch_plan(okv_ctx* ctx, const Work& w, uint32_t nblk, uint64_t* d_row_star
   return OKV_OK;
 }
 
-// Tile-pass geometry (okv_tile_kernel): tiles per block from the call's
-// average block span, rounded down to 4 KiB (a segment's meta block and
-// trailer add far less than that per block); blocks whose walk ends past
-// tpb tiles are big blocks (okv_copy_kernel).  Index-only decodes write only
-// the row index: one workgroup per block, no span limit.
-struct TileGeo {
-  uint32_t tpb;
-  uint64_t span_cap;
-};
-// Tiles per block from the average block span, or from the longest walk the
-// last okv_decode_plan of the same batch measured (blocks longer than the span
-// go to okv_copy_kernel: with bimodal block sizes most bytes would).
-TileGeo tile_geo(const okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_only) {
+// ... or from the longest walk the last okv_decode_plan of the same batch
+// measured (with bimodal block sizes most bytes would be big blocks' otherwise).
+TileGeo tile_geo(const okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_only,
+                 uint64_t tile = kTileBytes) {
   if (index_only || !nblk) return {1, ~0ull};
-  const uint64_t kT = uint64_t(ctx->tile_kib) << 10;
   uint64_t span = (w.seg_bytes / nblk) & ~uint64_t(4095);
   if (span < 4096) span = 4096;
   const SpanHint& h = ctx->span_hint;
@@ -2417,75 +2423,125 @@ TileGeo tile_geo(const okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_on
     span = std::max<uint64_t>(span, (h.span + 4095) & ~uint64_t(4095));
   // (the hint is consumed by the decode that uses it -- decode_device clears
   // it -- so a later batch staged into the same buffers is not sized by it)
-  uint64_t tpb = std::min<uint64_t>(64, (span + kT - 1) / kT);
+  uint64_t tpb = std::min<uint64_t>(64, (span + tile - 1) / tile);
   while (tpb > 1 && uint64_t(nblk) * tpb >= (uint64_t(1) << 31)) tpb >>= 1;
-  return {uint32_t(tpb), tpb * kT};
+  return {uint32_t(tpb), tpb * tile};
 }
 
-template <uint32_t kT, uint32_t kNT, bool kXcd, int kDiag>
-void launch_tile_t(hipStream_t s, const CopyParams& P, uint32_t tpb, uint32_t ntile) {
-  const uint32_t grid = kXcd ? ((ntile + 7u) & ~7u) : ntile;
-#ifdef OKV_ABLATE
-  if constexpr (kDiag == 9) {
-    hipLaunchKernelGGL((okv_tile_kernel_w7<kT, kNT, kXcd>), dim3(grid), dim3(kNT), 0, s, P, tpb,
-                       ntile);
-    return;
-  } else if constexpr (kDiag >= 32) {
-    hipLaunchKernelGGL((okv_tile_kernel_skip<kT, kNT, kXcd, uint32_t(kDiag - 32)>), dim3(grid),
-                       dim3(kNT), 0, s, P, tpb, ntile);
-  } else {
-    hipLaunchKernelGGL((okv_tile_kernel_diag<kT, kNT, kXcd, kDiag>), dim3(grid), dim3(kNT), 0, s,
-                       P, tpb, ntile);
-  }
-#else
-  static_assert(kDiag == 0, "the product library has no diagnostic arms");
-  hipLaunchKernelGGL((okv_tile_kernel<kT, kNT, kXcd>), dim3(grid), dim3(kNT), 0, s, P, tpb, ntile);
-#endif
-}
-typedef void (*TileLaunch)(hipStream_t, const CopyParams&, uint32_t, uint32_t);
-struct TileForm {
-  uint32_t kib, threads, diag;
-  TileLaunch x, plain;
-};
-#define OKV_TILE_FORM(K, N, D)                                                              \
-  TileForm {                                                                                \
-    K, N, D, launch_tile_t<K * 1024, N, true, D>, launch_tile_t<K * 1024, N, false, D>      \
-  }
-#ifdef OKV_ABLATE
-const TileForm kTileForms[] = {OKV_TILE_FORM(16, 256, 0), OKV_TILE_FORM(8, 256, 0),
-                               OKV_TILE_FORM(32, 256, 0), OKV_TILE_FORM(16, 512, 0),
-                               OKV_TILE_FORM(32, 512, 0), OKV_TILE_FORM(4, 256, 0),
-                               OKV_TILE_FORM(16, 256, 1), OKV_TILE_FORM(16, 256, 2),
-                               OKV_TILE_FORM(16, 256, 3), OKV_TILE_FORM(16, 256, 4),
-                               OKV_TILE_FORM(16, 256, 5), OKV_TILE_FORM(16, 256, 6),
-                               OKV_TILE_FORM(16, 256, 7), OKV_TILE_FORM(16, 256, 8),
-                               OKV_TILE_FORM(8, 256, 8), OKV_TILE_FORM(32, 512, 8),
-                               OKV_TILE_FORM(16, 256, 9), OKV_TILE_FORM(64, 1024, 0),
-                               OKV_TILE_FORM(64, 512, 0),
-                               // write attribution (okv_tile_kernel_skip): d32 + kSkip
-                               OKV_TILE_FORM(16, 256, 32), OKV_TILE_FORM(16, 256, 33),
-                               OKV_TILE_FORM(16, 256, 34), OKV_TILE_FORM(16, 256, 36),
-                               OKV_TILE_FORM(16, 256, 40), OKV_TILE_FORM(16, 256, 48),
-                               OKV_TILE_FORM(16, 256, 63),
-                               // value cuts on 128-byte lines (tile_pass kSkip 64)
-                               OKV_TILE_FORM(16, 256, 96),
-                               // whole 64-byte sectors per store (tile_pass kSkip 128)
-                               OKV_TILE_FORM(16, 256, 160), OKV_TILE_FORM(16, 256, 672),
-                               OKV_TILE_FORM(16, 256, 928)};
-const TileForm* tile_form(uint32_t kib, uint32_t threads, uint32_t diag) {
-  for (const TileForm& f : kTileForms)
-    if (f.kib == kib && f.threads == threads && f.diag == diag) return &f;
-  return nullptr;
-}
-#endif
+// The tile pass over P's blocks: kTileBytes source tiles, 256 threads,
+// consecutive tiles on one XCD (the grid padded to a multiple of 8).
 void launch_tile(okv_ctx* ctx, const CopyParams& P, const TileGeo& g) {
 #ifdef OKV_ABLATE
-  const TileForm* f = tile_form(ctx->tile_kib, ctx->tile_threads, ctx->tile_diag);
-  (ctx->tile_xcd ? f->x : f->plain)(ctx->stream, P, g.tpb, P.nblk * g.tpb);
+  ablate_launch_tile(ctx, P, g);  // the OKV_TILE form (default: okv_tile_kernel_diag<.., 0>)
 #else
-  // the product form: 16 KiB source tiles, 256 threads, XCD-grouped, value runs
-  launch_tile_t<16384, 256, true, 0>(ctx->stream, P, g.tpb, P.nblk * g.tpb);
+  const uint32_t ntile = P.nblk * g.tpb;
+  hipLaunchKernelGGL((okv_tile_kernel<kTileBytes, 256, true>), dim3((ntile + 7u) & ~7u),
+                     dim3(256), 0, ctx->stream, P, g.tpb, ntile);
 #endif
+}
+
+// The record key lengths pass 1 leaves for the tile pass (count kernel rt_kl).
+int ensure_hdr(okv_ctx* ctx, uint32_t nblk, uint16_t** rt_kl) {
+  int rc = grow(ctx, &ctx->d_hdr, &ctx->cap_hdr, size_t(nblk) * kRCap * 2);
+  *rt_kl = static_cast<uint16_t*>(ctx->d_hdr);
+  return rc;
+}
+
+// Look-back scratch of a single-pass decode: n flags of flag_bytes each,
+// zeroed once (the epoch tag makes every call's flags fresh), and n aggregate
+// and inclusive prefixes.
+int ensure_lookback(okv_ctx* ctx, size_t n, size_t flag_bytes, uint32_t** flag, Prefix** agg,
+                    Prefix** incl, size_t* cap) {
+  n = std::max<size_t>(n, 1);
+  if (n <= *cap && *flag) return OKV_OK;
+  if (*flag) {
+    OKV_HIP(hipStreamSynchronize(ctx->stream));
+    for (void* p : std::initializer_list<void*>{*flag, *agg, *incl}) (void)hipFree(p);
+    *flag = nullptr;
+  }
+  OKV_HIP(hipMalloc(flag, n * flag_bytes));
+  OKV_HIP(hipMemsetAsync(*flag, 0, n * flag_bytes, ctx->stream));
+  OKV_HIP(hipMalloc(agg, n * sizeof(Prefix)));
+  OKV_HIP(hipMalloc(incl, n * sizeof(Prefix)));
+  *cap = n;
+  return OKV_OK;
+}
+
+// Scratch of okv_decode_fused_kernel: one 8-byte look-back word per block (the
+// ablation stream kernel uses the first 4 bytes per block as its flags).
+int ensure_fused(okv_ctx* ctx, uint32_t nblk) {
+  const int rc = ensure_lookback(ctx, nblk, sizeof(uint64_t), &ctx->f_flag, &ctx->f_agg,
+                                 &ctx->f_incl, &ctx->f_cap);
+  if (rc || ctx->f_ctr) return rc;
+  OKV_HIP(hipMalloc(&ctx->f_ctr, 2 * sizeof(unsigned long long)));  // blocks, arrivals
+  OKV_HIP(hipMemsetAsync(ctx->f_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  ctx->f_base = 0;
+  return OKV_OK;
+}
+
+// Pass-3 parameters of a device-pointer decode.  big_count is this decode's
+// big-block counter slot: call before the launch that flips big_slot.
+CopyParams copy_params(okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_only,
+                       uint16_t* rt_kl, uint64_t span_cap, const okv_decode_out& o) {
+  CopyParams P = {};  // (vsrc, vtile, bchunk: null -- the ablation sweep's)
+  P.seg = w.seg;
+  P.seg_bytes = w.seg_bytes;
+  P.descs = w.descs;
+  P.nblk = nblk;
+  P.comp = w.comp;
+  P.index_only = index_only ? 1 : 0;
+  P.rt_pos = ctx->d_rec;
+  P.rt_kl = rt_kl;
+  P.span_cap = span_cap;
+  P.big_list = ctx->d_big;
+  P.big_count = big_counter(ctx);
+  P.cnt = ctx->d_cnt;
+  P.lp = ctx->d_lp;
+  P.tile_pre = ctx->d_tile_pre;
+  P.row_start = o.row_start;
+  P.key_base = o.key_base;
+  P.val_base = o.val_base;
+  P.blk_status = o.blk_status;
+  P.key_off = o.key_off;
+  P.key_len = o.key_len;
+  P.val_off = o.val_off;
+  P.val_len = o.val_len;
+  P.key_arena = o.key_arena;
+  P.val_arena = o.val_arena;
+  P.row_cap = o.row_cap;
+  P.key_cap = index_only ? 0 : o.key_cap;
+  P.val_cap = index_only ? 0 : o.val_cap;
+  P.tot = ctx->d_tot;
+  return P;
+}
+
+// Parameters of the single-pass kernels; starts the call's epoch.
+FusedParams fused_params(okv_ctx* ctx, const Work& w) {
+  ctx->f_epoch = (ctx->f_epoch + 1) & 0x3fffffffu;
+  return FusedParams{w.pre,       ctx->d_cnt,  ctx->d_lp,     ctx->d_tile_pre,    ctx->f_flag,
+                     ctx->f_agg,  ctx->f_incl, ctx->f_ctr,    ctx->f_ctr + 1,     ctx->f_base,
+                     ctx->f_epoch, ctx->d_tot, big_counter(ctx, 1)};
+}
+
+// The big-block kernel: the blocks of the big-block list (more than kRCap
+// rows, or a walk past the tile span), a no-op grid when the list is empty.
+void launch_big(okv_ctx* ctx, const CopyParams& P) {
+  const uint32_t grid = std::min<uint32_t>(P.nblk, 512);
+  if (P.index_only)
+    hipLaunchKernelGGL(okv_index_kernel, dim3((grid + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                       ctx->stream, P);
+  else
+    hipLaunchKernelGGL(okv_copy_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, P);
+}
+
+// okv_decode_chain: pass 3 after the chained context's last pass 3.  (A
+// shared pass-3 stream for chained contexts instead of this event wait
+// measured slower: C5 0.407 vs 0.396 ms, C3 1.465 vs 1.449 ms per step with
+// decodes in flight, profiles/r6/session/pass3_queue_ab.log.)
+int chain_wait(okv_ctx* ctx) {
+  if (ctx->chain && ctx->chain->p3_rec)
+    OKV_HIP(hipStreamWaitEvent(ctx->stream, ctx->chain->p3_done, 0));
+  return OKV_OK;
 }
 
 int read_totals(okv_ctx* ctx, Totals* out) {
@@ -2496,35 +2552,60 @@ int read_totals(okv_ctx* ctx, Totals* out) {
   return OKV_OK;
 }
 
-// Scratch of the single-pass small-block decode (flags zeroed once; the epoch
-// tag makes every call's flags fresh).
-int ensure_fused(okv_ctx* ctx, uint32_t nblk) {
-  const size_t n = std::max<size_t>(nblk, 1);
-  if (n <= ctx->f_cap && ctx->f_flag) return OKV_OK;
-  if (ctx->f_flag) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->f_flag);
-    (void)hipFree(ctx->f_agg);
-    (void)hipFree(ctx->f_incl);
+// A decode's totals into the caller's okv_decode_out; false when they exceed
+// its capacities (index-only decodes have no arenas).
+bool totals_fit(const Totals& T, bool index_only, okv_decode_out* o) {
+  o->n_rows = T.rows;
+  o->key_bytes = index_only ? 0 : T.kb;
+  o->val_bytes = index_only ? 0 : T.vb;
+  o->n_bad_blocks = T.bad;
+  return T.rows <= o->row_cap && (index_only || (T.kb <= o->key_cap && T.vb <= o->val_cap));
+}
+
+// After the pass-3 launches: the event chained contexts wait for, the last
+// profile mark and, unless the call is OKV_F_ASYNC, the totals.
+int finish_decode(okv_ctx* ctx, okv_decode_out* o, uint32_t flags) {
+  if (ctx->p3_done) {
+    OKV_HIP(hipEventRecord(ctx->p3_done, ctx->stream));
+    ctx->p3_rec = true;
   }
-  // (8 bytes per block: the fused kernel's look-back words; the ablation
-  // stream kernel uses the first 4 bytes per block as its flags)
-  OKV_HIP(hipMalloc(&ctx->f_flag, n * sizeof(uint64_t)));
-  OKV_HIP(hipMemsetAsync(ctx->f_flag, 0, n * sizeof(uint64_t), ctx->stream));
-  OKV_HIP(hipMalloc(&ctx->f_agg, n * sizeof(Prefix)));
-  OKV_HIP(hipMalloc(&ctx->f_incl, n * sizeof(Prefix)));
-  if (!ctx->f_ctr) {
-    OKV_HIP(hipMalloc(&ctx->f_ctr, 2 * sizeof(unsigned long long)));  // blocks, arrivals
-    OKV_HIP(hipMemsetAsync(ctx->f_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    ctx->f_base = 0;
-  }
-  ctx->f_cap = n;
+  prof_mark(ctx, 4);
+  if (flags & OKV_F_ASYNC) return OKV_OK;
+  Totals T;
+  const int rc = read_totals(ctx, &T);
+  if (rc) return rc;
+  if (!totals_fit(T, flags & OKV_F_INDEX_ONLY, o))
+    return set_err(ctx, OKV_E_CAPACITY, "output capacity too small (totals set)");
   return OKV_OK;
 }
 
-#ifdef OKV_ABLATE  // the measured alternative forms of round 4 (ablation build only)
+// okv_last_path of a decode: the compression stage's bits and the kernels'.
+uint32_t path_bits(const okv_ctx* ctx, int comp, bool index_only, uint32_t kernels) {
+  return (comp ? OKV_PATH_ZSTD : 0u) |
+         (comp == OKV_COMP_ZSTD && !index_only && ctx->z_retried ? OKV_PATH_ZSTD_REGROW : 0u) |
+         kernels;
+}
+
+#ifdef OKV_ABLATE  // the measured alternative forms and their knobs (ablation build only)
 #include "okv_decode_ablate_host.inc"
 #endif
+
+// The product's decode routes; each value is the route's okv_last_path bits.
+// Every route but kEmpty ends with the big-block kernel (launch_big).
+enum class Route : uint32_t {
+  kEmpty = 0,                              // no blocks: the count launch writes the zero totals
+  kFused = OKV_PATH_FUSED,                 // passes 1-3 in one launch (okv_decode_fused_kernel)
+  kSmall = OKV_PATH_BIG | OKV_PATH_SMALL,  // count, then okv_gather_small_kernel
+  kTile = OKV_PATH_BIG | OKV_PATH_TILE,    // count, then okv_tile_kernel
+};
+// Blocks averaging more than 16 KiB take the tile pass; small blocks the fused
+// kernel while the batch fits its resident grid (fused_max; a context opened
+// with OKV_OPEN_NO_FUSED never), else the count launch and the small gather.
+Route select_route(const okv_ctx* ctx, const Work& w, uint32_t nblk) {
+  if (!nblk) return Route::kEmpty;
+  if (gather_threads(w, nblk) == 256) return Route::kTile;
+  return ctx->fused && nblk <= ctx->fused_max ? Route::kFused : Route::kSmall;
+}
 
 int decode_device(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
                   uint32_t nblk, int comp, okv_decode_out* o, uint32_t flags) {
@@ -2538,335 +2619,61 @@ int decode_device(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const De
   int rc = prepare(ctx, seg, seg_bytes, descs, nblk, comp, index_only, &w);
   if (rc) return rc;
   prof_mark(ctx, 1);
-  // small blocks: passes 1-3 in one launch (okv_decode_fused_kernel)
-  const bool fused =
-      ctx->fused && nblk && nblk <= ctx->fused_max && gather_threads(ctx, w, nblk) == 64;
-  // (ablation build, OKV_DECODE_STREAM=1: larger batches of small blocks in
-  // the same single pass with the prefix by decoupled look-back,
-  // okv_decode_stream_kernel -- measured 9.2 vs 1.38 ms per CM segment of
-  // 386 K blocks: every block's look-back walks back to an inclusive frontier
-  // that lags by the blocks in flight; the product runs passes 1-3)
 #ifdef OKV_ABLATE
-  const bool stream = ctx->stream_lb && ctx->fused && nblk > ctx->fused_max &&
-                      gather_threads(ctx, w, nblk) == 64;
-#else
-  constexpr bool stream = false;
+  if (ctx->ab.active) return ablate_decode(ctx, w, nblk, comp, o, flags);  // a knob selects an arm
 #endif
-  // large blocks: the source-tile pass (okv_tile_kernel); value_sweep 1-7 are
-  // the round-2 forms (row pass + address-ordered value sweep)
-  const bool large = nblk && !fused && !stream && gather_threads(ctx, w, nblk) == 256;
-  // (ablation build, OKV_DECODE_GROUP=1: small blocks past the fused batch in
-  // the grouped single pass, okv_group_kernel -- measured slower than passes
-  // 1-3: CM decode stage 5.9-6.8 vs 4.1 ms)
-#ifdef OKV_ABLATE
-  const bool group = ctx->group && nblk && !fused && !stream && !large && !index_only;
-#else
-  constexpr bool group = false;
-#endif
-#ifdef OKV_ABLATE
-  // OKV_VALUE_SWEEP=9: the one-launch per-block decode (okv_block_kernel)
-  // (10: the same with 512-thread workgroups; 11: diagnostic, the prefix from
-  // okv_count_kernel instead of the look-back)
-  const bool block = large && ctx->value_sweep >= 9 && !index_only && !w.pre;
-  const bool block_diag = block && ctx->value_sweep == 11;
-  const bool tile = large && !block && ctx->value_sweep >= 8;
-  const bool sweep = large && !tile && !block && ctx->value_sweep && !index_only &&
-                     ctx->gather_staged && o->row_cap < (uint64_t(1) << 32);
-#else
-  const bool tile = large;  // the product: okv_tile_kernel for every large-block decode
-  constexpr bool sweep = false, block = false, block_diag = false;
-#endif
+  const Route route = select_route(ctx, w, nblk);
+  const bool tile = route == Route::kTile;
   const TileGeo geo = tile ? tile_geo(ctx, w, nblk, index_only) : TileGeo{1, ~0ull};
   ctx->span_hint = SpanHint{};  // a plan's hint sizes the one decode that follows it
+  // scratch
   uint16_t* rt_kl = nullptr;
-  if (tile || sweep) {
-    if ((rc = ensure_blocks(ctx, nblk)) ||
-        (rc = grow(ctx, &ctx->d_hdr, &ctx->cap_hdr, size_t(nblk) * kRCap * 2)))
-      return rc;
-    rt_kl = static_cast<uint16_t*>(ctx->d_hdr);
-  }
   if ((rc = ensure_blocks(ctx, nblk))) return rc;
-  uint32_t* const big_count = big_counter(ctx);  // this decode's slot (launch_plan flips it)
-#ifdef OKV_ABLATE
-  const uint32_t b0 = tile && ctx->pieces ? piece_split(nblk) : 0u;
-  // small blocks in pieces of ~small_piece bytes (OKV_SMALL_PIECE_MB): count
-  // then gather per piece, the gather reading what the count just read
-  uint32_t spn = 0;
-  if (!fused && !stream && !large && !group && nblk && ctx->small_piece &&
-      w.seg_bytes > ctx->small_piece)
-    spn = std::max<uint32_t>(kTile, uint32_t(uint64_t(nblk) * ctx->small_piece / w.seg_bytes) &
-                                        ~uint32_t(kTile - 1));
-  if (spn >= nblk) spn = 0;
-#endif
-  // the big-block kernel (okv_copy_kernel, okv_index_kernel) runs right after
-  // passes 1-2 when they are one count launch: before the chained context's
-  // pass-3 wait, so with decodes in flight it runs under the other decode's
-  // pass 3 (the list is empty on C1-C5: an empty launch cost 4.6 us + a
-  // kernel boundary in front of each pass 3), and before the pass-3 mark, so
-  // the pass-3 interval times the tile / gather kernel alone
-  bool early_big = false;
-  if (fused || stream || (block && !block_diag)) {
-    if ((rc = ensure_fused(ctx, nblk))) return rc;
+  if (tile && (rc = ensure_hdr(ctx, nblk, &rt_kl))) return rc;
+  if (route == Route::kFused && (rc = ensure_fused(ctx, nblk))) return rc;
+  const CopyParams P = copy_params(ctx, w, nblk, index_only, rt_kl, geo.span_cap, *o);
+  ctx->last_path = path_bits(ctx, comp, index_only, uint32_t(route));
+  // passes 1-2.  When they are the count launch, the big-block kernel runs
+  // right behind it: before the chained context's pass-3 wait, so with decodes
+  // in flight it runs under the other decode's pass 3 (the list is empty on
+  // C1-C5: an empty launch cost 4.6 us + a kernel boundary in front of each
+  // pass 3), and before the pass-3 mark, so the pass-3 interval times the tile
+  // / gather kernel alone.  The fused kernel does passes 1-2 itself.
+  if (route == Route::kFused) {
     prof_mark(ctx, 2);
-    prof_mark(ctx, 3);
-#ifdef OKV_ABLATE
-  } else if (group) {
-    if ((rc = ensure_group(ctx, (nblk + kGroup - 1) / kGroup))) return rc;
-    prof_mark(ctx, 2);
-    prof_mark(ctx, 3);
-#endif
-#ifdef OKV_ABLATE
-  } else if (b0) {
-    rc = launch_plan_pieces(ctx, w, nblk, b0, o->row_start, rt_kl, geo.span_cap);
-    if (rc) return rc;
-  } else if (spn) {  // the counts run piece by piece with the gathers below
-    if (!ctx->d_ptot) OKV_HIP(hipMalloc(&ctx->d_ptot, 2 * sizeof(Totals)));
-    prof_mark(ctx, 2);
-    prof_mark(ctx, 3);
-#endif
   } else {
-    rc = launch_plan(ctx, w, nblk, o->row_start, true, rt_kl, geo.span_cap);
-    if (rc) return rc;
-    early_big = nblk != 0;
-    if (!early_big) prof_mark(ctx, 3);
-  }
-  CopyParams P;
-  P.seg = w.seg;
-  P.seg_bytes = w.seg_bytes;
-  P.descs = w.descs;
-  P.nblk = nblk;
-  P.comp = w.comp;
-  P.index_only = index_only ? 1 : 0;
-  P.rt_pos = ctx->d_rec;
-  P.rt_kl = rt_kl;
-  P.span_cap = geo.span_cap;
-  P.big_list = ctx->d_big;
-  P.big_count = big_count;
-  P.cnt = ctx->d_cnt;
-  P.lp = ctx->d_lp;
-  P.tile_pre = ctx->d_tile_pre;
-  P.row_start = o->row_start;
-  P.key_base = o->key_base;
-  P.val_base = o->val_base;
-  P.blk_status = o->blk_status;
-  P.key_off = o->key_off;
-  P.key_len = o->key_len;
-  P.val_off = o->val_off;
-  P.val_len = o->val_len;
-  P.key_arena = o->key_arena;
-  P.val_arena = o->val_arena;
-  P.row_cap = o->row_cap;
-  P.key_cap = index_only ? 0 : o->key_cap;
-  P.val_cap = index_only ? 0 : o->val_cap;
-  P.vsrc = nullptr;
-  P.vtile = nullptr;
-  P.bchunk = nullptr;
-  P.tot = ctx->d_tot;
-  uint64_t sw_tiles = 0;
-  if (sweep) {
-    sw_tiles = (o->val_cap + kSwTile - 1) / kSwTile;
-    if ((rc = grow(ctx, &ctx->d_vsrc, &ctx->cap_vsrc, std::max<uint64_t>(o->row_cap, 1) * 24 + 256)) ||
-        (rc = grow(ctx, &ctx->d_vtile, &ctx->cap_vtile, (sw_tiles + 4) * 4)))
-      return rc;
-    // [row] u64 sources, then [row] 16-byte boundary chunks
-    P.vsrc = static_cast<uint64_t*>(ctx->d_vsrc);
-    P.bchunk = reinterpret_cast<uint4*>(static_cast<uint8_t*>(ctx->d_vsrc) +
-                                        ((std::max<uint64_t>(o->row_cap, 1) * 8 + 255) & ~255ull));
-    P.vtile = static_cast<uint32_t*>(ctx->d_vtile);
-  }
-  const uint32_t gt = nblk ? gather_threads(ctx, w, nblk) : 0;
-  ctx->last_path = (comp ? OKV_PATH_ZSTD : 0u) |
-                   (comp == OKV_COMP_ZSTD && !index_only && ctx->z_retried ? OKV_PATH_ZSTD_REGROW : 0u) |
-                   (!nblk ? 0u
-                    : fused ? OKV_PATH_FUSED
-                    : stream ? OKV_PATH_STREAM
-                    : group ? OKV_PATH_GROUP | OKV_PATH_BIG  // (ablation builds only)
-                    : OKV_PATH_BIG | (tile ? OKV_PATH_TILE
-                                      : sweep ? OKV_PATH_SWEEP | OKV_PATH_STAGED
-                                      : gt == 256 && ctx->gather_staged && !index_only
-                                          ? OKV_PATH_STAGED
-                                      : gt == 64 && ctx->gather_staged ? OKV_PATH_SMALL
-                                                                       : OKV_PATH_GATHER));
-  const uint32_t nbig_grid = std::min<uint32_t>(nblk, 512);
-  auto launch_big = [&]() {
-    if (index_only)
-      hipLaunchKernelGGL(okv_index_kernel, dim3((nbig_grid + kThreads - 1) / kThreads),
-                         dim3(kThreads), 0, ctx->stream, P);
-    else
-      hipLaunchKernelGGL(okv_copy_kernel, dim3(nbig_grid), dim3(kThreads), 0, ctx->stream, P);
-  };
-  if (early_big) {
-    launch_big();
-    OKV_HIP(hipGetLastError());
-    prof_mark(ctx, 3);
-  }
-  // okv_decode_chain: pass 3 after the chained context's last pass 3.  (A
-  // shared pass-3 stream for chained contexts instead of this event wait
-  // measured slower: C5 0.407 vs 0.396 ms, C3 1.465 vs 1.449 ms per step with
-  // decodes in flight, profiles/r6/session/pass3_queue_ab.log.)
-  if (ctx->chain && ctx->chain->p3_rec)
-    OKV_HIP(hipStreamWaitEvent(ctx->stream, ctx->chain->p3_done, 0));
-  if (nblk) {
-    const dim3 g(ctx->gather_grid ? std::min<uint32_t>(nblk, ctx->gather_grid) : nblk);
-#ifdef OKV_ABLATE
-    if (block_diag) {
-      hipLaunchKernelGGL((okv_block_kernel<1024, false>), dim3(nblk), dim3(1024), 0, ctx->stream, P,
-                         FusedParams{});
-    } else
-#endif
-    if (fused || stream || block) {
-      FusedParams F;
-      F.pre = w.pre;
-      F.cnt = ctx->d_cnt;
-      F.lp = ctx->d_lp;
-      F.tile_pre = ctx->d_tile_pre;
-      F.flag = ctx->f_flag;
-      F.agg = ctx->f_agg;
-      F.incl = ctx->f_incl;
-      F.ctr = ctx->f_ctr;
-      F.arr = ctx->f_ctr + 1;
-      F.base = ctx->f_base;
-      ctx->f_epoch = (ctx->f_epoch + 1) & 0x3fffffffu;
-      F.epoch = ctx->f_epoch;
-      F.tot = ctx->d_tot;
-      F.big_zero = big_counter(ctx, 1);
-#ifdef OKV_ABLATE
-      if (block && ctx->value_sweep == 10)
-        hipLaunchKernelGGL(okv_block_kernel<512>, dim3(nblk), dim3(512), 0, ctx->stream, P, F);
-      else if (block)
-        hipLaunchKernelGGL(okv_block_kernel<1024>, dim3(nblk), dim3(1024), 0, ctx->stream, P, F);
-      else if (stream)
-        hipLaunchKernelGGL(okv_decode_stream_kernel, dim3(nblk), dim3(64), 0, ctx->stream, P, F);
-      else
-#endif
-        hipLaunchKernelGGL(okv_decode_fused_kernel, dim3(nblk), dim3(64), 0, ctx->stream, P, F);
-      const hipError_t le = hipGetLastError();
-      if (le != hipSuccess) {
-        // nothing ran: the counters keep their value, so f_base must too
-        return set_err(ctx, OKV_E_HIP, "okv_decode_fused_kernel launch", le);
-      }
-      // (the stream / block arms advance both counters by nblk once the grid
-      // completes; the product fused kernel uses none)
-      if (stream || block) ctx->f_base += nblk;
-      if (!block) ctx->big_slot ^= 1u;  // the kernel zeroed the other slot (see big_counter)
-    }
-#ifdef OKV_ABLATE
-    else if (group) {
-      GroupParams G;
-      G.pre = w.pre;
-      G.cnt = ctx->d_cnt;
-      G.lp = ctx->d_lp;
-      G.tile_pre = ctx->d_tile_pre;
-      G.flag = ctx->g_flag;
-      G.agg = ctx->g_agg;
-      G.incl = ctx->g_incl;
-      ctx->g_epoch = (ctx->g_epoch + 1) & 0x3fffffffu;
-      if (!ctx->g_epoch) ctx->g_epoch = 1;  // (a zero tag would match the zeroed flags)
-      G.epoch = ctx->g_epoch;
-      G.tot = ctx->d_tot;
-      G.big_zero = big_counter(ctx, 1);
-      hipLaunchKernelGGL(okv_group_kernel, dim3((nblk + kGroup - 1) / kGroup), dim3(kThreads), 0,
-                         ctx->stream, P, G);
+    if ((rc = launch_plan(ctx, w, nblk, o->row_start, true, rt_kl, geo.span_cap))) return rc;
+    if (route != Route::kEmpty) {
+      launch_big(ctx, P);
       OKV_HIP(hipGetLastError());
+    }
+  }
+  prof_mark(ctx, 3);
+  if ((rc = chain_wait(ctx))) return rc;
+  // pass 3
+  switch (route) {
+    case Route::kEmpty:
+      break;
+    case Route::kFused: {
+      hipLaunchKernelGGL(okv_decode_fused_kernel, dim3(nblk), dim3(64), 0, ctx->stream, P,
+                         fused_params(ctx, w));
+      const hipError_t le = hipGetLastError();
+      if (le != hipSuccess) return set_err(ctx, OKV_E_HIP, "okv_decode_fused_kernel launch", le);
       ctx->big_slot ^= 1u;  // the kernel zeroed the other slot (see big_counter)
+      launch_big(ctx, P);
+      break;
     }
-#endif
-    else if (tile) {
-      if ((ctx->tile_diag >= 3 && ctx->tile_diag <= 5) || ctx->tile_diag == 7) {
-        // phase probe: 8 timestamps per 256th workgroup
-        const size_t n = (size_t(nblk) * geo.tpb / 256 + 1) * 64;
-        if ((rc = grow(ctx, &ctx->d_vsrc, &ctx->cap_vsrc, n))) return rc;
-        P.vsrc = static_cast<uint64_t*>(ctx->d_vsrc);
-      }
-#ifdef OKV_ABLATE
-      if (b0) {  // the first piece's tile pass, then the second's after its walk
-        launch_tile(ctx, piece_params(P, 0, b0), geo);
-        OKV_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_piece[1], 0));
-        launch_tile(ctx, piece_params(P, b0, nblk - b0), geo);
-      } else
-#endif
-        launch_tile(ctx, P, geo);
-    }
-#ifdef OKV_ABLATE
-    else if (sweep) {
-      // per-block rows + keys (one wave per block), then the value sweep
-      hipLaunchKernelGGL(okv_rows_kernel, g, dim3(64), 0, ctx->stream, P);
-      if (sw_tiles) {
-        SweepParams S{w.seg, w.seg_bytes, o->val_off, o->val_len, P.vsrc, P.vtile, P.bchunk,
-                      o->val_arena,
-                      ctx->d_tot, P.big_count, o->row_cap, o->key_cap, o->val_cap};
-        if (ctx->value_sweep == 5)
-          hipLaunchKernelGGL((okv_value_sweep_kernel<4, true>), dim3(uint32_t((sw_tiles + 3) / 4)),
-                             dim3(256), 0, ctx->stream, S);
-        else if (ctx->value_sweep == 7)
-          hipLaunchKernelGGL((okv_value_sweep_kernel<3, true>), dim3(uint32_t((sw_tiles + 2) / 3)),
-                             dim3(256), 0, ctx->stream, S);
-        else if (ctx->value_sweep == 6)
-          hipLaunchKernelGGL((okv_value_sweep_kernel<2, true>), dim3(uint32_t((sw_tiles + 1) / 2)),
-                             dim3(256), 0, ctx->stream, S);
-        else if (ctx->value_sweep == 4)
-          hipLaunchKernelGGL(okv_value_sweep_kernel<4>, dim3(uint32_t((sw_tiles + 3) / 4)),
-                             dim3(256), 0, ctx->stream, S);
-        else if (ctx->value_sweep == 2)
-          hipLaunchKernelGGL(okv_value_sweep_kernel<2>, dim3(uint32_t((sw_tiles + 1) / 2)),
-                             dim3(256), 0, ctx->stream, S);
-        else
-          hipLaunchKernelGGL(okv_value_sweep_kernel<1>, dim3(uint32_t(sw_tiles)), dim3(256), 0,
-                             ctx->stream, S);
-      }
-      // the whole pass when the sweep is unsafe on device (big blocks,
-      // capacity); otherwise every workgroup returns at once (small grid)
-      hipLaunchKernelGGL((okv_gather_staged_kernel<kThreads>), dim3(std::min<uint32_t>(nblk, 2048)),
-                         dim3(kThreads), 0, ctx->stream, P);
-    } else if (gather_threads(ctx, w, nblk) == 256 && ctx->gather_staged && !index_only) {
-      hipLaunchKernelGGL((okv_gather_staged_kernel<kThreads>), g, dim3(kThreads), 0, ctx->stream, P);
-    } else if (spn && ctx->gather_staged) {
-      Totals* pt = static_cast<Totals*>(ctx->d_ptot);
-      const Totals* base = nullptr;
-      for (uint32_t p0 = 0, k = 0; p0 < nblk; p0 += spn, ++k) {
-        const uint32_t n = std::min(spn, nblk - p0);
-        Totals* tot = p0 + n == nblk ? ctx->d_tot : pt + (k & 1);
-        launch_count_piece(ctx, w, p0, n, o->row_start, base, tot, k == 0);
-        hipLaunchKernelGGL(okv_gather_small_kernel, dim3(n), dim3(64), 0, ctx->stream,
-                           piece_params(P, p0, n));
-        base = tot;
-      }
-      ctx->big_slot ^= 1u;  // the first count launch zeroed the other slot
-    } else if (gather_threads(ctx, w, nblk) == 64 && ctx->gather_staged)
-      hipLaunchKernelGGL(okv_gather_small_kernel, g, dim3(64), 0, ctx->stream, P);
-    else if (gather_threads(ctx, w, nblk) == 64)
-      hipLaunchKernelGGL(okv_gather_kernel<64>, g, dim3(64), 0, ctx->stream, P);
-    else
-      hipLaunchKernelGGL(okv_gather_kernel<kThreads>, g, dim3(kThreads), 0, ctx->stream, P);
-#else
-    else if (gather_threads(ctx, w, nblk) == 64) {
-      hipLaunchKernelGGL(okv_gather_small_kernel, g, dim3(64), 0, ctx->stream, P);
-    } else {
-      return set_err(ctx, OKV_E_ARG, "decode path");  // unreachable: large => tile
-    }
-#endif
-    if (!block && !early_big) launch_big();  // (the block kernel decodes every block itself)
-    OKV_HIP(hipGetLastError());
+    case Route::kSmall:
+      hipLaunchKernelGGL(okv_gather_small_kernel, dim3(nblk), dim3(64), 0, ctx->stream, P);
+      break;
+    case Route::kTile:
+      launch_tile(ctx, P, geo);
+      break;
   }
-  if (ctx->p3_done) {
-    OKV_HIP(hipEventRecord(ctx->p3_done, ctx->stream));
-    ctx->p3_rec = true;
-  }
-  prof_mark(ctx, 4);
-  if (flags & OKV_F_ASYNC) return OKV_OK;
-  Totals T;
-  rc = read_totals(ctx, &T);
-  if (rc) return rc;
-  o->n_rows = T.rows;
-  o->key_bytes = index_only ? 0 : T.kb;
-  o->val_bytes = index_only ? 0 : T.vb;
-  o->n_bad_blocks = T.bad;
-  if (T.rows > o->row_cap || (!index_only && (T.kb > o->key_cap || T.vb > o->val_cap)))
-    return set_err(ctx, OKV_E_CAPACITY, "output capacity too small (totals set)");
-  return OKV_OK;
+  if (route != Route::kEmpty) OKV_HIP(hipGetLastError());
+  return finish_decode(ctx, o, flags);
 }
 
-// Host pointers: stage inputs to device scratch, decode, copy results back.
 // Upper bounds of a host-mode decode's outputs from the host descriptors
 // (uncompressed blocks: a block's records lie in its BlockSize bytes inside
 // the segment, each >= 6 bytes; every block region pads to 16 bytes), or
@@ -2940,6 +2747,21 @@ int point_wait(okv_ctx* ctx, const volatile uint32_t* done, uint32_t seq) {
   return OKV_OK;
 }
 
+size_t al(size_t x) { return (x + 255) & ~size_t(255); }  // slab / scratch regions
+
+// One point-kernel call: clear the slab's completion word, launch with the
+// next call number (never 0: the cleared word's value) and wait for it.
+template <bool kFind>
+int point_run(okv_ctx* ctx, const CopyParams& P, Totals* tot, uint32_t* done, const uint8_t* key,
+              uint32_t klen, int32_t* found) {
+  ctx->last_path = OKV_PATH_POINT;
+  *done = 0;
+  const uint32_t seq = ++ctx->point_seq ? ctx->point_seq : ++ctx->point_seq;  // (never 0)
+  hipLaunchKernelGGL(okv_point_kernel<kFind>, dim3(1), dim3(kThreads), 0, ctx->stream, P, tot,
+                     PointFind{key, klen, found, done, seq});
+  OKV_HIP(hipGetLastError());
+  return point_wait(ctx, done, seq);
+}
 
 // One launch, one synchronisation: the blocks and descriptors are copied into
 // the pinned slab, the kernel reads them there and writes every output there
@@ -2955,7 +2777,6 @@ int decode_point(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv
     R += d.block_size / 6;
     A += round16(d.block_size);
   }
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   const size_t n1 = size_t(nblk) + 1;
   const size_t o_desc = al(seg_bytes + 64), o_rs = al(o_desc + nblk * sizeof(Desc)),
                o_kb = al(o_rs + n1 * 8), o_vb = al(o_kb + n1 * 8), o_st = al(o_vb + n1 * 8),
@@ -2988,20 +2809,10 @@ int decode_point(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv
   P.key_cap = A + 16;
   P.val_cap = A + 16;
   Totals* tot = reinterpret_cast<Totals*>(S + o_tot);
-  ctx->last_path = OKV_PATH_POINT;
   uint32_t* done = reinterpret_cast<uint32_t*>(S + o_tot + sizeof(Totals));
-  *done = 0;
-  const uint32_t seq = ++ctx->point_seq ? ctx->point_seq : ++ctx->point_seq;  // (never 0)
-  hipLaunchKernelGGL(okv_point_kernel<false>, dim3(1), dim3(kThreads), 0, ctx->stream, P, tot,
-                     PointFind{nullptr, 0, nullptr, done, seq});
-  OKV_HIP(hipGetLastError());
-  if ((rc = point_wait(ctx, done, seq))) return rc;
+  if ((rc = point_run<false>(ctx, P, tot, done, nullptr, 0, nullptr))) return rc;
   const Totals T = *tot;
-  o->n_rows = T.rows;
-  o->key_bytes = T.kb;
-  o->val_bytes = T.vb;
-  o->n_bad_blocks = T.bad;
-  if (T.rows > o->row_cap || T.kb > o->key_cap || T.vb > o->val_cap)
+  if (!totals_fit(T, false, o))
     return set_err(ctx, OKV_E_CAPACITY, "output capacity too small (totals set)");
   auto out = [](void* dst, const void* src, size_t n) {
     if (dst && n) std::memcpy(dst, src, n);
@@ -3032,7 +2843,6 @@ int point_get(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_bl
     return OKV_OK;  // not a point-path block: the caller decodes it in full
   const Desc& d = *reinterpret_cast<const Desc*>(desc);
   const uint64_t A = go_read_status(d, seg_bytes) == OKV_BLK_OK ? round16(d.block_size) : 0;
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   const size_t o_desc = al(seg_bytes + 64), o_key = al(o_desc + sizeof(Desc)),
                o_misc = al(o_key + klen + 16), o_tot = al(o_misc + 72), o_ka = al(o_tot + 64),
                o_va = al(o_ka + A + 16), total = al(o_va + A + 16);
@@ -3060,14 +2870,8 @@ int point_get(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_bl
   P.key_arena = S + o_ka;
   P.val_arena = S + o_va;
   Totals* tot = reinterpret_cast<Totals*>(S + o_tot);
-  ctx->last_path = OKV_PATH_POINT;
   uint32_t* done = reinterpret_cast<uint32_t*>(misc + 8);
-  *done = 0;
-  const uint32_t seq = ++ctx->point_seq ? ctx->point_seq : ++ctx->point_seq;  // (never 0)
-  hipLaunchKernelGGL(okv_point_kernel<true>, dim3(1), dim3(kThreads), 0, ctx->stream, P, tot,
-                     PointFind{S + o_key, uint32_t(klen), found, done, seq});
-  OKV_HIP(hipGetLastError());
-  if ((rc = point_wait(ctx, done, seq))) return rc;
+  if ((rc = point_run<true>(ctx, P, tot, done, S + o_key, uint32_t(klen), found))) return rc;
   out->status = *P.blk_status;
   out->found = *found;
   if (out->found == 1) {
@@ -3079,6 +2883,23 @@ int point_get(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_bl
   return OKV_OK;
 }
 
+// Host inputs: the segment and the descriptors into the context's device
+// staging buffers (d_seg, d_desc), on the context's stream.
+int stage_inputs(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_block_desc* descs,
+                 uint32_t nblk) {
+  int rc;
+  if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_seg), &ctx->cap_seg, seg_bytes + 64)) ||
+      (rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->cap_desc,
+                 size_t(nblk) * sizeof(Desc) + 64)))
+    return rc;
+  if (seg_bytes)
+    OKV_HIP(hipMemcpyAsync(ctx->d_seg, seg, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (nblk)
+    OKV_HIP(hipMemcpyAsync(ctx->d_desc, descs, size_t(nblk) * sizeof(Desc),
+                           hipMemcpyHostToDevice, ctx->stream));
+  return OKV_OK;
+}
+
 // Host pointers: stage inputs to device scratch, decode, copy results back.
 // The device outputs are sized from the host descriptors' bounds when those
 // exist (one pass-1 walk per call); otherwise from a pass-1 plan first.
@@ -3087,20 +2908,9 @@ int decode_host(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_
   if (ctx->point && point_eligible(seg_bytes, descs, nblk, comp, flags))
     return decode_point(ctx, seg, seg_bytes, descs, nblk, comp, o);
   const bool index_only = flags & OKV_F_INDEX_ONLY;
-  int rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_seg), &ctx->cap_seg, seg_bytes + 64);
-  if (rc) return rc;
-  rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->cap_desc,
-            size_t(nblk) * sizeof(Desc) + 64);
-  if (rc) return rc;
-  if (seg_bytes)
-    OKV_HIP(hipMemcpyAsync(ctx->d_seg, seg, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (nblk)
-    OKV_HIP(hipMemcpyAsync(ctx->d_desc, descs, size_t(nblk) * sizeof(Desc),
-                           hipMemcpyHostToDevice, ctx->stream));
-  rc = ensure_blocks(ctx, nblk);
+  int rc = stage_inputs(ctx, seg, seg_bytes, descs, nblk);
   if (rc) return rc;
   // device output layout inside one scratch allocation
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   const size_t n1 = size_t(nblk) + 1;
   size_t off_rs = 0, off_kb = al(off_rs + n1 * 8), off_vb = al(off_kb + n1 * 8),
          off_st = al(off_vb + n1 * 8), off_rows = al(off_st + n1 * 4);
@@ -3119,16 +2929,13 @@ int decode_host(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_
     Work w;
     rc = prepare(ctx, ctx->d_seg, seg_bytes, ctx->d_desc, nblk, comp, index_only, &w);
     if (rc) return rc;
+    if ((rc = ensure_blocks(ctx, nblk))) return rc;
     rc = launch_plan(ctx, w, nblk, reinterpret_cast<uint64_t*>(base + off_rs));
     if (rc) return rc;
     Totals T;
     rc = read_totals(ctx, &T);
     if (rc) return rc;
-    o->n_rows = T.rows;
-    o->key_bytes = index_only ? 0 : T.kb;
-    o->val_bytes = index_only ? 0 : T.vb;
-    o->n_bad_blocks = T.bad;
-    if (T.rows > o->row_cap || (!index_only && (T.kb > o->key_cap || T.vb > o->val_cap)))
+    if (!totals_fit(T, index_only, o))
       return set_err(ctx, OKV_E_CAPACITY, "output capacity too small (totals set)");
     R = T.rows;
     KB = index_only ? 0 : T.kb;
@@ -3161,27 +2968,22 @@ int decode_host(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_
   o->key_bytes = d.key_bytes;
   o->val_bytes = d.val_bytes;
   o->n_bad_blocks = d.n_bad_blocks;
-  if (rc == OKV_E_CAPACITY) {  // the caller's capacity (a bounded decode: totals are set)
-    return set_err(ctx, OKV_E_CAPACITY, "output capacity too small (totals set)");
-  }
-  if (rc) return rc;
+  if (rc) return rc;  // (OKV_E_CAPACITY: the caller's capacity in a bounded decode; totals are set)
   const uint64_t nR = d.n_rows, nK = index_only ? 0 : d.key_bytes, nV = index_only ? 0 : d.val_bytes;
-  auto d2h = [&](void* dst, const void* src, size_t n) -> int {
-    if (dst && n) OKV_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, ctx->stream));
-    return OKV_OK;
-  };
-  if ((rc = d2h(o->row_start, d.row_start, n1 * 8))) return rc;
-  if ((rc = d2h(o->blk_status, d.blk_status, size_t(nblk) * 4))) return rc;
-  if (!index_only) {
-    if ((rc = d2h(o->key_base, d.key_base, size_t(nblk) * 8))) return rc;
-    if ((rc = d2h(o->val_base, d.val_base, size_t(nblk) * 8))) return rc;
-    if ((rc = d2h(o->key_arena, d.key_arena, nK))) return rc;
-    if ((rc = d2h(o->val_arena, d.val_arena, nV))) return rc;
-  }
-  if ((rc = d2h(o->key_off, d.key_off, nR * 8))) return rc;
-  if ((rc = d2h(o->key_len, d.key_len, nR * 2))) return rc;
-  if ((rc = d2h(o->val_off, d.val_off, nR * 8))) return rc;
-  if ((rc = d2h(o->val_len, d.val_len, nR * 4))) return rc;
+  const size_t nb = index_only ? 0 : size_t(nblk) * 8;  // (no bases, no arenas)
+  const struct {
+    void* dst;
+    const void* src;
+    size_t n;
+  } copies[] = {{o->row_start, d.row_start, n1 * 8},
+                {o->blk_status, d.blk_status, size_t(nblk) * 4},
+                {o->key_base, d.key_base, nb},       {o->val_base, d.val_base, nb},
+                {o->key_arena, d.key_arena, nK},     {o->val_arena, d.val_arena, nV},
+                {o->key_off, d.key_off, nR * 8},     {o->key_len, d.key_len, nR * 2},
+                {o->val_off, d.val_off, nR * 8},     {o->val_len, d.val_len, nR * 4}};
+  for (const auto& c : copies)
+    if (c.dst && c.n)
+      OKV_HIP(hipMemcpyAsync(c.dst, c.src, c.n, hipMemcpyDeviceToHost, ctx->stream));
   OKV_HIP(hipStreamSynchronize(ctx->stream));
   return OKV_OK;
 }
@@ -3209,10 +3011,11 @@ okv_ctx* okv_open_on_stream(int device, void* stream) {
   if (hipSetDevice(device) != hipSuccess) return nullptr;
   okv_ctx* ctx = new okv_ctx();
   ctx->device = device;
-  // The fused kernel's blocks wait for the last-arriving block of their grid,
-  // so every block must be resident at once: cap the batch at a quarter of
-  // the device's resident capacity for it (room for other contexts' grids on
-  // the same device), and at kFusedMaxBlocks.
+  // Precondition of okv_decode_fused_kernel (see kFusedMaxBlocks): the whole
+  // grid is resident at once and dispatched in index order, since each block
+  // spins on the look-back words of the blocks before it.  So cap the batch
+  // at a quarter of the device's resident capacity for the kernel (room for
+  // other contexts' grids on the same device), and at kFusedMaxBlocks.
   {
     int ncu = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
@@ -3223,42 +3026,7 @@ okv_ctx* okv_open_on_stream(int device, void* stream) {
     if (ctx->fused_max == 0) ctx->fused = false;
   }
 #ifdef OKV_ABLATE
-  // ablation build only: the measured alternative forms (tools/ablate*.py)
-  // A/B knobs of the pass-3 launch (both bit-exact): OKV_GATHER_THREADS=64|256
-  // (workgroup width), OKV_GATHER_GRID=<workgroups> (persistent grid)
-  if (const char* v = getenv("OKV_GATHER_THREADS")) {
-    ctx->gather_threads = uint32_t(atoi(v));
-    if (ctx->gather_threads != 64 && ctx->gather_threads != 256) {
-      delete ctx;
-      return nullptr;
-    }
-  }
-  if (const char* v = getenv("OKV_GATHER_GRID")) ctx->gather_grid = uint32_t(atoi(v));
-  if (const char* v = getenv("OKV_DECODE_FUSED")) ctx->fused = atoi(v) != 0;
-  if (const char* v = getenv("OKV_DECODE_GROUP")) ctx->group = atoi(v) != 0;
-  if (const char* v = getenv("OKV_DECODE_PIECES")) ctx->pieces = atoi(v) != 0;
-  if (const char* v = getenv("OKV_DECODE_STREAM")) ctx->stream_lb = atoi(v) != 0;
-  if (const char* v = getenv("OKV_SMALL_PIECE_MB")) ctx->small_piece = uint64_t(atoi(v)) << 20;
-  if (const char* v = getenv("OKV_GATHER_STAGED")) ctx->gather_staged = atoi(v) != 0;
-  if (const char* v = getenv("OKV_VALUE_SWEEP")) {
-    ctx->value_sweep = uint32_t(atoi(v));
-    if (ctx->value_sweep > 11 || ctx->value_sweep == 3) {
-      delete ctx;
-      return nullptr;
-    }
-  }
-  if (const char* v = getenv("OKV_TILE")) {  // <KiB>[x][w<threads>]
-    ctx->tile_kib = uint32_t(atoi(v));
-    ctx->tile_xcd = strchr(v, 'x') != nullptr;
-    const char* w = strchr(v, 'w');
-    ctx->tile_threads = w ? uint32_t(atoi(w + 1)) : 256u;
-    const char* dg = strchr(v, 'd');
-    ctx->tile_diag = dg ? uint32_t(atoi(dg + 1)) : 0u;
-    if (!tile_form(ctx->tile_kib, ctx->tile_threads, ctx->tile_diag)) {
-      delete ctx;
-      return nullptr;
-    }
-  }
+  if (!(ctx = ablate_open(ctx))) return nullptr;  // the OKV_* knobs of the alternative forms
 #endif
   if (stream) {
     ctx->stream = static_cast<hipStream_t>(stream);
@@ -3293,55 +3061,20 @@ void okv_close(okv_ctx* ctx) {
     auto& v = ctx->chain->chained_by;
     v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
   }
-  (void)hipFree(ctx->d_cnt);
-  (void)hipFree(ctx->d_lp);
-  (void)hipFree(ctx->d_tile_tot);
-  (void)hipFree(ctx->d_tile_pre);
-  (void)hipFree(ctx->d_rec);
-  (void)hipFree(ctx->d_big);
-  (void)hipFree(ctx->d_ctr);
-  if (ctx->p3_done) (void)hipEventDestroy(ctx->p3_done);
-  (void)hipFree(ctx->f_flag);
-  (void)hipFree(ctx->f_agg);
-  (void)hipFree(ctx->f_incl);
-  (void)hipFree(ctx->g_flag);
-  (void)hipFree(ctx->g_agg);
-  (void)hipFree(ctx->g_incl);
-  (void)hipFree(ctx->f_ctr);
-  (void)hipFree(ctx->d_tot);
-  if (ctx->h_tot) (void)hipHostFree(ctx->h_tot);
-  if (ctx->h_span) (void)hipHostFree(ctx->h_span);
-  (void)hipFree(ctx->d_span);
-  (void)hipFree(ctx->d_seg);
-  (void)hipFree(ctx->d_desc);
-  (void)hipFree(ctx->d_out);
-  (void)hipFree(ctx->d_hash);
-  if (ctx->h_slab) (void)hipHostFree(ctx->h_slab);
-  (void)hipFree(ctx->d_vsrc);
-  (void)hipFree(ctx->d_hdr);
-  (void)hipFree(ctx->d_vtile);
-  (void)hipFree(ctx->z_cap_off);
-  (void)hipFree(ctx->z_dec_len);
-  (void)hipFree(ctx->z_status);
-  (void)hipFree(ctx->z_desc);
-  (void)hipFree(ctx->z_dec);
-  (void)hipFree(ctx->z_lit);
-  (void)hipFree(ctx->z_blit);
-  (void)hipFree(ctx->z_tabs);
-  (void)hipFree(ctx->d_ptot);
-  if (ctx->z_ev) (void)hipEventDestroy(ctx->z_ev);
-  (void)hipFree(ctx->z_zb);
-  (void)hipFree(ctx->z_seq_off);
-  (void)hipFree(ctx->z_seqs);
-  (void)hipFree(ctx->z_list);
-  (void)hipFree(ctx->z_need);
-  if (ctx->stream2) {
-    (void)hipStreamSynchronize(ctx->stream2);
-    (void)hipStreamDestroy(ctx->stream2);
-  }
-  for (hipEvent_t& ev : ctx->ev_piece)
-    if (ev) (void)hipEventDestroy(ev);
-  (void)hipFree(ctx->d_tot2);
+  for (void* p : std::initializer_list<void*>{
+           ctx->d_cnt, ctx->d_lp, ctx->d_tile_tot, ctx->d_tile_pre, ctx->d_rec, ctx->d_big,
+           ctx->d_ctr, ctx->d_hdr, ctx->d_tot, ctx->d_span, ctx->f_flag, ctx->f_agg, ctx->f_incl,
+           ctx->f_ctr, ctx->d_seg, ctx->d_desc, ctx->d_out, ctx->d_hash, ctx->z_cap_off,
+           ctx->z_dec_len, ctx->z_status, ctx->z_desc, ctx->z_dec, ctx->z_lit, ctx->z_blit,
+           ctx->z_tabs, ctx->z_zb, ctx->z_seq_off, ctx->z_seqs, ctx->z_list, ctx->z_need})
+    (void)hipFree(p);
+  for (void* p : std::initializer_list<void*>{ctx->h_tot, ctx->h_span, ctx->h_slab})
+    if (p) (void)hipHostFree(p);
+  for (hipEvent_t e : {ctx->p3_done, ctx->z_ev})
+    if (e) (void)hipEventDestroy(e);
+#ifdef OKV_ABLATE
+  ablate_close(ctx);  // the arms' scratch
+#endif
   okv::enc_release(ctx);
   okv::merge_release(ctx);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -3394,16 +3127,7 @@ int okv_decode_plan(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
   const Desc* d_desc = reinterpret_cast<const Desc*>(descs);
   int rc;
   if (!(flags & OKV_F_DEVICE_PTRS)) {
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_seg), &ctx->cap_seg, seg_bytes + 64)))
-      return rc;
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->cap_desc,
-                   size_t(nblk) * sizeof(Desc) + 64)))
-      return rc;
-    if (seg_bytes)
-      OKV_HIP(hipMemcpyAsync(ctx->d_seg, seg, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (nblk)
-      OKV_HIP(hipMemcpyAsync(ctx->d_desc, descs, size_t(nblk) * sizeof(Desc),
-                             hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = stage_inputs(ctx, seg, seg_bytes, descs, nblk))) return rc;
     d_seg = ctx->d_seg;
     d_desc = ctx->d_desc;
   } else if (!aligned16(seg)) {
@@ -3414,6 +3138,7 @@ int okv_decode_plan(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
                     (flags & OKV_F_INDEX_ONLY) != 0, &w)))
     return rc;
   OKV_HIP(hipMemsetAsync(ctx->d_span, 0, sizeof(unsigned long long), ctx->stream));
+  if ((rc = ensure_blocks(ctx, nblk))) return rc;
   if ((rc = launch_plan(ctx, w, nblk, nullptr, false, nullptr, ~0ull, ctx->d_span))) return rc;
   OKV_HIP(hipMemcpyAsync(ctx->h_span, ctx->d_span, sizeof(unsigned long long),
                          hipMemcpyDeviceToHost, ctx->stream));
@@ -3454,13 +3179,7 @@ int okv_decode_totals(okv_ctx* ctx, okv_decode_out* out) {
   Totals T;
   int rc = read_totals(ctx, &T);
   if (rc) return rc;
-  out->n_rows = T.rows;
-  out->key_bytes = T.kb;
-  out->val_bytes = T.vb;
-  out->n_bad_blocks = T.bad;
-  if (T.rows > out->row_cap || T.kb > out->key_cap || T.vb > out->val_cap)
-    return OKV_E_CAPACITY;
-  return OKV_OK;
+  return totals_fit(T, false, out) ? OKV_OK : OKV_E_CAPACITY;
 }
 
 int okv_hash_blocks(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
@@ -3473,19 +3192,10 @@ int okv_hash_blocks(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
   uint64_t* d_h = hashes;
   int rc;
   if (!(flags & OKV_F_DEVICE_PTRS)) {
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_seg), &ctx->cap_seg, seg_bytes + 64)))
-      return rc;
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->cap_desc,
-                   size_t(nblk) * sizeof(Desc) + 64)))
-      return rc;
     if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_hash), &ctx->cap_hash,
-                   size_t(nblk) * 8 + 64)))
+                   size_t(nblk) * 8 + 64)) ||
+        (rc = stage_inputs(ctx, seg, seg_bytes, descs, nblk)))
       return rc;
-    if (seg_bytes)
-      OKV_HIP(hipMemcpyAsync(ctx->d_seg, seg, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (nblk)
-      OKV_HIP(hipMemcpyAsync(ctx->d_desc, descs, size_t(nblk) * sizeof(Desc),
-                             hipMemcpyHostToDevice, ctx->stream));
     d_seg = ctx->d_seg;
     d_desc = ctx->d_desc;
     d_h = ctx->d_hash;
@@ -3494,22 +3204,11 @@ int okv_hash_blocks(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
     launch_hash(ctx->stream, d_seg, seg_bytes, d_desc, nblk, d_h);
     OKV_HIP(hipGetLastError());
   }
-  if (!(flags & OKV_F_DEVICE_PTRS)) {
-    if (nblk)
-      OKV_HIP(hipMemcpyAsync(hashes, d_h, size_t(nblk) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  if (nblk && !(flags & OKV_F_DEVICE_PTRS))
+    OKV_HIP(hipMemcpyAsync(hashes, d_h, size_t(nblk) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (!(flags & OKV_F_ASYNC)) OKV_HIP(hipStreamSynchronize(ctx->stream));
   return OKV_OK;
 }
-
-#ifdef OKV_ABLATE
-// Diagnostic (tile-pass phase probe, OKV_TILE=...d3 / d7): copy the probe buffer to host.
-int okv_debug_probe(okv_ctx* ctx, void* host, size_t bytes) {
-  if (!ctx || !ctx->d_vsrc) return OKV_E_ARG;
-  OKV_HIP(hipMemcpy(host, ctx->d_vsrc, std::min(bytes, ctx->cap_vsrc), hipMemcpyDeviceToHost));
-  return OKV_OK;
-}
-#endif
 
 uint32_t okv_last_path(const okv_ctx* ctx) { return ctx ? ctx->last_path : 0u; }
 

@@ -620,3 +620,110 @@ def test_large_batches_of_small_blocks(decoder, nofused_decoder, golden):
         want = [b["status"] if comp == _lib.COMP_NONE else b["status_lz4"] for b in case["blocks"]]
         assert [int(x) for x in got.status] == want * 60
         _assert_same_as_oracle(got, cseg, cd, comp, False)
+
+
+def _device_decode(dec, seg, d, comp=_lib.COMP_NONE, index_only=False, sync=True):
+    """(seg, d) through OKV_F_DEVICE_PTRS into torch tensors sized by
+    okv_decode_plan; returns the okv_decode_out and a function that copies the
+    outputs into a Decoded (call it once the decode has completed)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    s = np.frombuffer(bytes(seg), np.uint8)
+    n = d.shape[0]
+    seg_t = torch.from_numpy(s.copy()).to(dev)
+    d_t = torch.from_numpy(d.view(np.int64).copy()).to(dev)
+    rows, kb, vb = dec.plan_device(seg_t, s.size, d_t, n, comp, index_only)
+    out = {k: torch.zeros(m, dtype=t, device=dev) for k, m, t in [
+        ("row_start", n + 1, torch.int64), ("key_base", n, torch.int64),
+        ("val_base", n, torch.int64), ("status", max(n, 1), torch.int32),
+        ("key_off", rows, torch.int64), ("key_len", rows, torch.int16),
+        ("val_off", rows, torch.int64), ("val_len", rows, torch.int32),
+        ("key_arena", kb, torch.uint8), ("val_arena", vb, torch.uint8)]}
+    o = dec.decode_device(seg_t, s.size, d_t, n, out, comp, index_only=index_only, sync=sync)
+
+    def fetch():
+        h = {k: v.cpu().numpy() for k, v in out.items()}
+        full = not index_only
+        return okv.Decoded(
+            status=h["status"][:n], row_start=h["row_start"].view(np.uint64),
+            key_base=h["key_base"].view(np.uint64) if full else None,
+            val_base=h["val_base"].view(np.uint64) if full else None,
+            key_off=h["key_off"].view(np.uint64), key_len=h["key_len"].view(np.uint16),
+            val_off=h["val_off"].view(np.uint64), val_len=h["val_len"].view(np.uint32),
+            key_arena=h["key_arena"] if full else None,
+            val_arena=h["val_arena"] if full else None,
+            index_only=index_only, seg=s if index_only else None)
+    return o, fetch, (seg_t, d_t, out)
+
+
+def test_dispatcher_routes(decoder, nofused_decoder):
+    """The decode dispatcher's routes, pinned: each batch with device pointers,
+    full and index-only, equals the oracle, and okv_last_path is exactly the
+    value the route sets.  Then the tile and the small-gather batches enqueued
+    (OKV_F_ASYNC) on two contexts chained to each other, read back with
+    okv_decode_totals."""
+    import ctypes as C
+
+    from oracle import pyoracle as P
+    from tests import zstd_cases as ZC
+    small8 = _mixed_segment(["s"] * 8, 31)
+    small600 = _mixed_segment(["s"] * 600, 32)
+    tile4 = _mixed_segment(["L"] * 4, 33)
+    tile4_big = _mixed_segment(["L", "M", "L", "L"], 34)
+    zseg, _, _ = ZC.Z.zstd_segment(ZC._rows(41, 400), 3584, 4096, level=3)
+    zd = np.array([st.desc() for st in P.bytes_to_metadata(ZC._meta_of(zseg)).entries[:4]],
+                  np.uint64).reshape(-1, 4)
+    assert zd.shape[0] == 4
+    zstd4 = (zseg[:int(zd[-1][0] + zd[-1][1])], zd)
+    NONE, ZSTD = _lib.COMP_NONE, _lib.COMP_ZSTD
+    batches = [
+        ("empty", decoder, (b"\x00" * 32, np.zeros((0, 4), np.uint64)), NONE),
+        ("fused", decoder, small8, NONE),
+        ("small_gather", decoder, small600, NONE),  # past kFusedMaxBlocks
+        ("no_fused", nofused_decoder, small8, NONE),
+        ("tile", decoder, tile4, NONE),
+        ("tile_big", decoder, tile4_big, NONE),
+        ("zstd", decoder, zstd4, ZSTD),
+    ]
+    seen = {}
+    for name, dec, (seg, d), comp in batches:
+        for index_only in (False, True):
+            _, fetch, _keep = _device_decode(dec, seg, d, comp, index_only)
+            seen[name, index_only] = dec.last_path()
+            print(f"dispatcher route {name} index_only={index_only}: {dec.last_path()}")
+            _assert_same_as_oracle(fetch(), seg, d, comp, index_only)
+    # (the values the dispatcher set before it was split into routes)
+    assert seen == {
+        ("empty", False): 0, ("empty", True): 0,
+        ("fused", False): 1, ("fused", True): 1,
+        ("small_gather", False): 66, ("small_gather", True): 66,
+        ("no_fused", False): 66, ("no_fused", True): 66,
+        ("tile", False): 68, ("tile", True): 68,
+        ("tile_big", False): 68, ("tile_big", True): 68,
+        ("zstd", False): 129, ("zstd", True): 129,
+    }
+    # the big-block list of tile_big is not empty: its 'M' block has > kRCap rows
+    assert int(np.diff(CO.decode_soa(tile4_big[0], CO.descs_array(
+        [tuple(int(x) for x in r) for r in tile4_big[1]]))["row_start"].astype(np.int64)).max()) > 64
+
+    a, b = okv.Decoder(0), okv.Decoder(0)
+    try:
+        a.chain(b)
+        b.chain(a)
+        runs = []
+        for dec, (seg, d), want in ((a, tile4, 68), (b, small600, 66)):
+            o, fetch, keep = _device_decode(dec, seg, d, sync=False)
+            runs.append((dec, seg, d, want, o, fetch, keep))
+        for dec, seg, d, want, o, fetch, _keep in runs:
+            assert _lib.lib().okv_decode_totals(dec._ctx, C.byref(o)) == 0
+            lp = dec.last_path()
+            print(f"dispatcher route chained: last_path={lp}")
+            ref = _assert_same_as_oracle(fetch(), seg, d, NONE, False)
+            assert (o.n_rows, o.key_bytes, o.val_bytes, o.n_bad_blocks) == \
+                (int(ref["row_start"][-1]), ref["key_arena"].size, ref["val_arena"].size, 0)
+            assert lp == want
+        a.chain(None)
+        b.chain(None)
+    finally:
+        a.close()
+        b.close()

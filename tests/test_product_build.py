@@ -67,7 +67,10 @@ def test_product_source_holds_only_product_kernels():
         assert src.rfind("#ifdef OKV_ABLATE", 0, inc) > src.rfind("#endif", 0, inc), inc_name
     # round 4's arms are in the includes, not in the product translation units
     for name in ("okv_decode_stream_kernel", "launch_plan_pieces", "launch_count_piece",
-                 "piece_params", "okv_group_kernel", "ensure_group"):
+                 "piece_params", "okv_group_kernel", "ensure_group",
+                 # the ablation dispatch: its selector, its tile forms, its knobs
+                 "ablate_decode", "ablate_open", "ablate_close", "ablate_launch_tile",
+                 "ablate_count_prefetch", "launch_tile_t", "tile_form", "okv_debug_probe"):
         assert not re.search(r"\b" + name + r"\s*\([^;]*\)\s*\{", src), name
     enc = open(os.path.join(ROOT, "objectkv_amd", "csrc", "okv_encode.hip")).read()
     for name in ("okv_enc_plan_kernel", "enc_plan_fast"):
@@ -75,6 +78,19 @@ def test_product_source_holds_only_product_kernels():
     for inc_name in ("okv_encode_ablate.inc", "okv_encode_ablate_host.inc"):
         inc = enc.index(f'#include "{inc_name}"')
         assert enc.rfind("#ifdef OKV_ABLATE", 0, inc) > enc.rfind("#endif", 0, inc), inc_name
+
+
+def test_decode_ablation_enters_through_hooks():
+    """The ablation arms are out of line: okv_decode.hip names OKV_ABLATE for
+    the three includes, the two device-side stamp macros and at most five
+    single-line host hooks, one of them in decode_device, whose body is the
+    product dispatcher and fits two screens."""
+    src = open(os.path.join(ROOT, "objectkv_amd", "csrc", "okv_decode.hip")).read()
+    assert src.count("#ifdef OKV_ABLATE") <= 10
+    body = src[src.index("\nint decode_device("):]
+    body = body[:body.index("\n}\n")]
+    assert body.count("OKV_ABLATE") <= 1
+    assert body.count("\n") <= 120
 
 
 def test_product_reads_no_environment():
