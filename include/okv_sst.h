@@ -344,7 +344,18 @@ int okv_synth_rows_fixed(okv_ctx *ctx, uint64_t seed, uint64_t first_row, uint64
  * For GetRange this is the stream RowIter(direction).Seek(startRange) yields
  * (ascending: rows >= start; descending: rows <= end, consumed from row_hi - 1).
  * Inputs are given in the snapshot's priority order (:235-254); among equal keys
- * the lowest index owns the key (findMaxIndexes, :404-424). */
+ * the lowest index owns the key (findMaxIndexes, :404-424).
+ *
+ * What the callee relies on and the tests pin (tests/test_merge_gpu.py):
+ *  - an input with row_lo == row_hi is ignored: it owns nothing and, in
+ *    OKV_MERGE_GETRANGE, takes no part in the loop (Go fails before the loop on a
+ *    segment without a first row: the caller's check);
+ *  - the rows [row_lo, row_hi) of each input must be strictly ascending by key
+ *    (bytes.Compare, keys of up to 65535 bytes); unsorted or repeated keys inside one
+ *    input give unspecified rows;
+ *  - OKV_MERGE_GETRANGE assumes non-empty keys, as the writer guarantees
+ *    (segment_writer.go:90-91): Go's `lastKey != ""` test makes the loop treat an empty
+ *    key differently.  OKV_MERGE_ALL orders the empty key first like any other. */
 typedef struct okv_merge_src {
   const uint8_t *key_arena;
   const uint64_t *key_off;

@@ -10,6 +10,11 @@ Pinned by the reference's own known answers (tests/test_snapshot.py re-asserts
 snapshot_reader_test.go: TestGetRow :196-245, TestGetRangeAscending :276-375,
 TestGetRangeDescending :377-476, TestFindMaxIndexes :478-529).  The Go
 toolchain is absent, so nothing here is checked against Go output directly.
+
+The loop of GetRange is merge_loop(), over any cursors with Next();
+merge_lists() runs it over in-memory row lists and also reports how the loop
+ended (the reference of tests/test_merge_gpu.py, tied to Reader.GetRange by
+tests/test_snapshot.py::test_list_loop_matches_reader).
 """
 from __future__ import annotations
 
@@ -116,6 +121,112 @@ def find_max_indexes(arr, compare):  # :404-424
     return idx
 
 
+# How merge_loop ended (its second result, or .end of the io.EOF it raises).
+END_LIMIT = "limit"          # :355-357: the limit-th row was appended
+END_BOUND = "bound"          # :340-347: the next key is outside the range
+END_STALE = "stale"          # :336-338: a stream that ran out left its cursor on lastKey
+END_EOF_ROLL = "eof-roll"    # :316-331: Next() hit io.EOF rolling a tombstone forward
+END_EOF_STALE = "eof-stale"  # the same, from a stale L0-tombstone cursor after an emit
+
+
+def merge_loop(cursors, iters, levels, bound, limit, direction):
+    """The loop of Reader.GetRange (snapshot_reader.go:294-365) over open
+    streams: cursors[i] is the row stream i stands on (.Key, .Value), iters[i]
+    has Next() (raising GoError(EOF) when the stream runs out), levels[i] is
+    the segment's level, bound is `end` ascending and `start` descending.
+    -> ([(stream, row)], END_*); an io.EOF is raised with .end set."""
+    rows = []
+    last_key = None
+    stale = set()  # streams whose io.EOF was swallowed after an emit (:351-365)
+    while True:
+        nxt = find_max_indexes(cursors, lambda a, b: first_value(a.Key, b.Key, direction))
+        if not nxt:
+            raise P.GoError(ErrNoNextIndexFound)
+        if levels[nxt[0]] == 0 and cursors[nxt[0]].Value is None:
+            for ind in nxt:  # :316-331: any EOF is an error
+                try:
+                    cursors[ind] = iters[ind].Next()
+                except P.GoError as e:
+                    if e.kind == P.EOF:
+                        e.end = END_EOF_STALE if nxt[0] in stale else END_EOF_ROLL
+                    raise
+            continue
+        row = cursors[nxt[0]]
+        if _b(last_key) != b"" and _b(row.Key) == _b(last_key):
+            return rows, END_STALE
+        if direction == P.DirectionAscending and _cmp(row.Key, bound) >= 0:
+            return rows, END_BOUND
+        if direction == P.DirectionDescending and _cmp(row.Key, bound) <= 0:
+            return rows, END_BOUND
+        last_key = row.Key
+        if len(rows) >= limit:  # rows[addedRowIndex] with addedRowIndex == limit
+            raise P.GoPanic("index out of range")
+        rows.append((nxt[0], row))
+        if len(rows) >= limit:
+            return rows, END_LIMIT
+        for ind in nxt:  # :351-365: io.EOF leaves the cursor in place
+            try:
+                cursors[ind] = iters[ind].Next()
+            except P.GoError as e:
+                if e.kind != P.EOF:
+                    raise
+                stale.add(ind)
+
+
+class ListRow:
+    """One row of a list-backed stream: .Key, .Value (None = Go nil), .row (its
+    index in the list as given, ascending)."""
+
+    __slots__ = ("Key", "Value", "row")
+
+    def __init__(self, Key, Value, row):
+        self.Key, self.Value, self.row = Key, Value, row
+
+
+class ListCursor:
+    """RowIter over an in-memory list [(key, value_or_None), ...] sorted
+    ascending: rows [lo, hi) in `direction` (descending from hi - 1)."""
+
+    def __init__(self, rows, direction, lo=0, hi=None):
+        hi = len(rows) if hi is None else hi
+        self.rows = rows
+        self.order = range(hi - 1, lo - 1, -1) if direction == P.DirectionDescending \
+            else range(lo, hi)
+        self.at = 0
+
+    def Next(self):
+        if self.at >= len(self.order):
+            raise P.GoError(P.EOF)
+        r = self.order[self.at]
+        self.at += 1
+        return ListRow(self.rows[r][0], self.rows[r][1], r)
+
+
+def merge_lists(streams, bound, limit, direction):
+    """merge_loop over in-memory streams [(rows, level, lo, hi)] in priority
+    order (rows [lo, hi) of each list take part; an empty range takes no part,
+    as GetRange fails before the loop on a stream without a first row).
+    -> ([(stream, row)] or None on io.EOF, END_*)."""
+    iters, cursors, levels, index = [], [], [], []
+    for i, (rows, level, lo, hi) in enumerate(streams):
+        if hi <= lo:
+            continue
+        it = ListCursor(rows, direction, lo, hi)
+        iters.append(it)
+        cursors.append(it.Next())
+        levels.append(level)
+        index.append(i)
+    if not iters:
+        return [], None
+    try:
+        picks, end = merge_loop(cursors, iters, levels, bound, limit, direction)
+    except P.GoError as e:
+        if e.kind != P.EOF:
+            raise
+        return None, e.end
+    return [(index[s], row.row) for s, row in picks], end
+
+
 class Reader:
     """snapshot_reader.go:16-27, 63-74 (NewReader)."""
 
@@ -186,36 +297,9 @@ class Reader:
             cursors.append(it.Next())  # io.EOF here is a GetRange error
         if limit < 0:
             raise P.GoPanic("makeslice: len out of range")
-        rows = []
-        last_key = None
-        while True:
-            nxt = find_max_indexes(cursors, lambda a, b: first_value(a.Key, b.Key, direction))
-            if not nxt:
-                raise P.GoError(ErrNoNextIndexFound)
-            if segs[nxt[0]].Level == 0 and cursors[nxt[0]].Value is None:
-                for ind in nxt:  # :316-331: any EOF is an error
-                    cursors[ind] = iters[ind].Next()
-                continue
-            row = cursors[nxt[0]]
-            if _b(last_key) != b"" and _b(row.Key) == _b(last_key):
-                break
-            if direction == P.DirectionAscending and _cmp(row.Key, end) >= 0:
-                break
-            if direction == P.DirectionDescending and _cmp(row.Key, start) <= 0:
-                break
-            last_key = row.Key
-            if len(rows) >= limit:  # rows[addedRowIndex] with addedRowIndex == limit
-                raise P.GoPanic("index out of range")
-            rows.append(row)
-            if len(rows) >= limit:
-                break
-            for ind in nxt:  # :351-365: io.EOF leaves the cursor in place
-                try:
-                    cursors[ind] = iters[ind].Next()
-                except P.GoError as e:
-                    if e.kind != P.EOF:
-                        raise
-        return rows
+        bound = end if direction == P.DirectionAscending else start
+        picks, _end = merge_loop(cursors, iters, [s.Level for s in segs], bound, limit, direction)
+        return [row for _stream, row in picks]
 
     def RowIter(self, start, direction, bufferSize=100):  # :430-443
         return Iter(self, start, direction, bufferSize)

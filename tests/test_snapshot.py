@@ -4,6 +4,8 @@ TestGetRangeAscending (:276-375), TestGetRangeDescending (:377-476),
 TestFindMaxIndexes (:478-529), and the quirks the restatement keeps."""
 from __future__ import annotations
 
+import functools
+
 import pytest
 
 from oracle import pyoracle as P
@@ -163,3 +165,84 @@ def test_descending_seek_on_block_first_key():
     rows = r.GetRange(b"k31", fk, 100, P.DirectionDescending)
     keys = [x.Key for x in rows]
     assert fk not in keys and keys[0] < fk and keys[-1] > b"k31"
+
+
+def _outcome(fn):
+    try:
+        rows = fn()
+    except P.GoError as e:
+        return ("err", e.kind)
+    except P.GoPanic:
+        return ("panic",)
+    return ("rows", rows)
+
+
+def _list_streams(r, start, end, direction):
+    """The streams Reader.GetRange opens for (start, end, direction), in its
+    priority order, drained into ascending lists: [(rows, level, lo, hi)]."""
+    segs = r.getPossibleSegmentsForRange(start, end)
+    segs.sort(key=functools.cmp_to_key(lambda a, b: S._getrange_cmp(a, b, direction)))
+    out = []
+    for seg in segs:
+        it = r.readerFactory(seg).RowIter(direction)
+        it.Seek(end if direction == P.DirectionDescending else start)
+        rows = []
+        while True:
+            try:
+                kv = it.Next()
+            except P.GoError as e:
+                assert e.kind == P.EOF
+                break
+            rows.append((kv.Key, kv.Value))
+        if direction == P.DirectionDescending:
+            rows.reverse()
+        out.append((rows, seg.Level, 0, len(rows)))
+    return out
+
+
+def _snapshot_sets():
+    yield SC.reference_segments(), [b"key%03d" % i for i in range(0, 200, 45)] + \
+        [b"key0010", b"key900", b"key00", b"key0000"]
+    yield SC.quirk_segments(), [b"k%02d" % i for i in range(0, 62, 12)] + [b"k20", b"k21", b"k25"]
+    for seed in (1, 2):
+        segs, keys = SC.random_snapshot(seed, nseg=3 + seed)
+        yield segs, keys[::60] + [keys[3] + b"\x00"]
+
+
+def test_list_loop_matches_reader():
+    """merge_lists (the GetRange loop over in-memory streams, the reference of
+    tests/test_merge_gpu.py) gives the rows or the error of Reader.GetRange
+    when fed the streams GetRange opens; the end reasons seen cover all five."""
+    ends = set()
+    for segs, probes in _snapshot_sets():
+        data = {sid: (d, n) for sid, _l, d, n, _m in segs}
+        r = S.Reader(lambda rec: P.SegmentReader(*data[rec.ID]))
+        r.UpdateSegments([S.SegmentRecord(sid, lvl, P.bytes_to_metadata(m).FirstKey,
+                                          P.bytes_to_metadata(m).LastKey)
+                          for sid, lvl, _d, _n, m in segs], None)
+        probes = probes + [P.UnboundStart, P.UnboundEnd]
+        for a in probes:
+            for b in probes:
+                if S._cmp(a, b) >= 0:
+                    continue
+                for d in (P.DirectionAscending, P.DirectionDescending):
+                    streams = _list_streams(r, a, b, d)
+                    bound = b if d == P.DirectionAscending else a
+                    for lim in (0, 1, 3, 1000):
+                        want = _outcome(lambda: [(x.Key, x.Value)
+                                                 for x in r.GetRange(a, b, lim, d) or []])
+                        if not streams:
+                            assert want == ("rows", [])
+                            continue
+                        if any(not rows for rows, _l, _lo, _hi in streams):
+                            assert want == ("err", P.EOF)  # a stream with no first row
+                            continue
+
+                        def run():
+                            picks, end = S.merge_lists(streams, bound, lim, d)
+                            ends.add(end)
+                            if picks is None:
+                                raise P.GoError(P.EOF)
+                            return [streams[s][0][row] for s, row in picks]
+                        assert _outcome(run) == want, (a, b, lim, d)
+    assert ends == {S.END_LIMIT, S.END_BOUND, S.END_STALE, S.END_EOF_ROLL, S.END_EOF_STALE}
