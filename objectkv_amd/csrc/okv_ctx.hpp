@@ -1,13 +1,17 @@
 // okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip)
 // and encode (okv_encode.hip) translation units.  Internal header.
+// Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
+// its capacity and frees itself with its owner; kernels get raw pointers from data().
 #pragma once
 #include <hip/hip_runtime.h>
+#define OKV_BUF_HIP
 
 #include <algorithm>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
+#include "okv_buf.hpp"
 #include "okv_kernels.hpp"
 #include "okv_sst.h"
 
@@ -54,21 +58,18 @@ struct AblateState {
   uint32_t tile_threads = 256;  // okv_tile_kernel workgroup width
   uint32_t tile_diag = 0;       // diagnostic arms (1: no chunk pass, 2: no DMA, ...)
   // grouped single pass: look-back scratch
-  uint32_t* g_flag = nullptr;   // [groups] look-back flags, tagged with g_epoch
-  Prefix* g_agg = nullptr;
-  Prefix* g_incl = nullptr;
-  size_t g_cap = 0;
+  DevBuf<uint32_t> g_flag;      // [groups] look-back flags, tagged with g_epoch (zeroed once)
+  DevBuf<Prefix> g_agg;
+  DevBuf<Prefix> g_incl;
   uint32_t g_epoch = 0;
   // decodes in pieces
-  void* d_ptot = nullptr;       // two Totals: the running prefix between small pieces
+  DevBuf<Totals> d_ptot;        // two Totals: the running prefix between small pieces
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_piece[2] = {nullptr, nullptr};
-  Totals* d_tot2 = nullptr;     // totals of the first large piece
+  DevBuf<Totals> d_tot2;        // totals of the first large piece
   // value sweep hand-off; the tile pass's phase probe uses d_vsrc too
-  void* d_vsrc = nullptr;       // [row] value sources
-  size_t cap_vsrc = 0;
-  void* d_vtile = nullptr;      // [value-arena tile] owning rows
-  size_t cap_vtile = 0;
+  DevBuf<uint8_t> d_vsrc;       // [row] value sources
+  DevBuf<uint32_t> d_vtile;     // [value-arena tile] owning rows
 };
 }  // namespace okv
 
@@ -84,30 +85,27 @@ struct okv_ctx {
   bool zstd_one_pass = false;      // OKV_OPEN_ZSTD_ONE_PASS: every zstd block by the general kernel
   bool point = true;               // host-mode point path (okv_point_kernel); OKV_OPEN_NO_POINT: off
   // pass-1/2 scratch
-  okv::BlockCount* d_cnt = nullptr;
-  okv::Prefix* d_lp = nullptr;
-  okv::Prefix* d_tile_tot = nullptr;
-  okv::Prefix* d_tile_pre = nullptr;
-  uint32_t* d_rec = nullptr;       // nblk x kRCap record positions (pass 1, rec_index)
-  uint32_t* d_big = nullptr;       // big-block list [nblk]
-  uint32_t* d_ctr = nullptr;       // [0] count-kernel arrivals, [1..2] big-block counter slots
+  okv::DevBuf<okv::BlockCount> d_cnt;
+  okv::DevBuf<okv::Prefix> d_lp;
+  okv::DevBuf<okv::Prefix> d_tile_tot;
+  okv::DevBuf<okv::Prefix> d_tile_pre;
+  okv::DevBuf<uint32_t> d_rec;     // nblk x kRCap record positions (pass 1, rec_index)
+  okv::DevBuf<uint32_t> d_big;     // big-block list [nblk]
+  okv::DevBuf<uint32_t> d_ctr;     // zeroed once: [0] count-kernel arrivals, [1..2] big-block counters
   uint32_t big_slot = 0;           // slot the next launch counts big blocks in
-  size_t cap_blocks = 0;
-  void* d_hdr = nullptr;           // [nblk x kRCap] pass-1 record key lengths (u16): tile pass
-  size_t cap_hdr = 0;
-  okv::Totals* d_tot = nullptr;
-  okv::Totals* h_tot = nullptr;    // pinned
+  okv::DevBuf<uint16_t> d_hdr;     // [nblk x kRCap] pass-1 record key lengths: tile pass
+  okv::DevBuf<okv::Totals> d_tot;
+  okv::PinBuf<okv::Totals> h_tot;
   // the longest block walk of the last okv_decode_plan, for that batch's tile
   // pass (tile_geo); keyed by the batch's device inputs
-  unsigned long long* d_span = nullptr;
-  unsigned long long* h_span = nullptr;  // pinned
+  okv::DevBuf<unsigned long long> d_span;
+  okv::PinBuf<unsigned long long> h_span;
   okv::SpanHint span_hint;
   // single-pass small-block decode (okv_decode_fused_kernel)
-  uint32_t* f_flag = nullptr;      // [nblk] 8-byte look-back words, tagged with f_epoch
-  okv::Prefix* f_agg = nullptr;
-  okv::Prefix* f_incl = nullptr;
-  size_t f_cap = 0;
-  unsigned long long* f_ctr = nullptr;  // block-index counter, f_base at the next call
+  okv::DevBuf<uint64_t> f_flag;    // [nblk] look-back words, tagged with f_epoch (zeroed once)
+  okv::DevBuf<okv::Prefix> f_agg;
+  okv::DevBuf<okv::Prefix> f_incl;
+  okv::DevBuf<unsigned long long> f_ctr;  // zeroed once: block-index counter, f_base at the next call
   unsigned long long f_base = 0;        // (f_ctr, f_base: the ablation build's stream / block arms)
   uint32_t f_epoch = 0;
   // okv_decode_chain: this context's pass 3 waits for chain's last pass 3
@@ -116,18 +114,13 @@ struct okv_ctx {
   hipEvent_t p3_done = nullptr;    // recorded after every pass 3 once created
   bool p3_rec = false;             // p3_done has been recorded
   // host-mode staging buffers (device side)
-  uint8_t* d_seg = nullptr;
-  size_t cap_seg = 0;
-  okv::Desc* d_desc = nullptr;
-  size_t cap_desc = 0;
-  void* d_out = nullptr;
-  size_t cap_out = 0;
-  uint64_t* d_hash = nullptr;
-  size_t cap_hash = 0;
+  okv::DevBuf<uint8_t> d_seg;
+  okv::DevBuf<okv::Desc> d_desc;
+  okv::DevBuf<uint8_t> d_out;
+  okv::DevBuf<uint64_t> d_hash;
   // host-mode point reads (okv_point_kernel): one pinned slab holding the
   // staged blocks, their descriptors and every output
-  uint8_t* h_slab = nullptr;
-  size_t cap_slab = 0;
+  okv::PinBuf<uint8_t> h_slab;
   uint32_t point_seq = 0;          // point-kernel call number (its slab completion word)
   // per-pass event timing (okv_profile)
   bool prof = false;
@@ -139,31 +132,24 @@ struct okv_ctx {
   okv::EncScratch* enc = nullptr;  // encode scratch (okv_encode.hip)
   okv::mrg::Scratch* merge = nullptr;  // merge scratch (okv_merge.hip)
   // zstd decompression scratch (okv_zstd.hip)
-  uint64_t* z_cap_off = nullptr;  // [nblk + 1] decompressed-region offsets
-  uint64_t* z_dec_len = nullptr;  // [nblk]
-  int32_t* z_status = nullptr;    // [nblk]
-  okv::Desc* z_desc = nullptr;    // [nblk] descriptors of the decompressed blocks
-  size_t z_cap_blocks = 0;
-  uint8_t* z_dec = nullptr;       // decompressed blocks
-  size_t z_cap_dec = 0;
-  uint8_t* z_lit = nullptr;       // per-wave literal scratch (general kernel)
-  size_t z_cap_lit = 0;
-  uint8_t* z_blit = nullptr;      // per-block literal scratch (prologue -> executor)
-  size_t z_cap_blit = 0;
-  uint32_t* z_tabs = nullptr;     // per-block FSE tables (prologue -> sequence stage)
-  size_t z_cap_tabs = 0;         // (+ kHufSlot u16 per block: Huffman tables, prologue -> stream stage)
-  hipEvent_t z_ev = nullptr;      // the sequence count's copy (zstd_run)
-  void* z_zb = nullptr;           // per-block zst::ZBlk
-  size_t z_cap_zb = 0;
-  uint64_t* z_seq_off = nullptr;  // [nblk + 1] sequence offsets
-  size_t z_cap_seq_off = 0;
-  uint64_t* z_seqs = nullptr;     // packed sequences
-  size_t z_cap_seqs = 0;
-  uint32_t* z_list = nullptr;     // [nblk] blocks decoded again (+ the count after them)
-  size_t z_cap_list = 0;
-  uint64_t* z_need = nullptr;     // [n] measured outputs, [n + 1] their regions
-  size_t z_cap_need = 0;
-  uint32_t z_retried = 0;         // blocks the last zstd decode decoded again
+  okv::DevBuf<uint64_t> z_cap_off;   // [nblk + 1] decompressed-region offsets
+  okv::DevBuf<uint64_t> z_dec_len;   // [nblk]
+  okv::DevBuf<int32_t> z_status;     // [nblk]
+  okv::DevBuf<okv::Desc> z_desc;     // [nblk] descriptors of the decompressed blocks
+  okv::DevBuf<uint8_t> z_dec;        // decompressed blocks
+  okv::DevBuf<uint8_t> z_lit;        // per-wave literal scratch (general kernel)
+  okv::DevBuf<uint8_t> z_blit;       // per-block literal scratch (prologue -> executor)
+  okv::DevBuf<uint16_t> z_tabs;      // per-block FSE tables (prologue -> sequence stage), then
+                                     // kHufSlot u16 per block: Huffman tables (prologue -> stream stage)
+  hipEvent_t z_ev = nullptr;         // the sequence count's copy (zstd_run)
+  okv::DevBuf<uint8_t> z_zb;         // per-block zst::ZBlk
+  okv::DevBuf<uint64_t> z_seq_off;   // [nblk + 1] sequence offsets
+  okv::DevBuf<uint64_t> z_seqs;      // packed sequences
+  okv::DevBuf<uint32_t> z_list;      // [nblk] blocks decoded again (+ the count after them)
+  okv::DevBuf<uint64_t> z_need;      // [n] measured outputs, [n + 1] their regions
+  okv::DevBuf<unsigned long long> z_eprof;  // OKV_ZSTD_PROF only: executor phase cycles
+  okv::DevBuf<unsigned long long> z_pprof;  // OKV_ZSTD_PROF only: prologue phase cycles
+  uint32_t z_retried = 0;            // blocks the last zstd decode decoded again
 };
 
 namespace okv {
@@ -197,18 +183,12 @@ inline int set_err(okv_ctx* c, int code, const char* what, hipError_t e = hipSuc
     if (e_ != hipSuccess) return set_err(ctx, OKV_E_HIP, #call, e_); \
   } while (0)
 
-inline int grow(okv_ctx* ctx, void** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return OKV_OK;
-  if (*p) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    OKV_HIP(hipFree(*p));
-    *p = nullptr;
-  }
-  size_t c = std::max<size_t>(need, 4096);
-  c = (c + 4095) & ~size_t(4095);
-  OKV_HIP(hipMalloc(p, c));
-  *cap = c;
-  return OKV_OK;
+// Room for n elements of scratch on the context's stream (Buf::reserve): a
+// compare when there is room already; a failure is OKV_E_HIP with HIP's text.
+template <class B>
+inline int reserve(okv_ctx* ctx, B& b, size_t n, bool* fresh = nullptr) {
+  const hipError_t e = b.reserve(ctx->stream, n, fresh);
+  return e == hipSuccess ? OKV_OK : set_err(ctx, OKV_E_HIP, "scratch allocation", e);
 }
 
 }  // namespace okv

@@ -2265,27 +2265,19 @@ namespace {
 
 int ensure_blocks(okv_ctx* ctx, uint32_t nblk) {
   const size_t n = std::max<size_t>(nblk, 1);
-  if (n <= ctx->cap_blocks && ctx->d_cnt) return OKV_OK;
   const size_t ntiles = (n + kTile - 1) / kTile;
-  if (ctx->d_cnt) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    for (void* p : std::initializer_list<void*>{ctx->d_cnt, ctx->d_lp, ctx->d_tile_tot,
-                                                ctx->d_tile_pre, ctx->d_rec, ctx->d_big})
-      (void)hipFree(p);
-  }
-  if (!ctx->d_ctr) {
-    OKV_HIP(hipMalloc(&ctx->d_ctr, 64));
-    OKV_HIP(hipMemsetAsync(ctx->d_ctr, 0, 64, ctx->stream));
+  bool fresh = false;
+  int rc;
+  if ((rc = reserve(ctx, ctx->d_ctr, 16, &fresh))) return rc;
+  if (fresh) {
+    OKV_HIP(hipMemsetAsync(ctx->d_ctr.data(), 0, ctx->d_ctr.bytes(), ctx->stream));
     ctx->big_slot = 0;
   }
-  OKV_HIP(hipMalloc(&ctx->d_rec, n * kRCap * sizeof(uint32_t)));
-  OKV_HIP(hipMalloc(&ctx->d_big, (n + 1) * sizeof(uint32_t)));
-  OKV_HIP(hipMalloc(&ctx->d_cnt, n * sizeof(BlockCount)));
-  OKV_HIP(hipMalloc(&ctx->d_lp, n * sizeof(Prefix)));
-  OKV_HIP(hipMalloc(&ctx->d_tile_tot, (ntiles + 1) * sizeof(Prefix)));
-  OKV_HIP(hipMalloc(&ctx->d_tile_pre, (ntiles + 1) * sizeof(Prefix)));
-  ctx->cap_blocks = n;
-  return OKV_OK;
+  if ((rc = reserve(ctx, ctx->d_rec, n * kRCap)) || (rc = reserve(ctx, ctx->d_big, n + 1)) ||
+      (rc = reserve(ctx, ctx->d_cnt, n)) || (rc = reserve(ctx, ctx->d_lp, n)) ||
+      (rc = reserve(ctx, ctx->d_tile_tot, ntiles + 1)))
+    return rc;
+  return reserve(ctx, ctx->d_tile_pre, ntiles + 1);
 }
 
 // Counters kept across calls (zeroed once): the count kernel's arrival
@@ -2295,7 +2287,7 @@ int ensure_blocks(okv_ctx* ctx, uint32_t nblk) {
 // by then, so no memset launch is needed per decode.
 constexpr uint32_t kCtrArrive = 0, kCtrBig = 1;
 uint32_t* big_counter(okv_ctx* ctx, uint32_t other = 0) {
-  return ctx->d_ctr + kCtrBig + (ctx->big_slot ^ other);
+  return ctx->d_ctr.data() + kCtrBig + (ctx->big_slot ^ other);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -2336,29 +2328,23 @@ int prepare(okv_ctx* ctx, const uint8_t* d_seg, uint64_t seg_bytes, const Desc* 
   ctx->z_retried = 0;
   if (comp != OKV_COMP_ZSTD || index_only || nblk == 0) return OKV_OK;
   int rc;
-  if (nblk + 1 > ctx->z_cap_blocks || !ctx->z_cap_off) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    for (void* p : std::initializer_list<void*>{ctx->z_cap_off, ctx->z_dec_len, ctx->z_status,
-                                                ctx->z_desc})
-      (void)hipFree(p);
-    const size_t n = size_t(nblk) + 1;
-    OKV_HIP(hipMalloc(&ctx->z_cap_off, n * 8));
-    OKV_HIP(hipMalloc(&ctx->z_dec_len, n * 8));
-    OKV_HIP(hipMalloc(&ctx->z_status, n * 4));
-    OKV_HIP(hipMalloc(&ctx->z_desc, n * sizeof(Desc)));
-    ctx->z_cap_blocks = n;
-  }
-  launch_zstd_cap(ctx->stream, d_desc, nblk, ctx->z_cap_off);
-  uint64_t total = 0;
-  OKV_HIP(hipMemcpyAsync(&total, ctx->z_cap_off + nblk, 8, hipMemcpyDeviceToHost, ctx->stream));
-  OKV_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_dec), &ctx->z_cap_dec, total + 64)))
+  const size_t n = size_t(nblk) + 1;
+  if ((rc = reserve(ctx, ctx->z_cap_off, n)) || (rc = reserve(ctx, ctx->z_dec_len, n)) ||
+      (rc = reserve(ctx, ctx->z_status, n)) || (rc = reserve(ctx, ctx->z_desc, n)))
     return rc;
+  launch_zstd_cap(ctx->stream, d_desc, nblk, ctx->z_cap_off.data());
+  uint64_t total = 0;
+  OKV_HIP(hipMemcpyAsync(&total, ctx->z_cap_off.data() + nblk, 8, hipMemcpyDeviceToHost,
+                         ctx->stream));
+  OKV_HIP(hipStreamSynchronize(ctx->stream));
+  if ((rc = reserve(ctx, ctx->z_dec, total + 64))) return rc;
   if ((rc = zstd_run(ctx, d_seg, seg_bytes, d_desc, nblk, &total))) return rc;
-  launch_zstd_desc(ctx->stream, d_desc, nblk, ctx->z_cap_off, ctx->z_dec_len, ctx->z_desc);
+  launch_zstd_desc(ctx->stream, d_desc, nblk, ctx->z_cap_off.data(), ctx->z_dec_len.data(),
+                   ctx->z_desc.data());
   OKV_HIP(hipGetLastError());
   // offsets <= total < seg_bytes, so no decompressed block reads as EOF
-  *w = Work{ctx->z_dec, total + 16, ctx->z_desc, OKV_COMP_NONE, ctx->z_status};
+  *w = Work{ctx->z_dec.data(), total + 16, ctx->z_desc.data(), OKV_COMP_NONE,
+            ctx->z_status.data()};
   return OKV_OK;
 }
 
@@ -2401,9 +2387,10 @@ int launch_plan(okv_ctx* ctx, const Work& w, uint32_t nblk, uint64_t* d_row_star
   prefetch = ablate_count_prefetch(prefetch, nblk);  // OKV_COUNT_PREFETCH A/B
 #endif
   hipLaunchKernelGGL(okv_count_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, w.seg,
-                     w.seg_bytes, w.descs, nblk, w.comp, ctx->d_cnt, ctx->d_lp, ctx->d_tile_tot,
-                     ctx->d_rec, rt_kl, ctx->d_big, big_counter(ctx), w.pre, prefetch, span_cap,
-                     ctx->d_tile_pre, ctx->d_tot, d_row_start, ctx->d_ctr + kCtrArrive,
+                     w.seg_bytes, w.descs, nblk, w.comp, ctx->d_cnt.data(), ctx->d_lp.data(),
+                     ctx->d_tile_tot.data(), ctx->d_rec.data(), rt_kl, ctx->d_big.data(),
+                     big_counter(ctx), w.pre, prefetch, span_cap, ctx->d_tile_pre.data(),
+                     ctx->d_tot.data(), d_row_start, ctx->d_ctr.data() + kCtrArrive,
                      big_counter(ctx, 1), nullptr, 0u, span_max);
   OKV_HIP(hipGetLastError());
   ctx->big_slot ^= 1u;  // the launch zeroes the other slot: the next launch's counter
@@ -2442,40 +2429,38 @@ void launch_tile(okv_ctx* ctx, const CopyParams& P, const TileGeo& g) {
 
 // The record key lengths pass 1 leaves for the tile pass (count kernel rt_kl).
 int ensure_hdr(okv_ctx* ctx, uint32_t nblk, uint16_t** rt_kl) {
-  int rc = grow(ctx, &ctx->d_hdr, &ctx->cap_hdr, size_t(nblk) * kRCap * 2);
-  *rt_kl = static_cast<uint16_t*>(ctx->d_hdr);
+  const int rc = reserve(ctx, ctx->d_hdr, size_t(nblk) * kRCap);
+  *rt_kl = ctx->d_hdr.data();
   return rc;
 }
 
-// Look-back scratch of a single-pass decode: n flags of flag_bytes each,
-// zeroed once (the epoch tag makes every call's flags fresh), and n aggregate
+// Look-back scratch of a single-pass decode: n flags, zeroed once per
+// allocation (the epoch tag makes every call's flags fresh), and n aggregate
 // and inclusive prefixes.
-int ensure_lookback(okv_ctx* ctx, size_t n, size_t flag_bytes, uint32_t** flag, Prefix** agg,
-                    Prefix** incl, size_t* cap) {
+template <class Flag>
+int ensure_lookback(okv_ctx* ctx, size_t n, DevBuf<Flag>& flag, DevBuf<Prefix>& agg,
+                    DevBuf<Prefix>& incl) {
   n = std::max<size_t>(n, 1);
-  if (n <= *cap && *flag) return OKV_OK;
-  if (*flag) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    for (void* p : std::initializer_list<void*>{*flag, *agg, *incl}) (void)hipFree(p);
-    *flag = nullptr;
-  }
-  OKV_HIP(hipMalloc(flag, n * flag_bytes));
-  OKV_HIP(hipMemsetAsync(*flag, 0, n * flag_bytes, ctx->stream));
-  OKV_HIP(hipMalloc(agg, n * sizeof(Prefix)));
-  OKV_HIP(hipMalloc(incl, n * sizeof(Prefix)));
-  *cap = n;
-  return OKV_OK;
+  bool fresh = false;
+  int rc;
+  if ((rc = reserve(ctx, flag, n, &fresh))) return rc;
+  if (fresh) OKV_HIP(hipMemsetAsync(flag.data(), 0, flag.bytes(), ctx->stream));
+  if ((rc = reserve(ctx, agg, n))) return rc;
+  return reserve(ctx, incl, n);
 }
 
 // Scratch of okv_decode_fused_kernel: one 8-byte look-back word per block (the
 // ablation stream kernel uses the first 4 bytes per block as its flags).
 int ensure_fused(okv_ctx* ctx, uint32_t nblk) {
-  const int rc = ensure_lookback(ctx, nblk, sizeof(uint64_t), &ctx->f_flag, &ctx->f_agg,
-                                 &ctx->f_incl, &ctx->f_cap);
-  if (rc || ctx->f_ctr) return rc;
-  OKV_HIP(hipMalloc(&ctx->f_ctr, 2 * sizeof(unsigned long long)));  // blocks, arrivals
-  OKV_HIP(hipMemsetAsync(ctx->f_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  ctx->f_base = 0;
+  bool fresh = false;
+  int rc;
+  if ((rc = ensure_lookback(ctx, nblk, ctx->f_flag, ctx->f_agg, ctx->f_incl)) ||
+      (rc = reserve(ctx, ctx->f_ctr, 2, &fresh)))  // blocks, arrivals
+    return rc;
+  if (fresh) {
+    OKV_HIP(hipMemsetAsync(ctx->f_ctr.data(), 0, ctx->f_ctr.bytes(), ctx->stream));
+    ctx->f_base = 0;
+  }
   return OKV_OK;
 }
 
@@ -2490,14 +2475,14 @@ CopyParams copy_params(okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_on
   P.nblk = nblk;
   P.comp = w.comp;
   P.index_only = index_only ? 1 : 0;
-  P.rt_pos = ctx->d_rec;
+  P.rt_pos = ctx->d_rec.data();
   P.rt_kl = rt_kl;
   P.span_cap = span_cap;
-  P.big_list = ctx->d_big;
+  P.big_list = ctx->d_big.data();
   P.big_count = big_counter(ctx);
-  P.cnt = ctx->d_cnt;
-  P.lp = ctx->d_lp;
-  P.tile_pre = ctx->d_tile_pre;
+  P.cnt = ctx->d_cnt.data();
+  P.lp = ctx->d_lp.data();
+  P.tile_pre = ctx->d_tile_pre.data();
   P.row_start = o.row_start;
   P.key_base = o.key_base;
   P.val_base = o.val_base;
@@ -2511,16 +2496,18 @@ CopyParams copy_params(okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_on
   P.row_cap = o.row_cap;
   P.key_cap = index_only ? 0 : o.key_cap;
   P.val_cap = index_only ? 0 : o.val_cap;
-  P.tot = ctx->d_tot;
+  P.tot = ctx->d_tot.data();
   return P;
 }
 
 // Parameters of the single-pass kernels; starts the call's epoch.
 FusedParams fused_params(okv_ctx* ctx, const Work& w) {
   ctx->f_epoch = (ctx->f_epoch + 1) & 0x3fffffffu;
-  return FusedParams{w.pre,       ctx->d_cnt,  ctx->d_lp,     ctx->d_tile_pre,    ctx->f_flag,
-                     ctx->f_agg,  ctx->f_incl, ctx->f_ctr,    ctx->f_ctr + 1,     ctx->f_base,
-                     ctx->f_epoch, ctx->d_tot, big_counter(ctx, 1)};
+  uint32_t* flag = reinterpret_cast<uint32_t*>(ctx->f_flag.data());
+  unsigned long long* ctr = ctx->f_ctr.data();
+  return FusedParams{w.pre, ctx->d_cnt.data(), ctx->d_lp.data(), ctx->d_tile_pre.data(), flag,
+                     ctx->f_agg.data(), ctx->f_incl.data(), ctr, ctr + 1, ctx->f_base,
+                     ctx->f_epoch, ctx->d_tot.data(), big_counter(ctx, 1)};
 }
 
 // The big-block kernel: the blocks of the big-block list (more than kRCap
@@ -2545,8 +2532,8 @@ int chain_wait(okv_ctx* ctx) {
 }
 
 int read_totals(okv_ctx* ctx, Totals* out) {
-  OKV_HIP(hipMemcpyAsync(ctx->h_tot, ctx->d_tot, sizeof(Totals), hipMemcpyDeviceToHost,
-                         ctx->stream));
+  OKV_HIP(hipMemcpyAsync(ctx->h_tot.data(), ctx->d_tot.data(), sizeof(Totals),
+                         hipMemcpyDeviceToHost, ctx->stream));
   OKV_HIP(hipStreamSynchronize(ctx->stream));
   *out = *ctx->h_tot;
   return OKV_OK;
@@ -2718,18 +2705,10 @@ bool point_eligible(uint64_t seg_bytes, const okv_block_desc* descs, uint32_t nb
   return true;
 }
 
-int grow_host(okv_ctx* ctx, uint8_t** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return OKV_OK;
-  if (*p) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    OKV_HIP(hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-  }
-  const size_t c = (std::max<size_t>(need, size_t(1) << 20) + 4095) & ~size_t(4095);
-  OKV_HIP(hipHostMalloc(reinterpret_cast<void**>(p), c, hipHostMallocDefault));
-  *cap = c;
-  return OKV_OK;
+// The pinned slab of the point path: at least 1 MiB, so that point reads of
+// growing size do not allocate again each time.
+int ensure_slab(okv_ctx* ctx, size_t need) {
+  return reserve(ctx, ctx->h_slab, std::max<size_t>(need, size_t(1) << 20));
 }
 
 // Wait for a point-kernel call by spinning on its completion word in the
@@ -2783,9 +2762,9 @@ int decode_point(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv
                o_tot = al(o_st + n1 * 4), o_ko = al(o_tot + sizeof(Totals) + 16),
                o_kl = al(o_ko + R * 8), o_vo = al(o_kl + R * 2), o_vl = al(o_vo + R * 8),
                o_ka = al(o_vl + R * 4), o_va = al(o_ka + A + 16), total = al(o_va + A + 16);
-  int rc = grow_host(ctx, &ctx->h_slab, &ctx->cap_slab, total);
+  int rc = ensure_slab(ctx, total);
   if (rc) return rc;
-  uint8_t* S = ctx->h_slab;
+  uint8_t* S = ctx->h_slab.data();
   if (seg_bytes) std::memcpy(S, seg, seg_bytes);
   std::memcpy(S + o_desc, descs, nblk * sizeof(Desc));
   CopyParams P;
@@ -2846,9 +2825,9 @@ int point_get(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_bl
   const size_t o_desc = al(seg_bytes + 64), o_key = al(o_desc + sizeof(Desc)),
                o_misc = al(o_key + klen + 16), o_tot = al(o_misc + 72), o_ka = al(o_tot + 64),
                o_va = al(o_ka + A + 16), total = al(o_va + A + 16);
-  int rc = grow_host(ctx, &ctx->h_slab, &ctx->cap_slab, total);
+  int rc = ensure_slab(ctx, total);
   if (rc) return rc;
-  uint8_t* S = ctx->h_slab;
+  uint8_t* S = ctx->h_slab.data();
   if (seg_bytes) std::memcpy(S, seg, seg_bytes);
   std::memcpy(S + o_desc, desc, sizeof(Desc));
   if (klen) std::memcpy(S + o_key, key, klen);
@@ -2888,14 +2867,13 @@ int point_get(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_bl
 int stage_inputs(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_block_desc* descs,
                  uint32_t nblk) {
   int rc;
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_seg), &ctx->cap_seg, seg_bytes + 64)) ||
-      (rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->cap_desc,
-                 size_t(nblk) * sizeof(Desc) + 64)))
+  if ((rc = reserve(ctx, ctx->d_seg, seg_bytes + 64)) ||
+      (rc = reserve(ctx, ctx->d_desc, size_t(nblk) + 2)))
     return rc;
   if (seg_bytes)
-    OKV_HIP(hipMemcpyAsync(ctx->d_seg, seg, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(ctx->d_seg.data(), seg, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (nblk)
-    OKV_HIP(hipMemcpyAsync(ctx->d_desc, descs, size_t(nblk) * sizeof(Desc),
+    OKV_HIP(hipMemcpyAsync(ctx->d_desc.data(), descs, size_t(nblk) * sizeof(Desc),
                            hipMemcpyHostToDevice, ctx->stream));
   return OKV_OK;
 }
@@ -2923,11 +2901,11 @@ int decode_host(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_
     KB = index_only ? 0 : std::min<uint64_t>(bbytes, o->key_cap);
     VB = index_only ? 0 : std::min<uint64_t>(bbytes, o->val_cap);
   } else {
-    rc = grow(ctx, &ctx->d_out, &ctx->cap_out, off_rows + 256);
+    rc = reserve(ctx, ctx->d_out, off_rows + 256);
     if (rc) return rc;
-    uint8_t* base = static_cast<uint8_t*>(ctx->d_out);
+    uint8_t* base = ctx->d_out.data();
     Work w;
-    rc = prepare(ctx, ctx->d_seg, seg_bytes, ctx->d_desc, nblk, comp, index_only, &w);
+    rc = prepare(ctx, ctx->d_seg.data(), seg_bytes, ctx->d_desc.data(), nblk, comp, index_only, &w);
     if (rc) return rc;
     if ((rc = ensure_blocks(ctx, nblk))) return rc;
     rc = launch_plan(ctx, w, nblk, reinterpret_cast<uint64_t*>(base + off_rs));
@@ -2945,9 +2923,9 @@ int decode_host(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_
          off_vl = al(off_vo + R * 8), off_ka = al(off_vl + R * 4), off_va = al(off_ka + KB),
          total = al(off_va + VB) + 256;
   // grow (keeps nothing: plan results live in ctx scratch, row_start[nblk] is rewritten)
-  rc = grow(ctx, &ctx->d_out, &ctx->cap_out, total);
+  rc = reserve(ctx, ctx->d_out, total);
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(ctx->d_out);
+  uint8_t* base = ctx->d_out.data();
   okv_decode_out d = *o;
   d.row_start = reinterpret_cast<uint64_t*>(base + off_rs);
   d.key_base = reinterpret_cast<uint64_t*>(base + off_kb);
@@ -2962,7 +2940,7 @@ int decode_host(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_
   d.row_cap = R;
   d.key_cap = KB;
   d.val_cap = VB;
-  rc = decode_device(ctx, ctx->d_seg, seg_bytes, ctx->d_desc, nblk, comp, &d,
+  rc = decode_device(ctx, ctx->d_seg.data(), seg_bytes, ctx->d_desc.data(), nblk, comp, &d,
                      (flags & ~OKV_F_ASYNC) | OKV_F_DEVICE_PTRS);
   o->n_rows = d.n_rows;
   o->key_bytes = d.key_bytes;
@@ -3037,11 +3015,8 @@ okv_ctx* okv_open_on_stream(int device, void* stream) {
     }
     ctx->own_stream = true;
   }
-  if (hipMalloc(&ctx->d_tot, sizeof(Totals)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&ctx->h_tot), sizeof(Totals), 0) != hipSuccess ||
-      hipMalloc(&ctx->d_span, sizeof(unsigned long long)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&ctx->h_span), sizeof(unsigned long long), 0) !=
-          hipSuccess) {
+  if (reserve(ctx, ctx->d_tot, 1) || reserve(ctx, ctx->h_tot, 1) || reserve(ctx, ctx->d_span, 1) ||
+      reserve(ctx, ctx->h_span, 1)) {
     okv_close(ctx);
     return nullptr;
   }
@@ -3061,24 +3036,16 @@ void okv_close(okv_ctx* ctx) {
     auto& v = ctx->chain->chained_by;
     v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
   }
-  for (void* p : std::initializer_list<void*>{
-           ctx->d_cnt, ctx->d_lp, ctx->d_tile_tot, ctx->d_tile_pre, ctx->d_rec, ctx->d_big,
-           ctx->d_ctr, ctx->d_hdr, ctx->d_tot, ctx->d_span, ctx->f_flag, ctx->f_agg, ctx->f_incl,
-           ctx->f_ctr, ctx->d_seg, ctx->d_desc, ctx->d_out, ctx->d_hash, ctx->z_cap_off,
-           ctx->z_dec_len, ctx->z_status, ctx->z_desc, ctx->z_dec, ctx->z_lit, ctx->z_blit,
-           ctx->z_tabs, ctx->z_zb, ctx->z_seq_off, ctx->z_seqs, ctx->z_list, ctx->z_need})
-    (void)hipFree(p);
-  for (void* p : std::initializer_list<void*>{ctx->h_tot, ctx->h_span, ctx->h_slab})
-    if (p) (void)hipHostFree(p);
   for (hipEvent_t e : {ctx->p3_done, ctx->z_ev})
     if (e) (void)hipEventDestroy(e);
 #ifdef OKV_ABLATE
-  ablate_close(ctx);  // the arms' scratch
+  ablate_close(ctx);  // the arms' second stream and events
 #endif
   okv::enc_release(ctx);
   okv::merge_release(ctx);
-  if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;
+  delete ctx;  // every scratch buffer releases itself
+  if (owned) (void)hipStreamDestroy(owned);
 }
 
 const char* okv_last_error(const okv_ctx* ctx) { return ctx ? ctx->err.c_str() : "no context"; }
@@ -3128,8 +3095,8 @@ int okv_decode_plan(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
   int rc;
   if (!(flags & OKV_F_DEVICE_PTRS)) {
     if ((rc = stage_inputs(ctx, seg, seg_bytes, descs, nblk))) return rc;
-    d_seg = ctx->d_seg;
-    d_desc = ctx->d_desc;
+    d_seg = ctx->d_seg.data();
+    d_desc = ctx->d_desc.data();
   } else if (!aligned16(seg)) {
     return set_err(ctx, OKV_E_ARG, "device seg must be 16-byte aligned");
   }
@@ -3137,10 +3104,11 @@ int okv_decode_plan(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
   if ((rc = prepare(ctx, d_seg, seg_bytes, d_desc, nblk, compression,
                     (flags & OKV_F_INDEX_ONLY) != 0, &w)))
     return rc;
-  OKV_HIP(hipMemsetAsync(ctx->d_span, 0, sizeof(unsigned long long), ctx->stream));
+  OKV_HIP(hipMemsetAsync(ctx->d_span.data(), 0, sizeof(unsigned long long), ctx->stream));
   if ((rc = ensure_blocks(ctx, nblk))) return rc;
-  if ((rc = launch_plan(ctx, w, nblk, nullptr, false, nullptr, ~0ull, ctx->d_span))) return rc;
-  OKV_HIP(hipMemcpyAsync(ctx->h_span, ctx->d_span, sizeof(unsigned long long),
+  if ((rc = launch_plan(ctx, w, nblk, nullptr, false, nullptr, ~0ull, ctx->d_span.data())))
+    return rc;
+  OKV_HIP(hipMemcpyAsync(ctx->h_span.data(), ctx->d_span.data(), sizeof(unsigned long long),
                          hipMemcpyDeviceToHost, ctx->stream));
   Totals T;
   if ((rc = read_totals(ctx, &T))) return rc;  // (synchronises: h_span is valid too)
@@ -3192,13 +3160,12 @@ int okv_hash_blocks(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes,
   uint64_t* d_h = hashes;
   int rc;
   if (!(flags & OKV_F_DEVICE_PTRS)) {
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->d_hash), &ctx->cap_hash,
-                   size_t(nblk) * 8 + 64)) ||
+    if ((rc = reserve(ctx, ctx->d_hash, size_t(nblk) + 8)) ||
         (rc = stage_inputs(ctx, seg, seg_bytes, descs, nblk)))
       return rc;
-    d_seg = ctx->d_seg;
-    d_desc = ctx->d_desc;
-    d_h = ctx->d_hash;
+    d_seg = ctx->d_seg.data();
+    d_desc = ctx->d_desc.data();
+    d_h = ctx->d_hash.data();
   }
   if (nblk) {
     launch_hash(ctx->stream, d_seg, seg_bytes, d_desc, nblk, d_h);

@@ -25,8 +25,7 @@ int ensure_pieces(okv_ctx* ctx) {
   OKV_HIP(hipStreamCreateWithFlags(&ctx->ab.stream2, hipStreamNonBlocking));
   OKV_HIP(hipEventCreateWithFlags(&ctx->ab.ev_piece[0], hipEventDisableTiming));
   OKV_HIP(hipEventCreateWithFlags(&ctx->ab.ev_piece[1], hipEventDisableTiming));
-  OKV_HIP(hipMalloc(&ctx->ab.d_tot2, sizeof(Totals)));
-  return OKV_OK;
+  return reserve(ctx, ctx->ab.d_tot2, 1);
 }
 
 // Pass 1-2 of blocks [b0, b0 + n) (b0 a multiple of kTile) on stream s,
@@ -38,12 +37,14 @@ void launch_count_piece(okv_ctx* ctx, hipStream_t s, const Work& w, uint32_t b0,
                         uint16_t* rt_kl = nullptr, uint64_t span_cap = ~0ull) {
   const uint64_t t0 = b0 / kTile;
   hipLaunchKernelGGL(okv_count_kernel, dim3((n + kTile - 1) / kTile), dim3(kThreads), 0, s, w.seg,
-                     w.seg_bytes, w.descs + b0, n, w.comp, ctx->d_cnt + b0, ctx->d_lp + b0,
-                     ctx->d_tile_tot + t0, ctx->d_rec + uint64_t(b0) * kRCap,
-                     rt_kl ? rt_kl + uint64_t(b0) * kRCap : nullptr, ctx->d_big, big_counter(ctx),
-                     w.pre ? w.pre + b0 : nullptr, 0, span_cap, ctx->d_tile_pre + t0, tot,
-                     d_row_start ? d_row_start + b0 : nullptr, ctx->d_ctr + kCtrArrive,
-                     first ? big_counter(ctx, 1) : nullptr, base, b0, nullptr);
+                     w.seg_bytes, w.descs + b0, n, w.comp, ctx->d_cnt.data() + b0,
+                     ctx->d_lp.data() + b0, ctx->d_tile_tot.data() + t0,
+                     ctx->d_rec.data() + uint64_t(b0) * kRCap,
+                     rt_kl ? rt_kl + uint64_t(b0) * kRCap : nullptr, ctx->d_big.data(),
+                     big_counter(ctx), w.pre ? w.pre + b0 : nullptr, 0, span_cap,
+                     ctx->d_tile_pre.data() + t0, tot, d_row_start ? d_row_start + b0 : nullptr,
+                     ctx->d_ctr.data() + kCtrArrive, first ? big_counter(ctx, 1) : nullptr, base,
+                     b0, nullptr);
 }
 
 // Passes 1-2 as two launches: blocks [0, b0) on the context stream (totals
@@ -54,12 +55,13 @@ int launch_plan_pieces(okv_ctx* ctx, const Work& w, uint32_t nblk, uint32_t b0,
   AblateState& A = ctx->ab;
   int rc = ensure_pieces(ctx);
   if (rc) return rc;
-  launch_count_piece(ctx, ctx->stream, w, 0, b0, nullptr, nullptr, A.d_tot2, true, rt_kl, span_cap);
+  launch_count_piece(ctx, ctx->stream, w, 0, b0, nullptr, nullptr, A.d_tot2.data(), true, rt_kl,
+                     span_cap);
   OKV_HIP(hipGetLastError());
   OKV_HIP(hipEventRecord(A.ev_piece[0], ctx->stream));
   OKV_HIP(hipStreamWaitEvent(A.stream2, A.ev_piece[0], 0));
-  launch_count_piece(ctx, A.stream2, w, b0, nblk - b0, d_row_start, A.d_tot2, ctx->d_tot, false,
-                     rt_kl, span_cap);
+  launch_count_piece(ctx, A.stream2, w, b0, nblk - b0, d_row_start, A.d_tot2.data(),
+                     ctx->d_tot.data(), false, rt_kl, span_cap);
   OKV_HIP(hipGetLastError());
   OKV_HIP(hipEventRecord(A.ev_piece[1], A.stream2));
   ctx->big_slot ^= 1u;  // the first launch zeroed the other slot
@@ -103,7 +105,7 @@ extern "C" int okv_debug_fused_times(uint64_t* out, uint32_t nblk) {
 // Look-back scratch of the grouped single pass (one 4-byte flag per group).
 int ensure_group(okv_ctx* ctx, uint32_t ngroups) {
   AblateState& A = ctx->ab;
-  return ensure_lookback(ctx, ngroups, sizeof(uint32_t), &A.g_flag, &A.g_agg, &A.g_incl, &A.g_cap);
+  return ensure_lookback(ctx, ngroups, A.g_flag, A.g_agg, A.g_incl);
 }
 
 // ---- the tile pass's forms (OKV_TILE=<KiB>[x][w<threads>][d<diag>]) ---------
@@ -205,28 +207,21 @@ okv_ctx* ablate_open(okv_ctx* ctx) {
   return ctx;
 }
 
-// okv_close's hook.
+// okv_close's hook (the arms' buffers release themselves with the context).
 void ablate_close(okv_ctx* ctx) {
   AblateState& A = ctx->ab;
-  (void)hipFree(A.g_flag);
-  (void)hipFree(A.g_agg);
-  (void)hipFree(A.g_incl);
-  (void)hipFree(A.d_ptot);
   if (A.stream2) {
     (void)hipStreamSynchronize(A.stream2);
     (void)hipStreamDestroy(A.stream2);
   }
   for (hipEvent_t& ev : A.ev_piece)
     if (ev) (void)hipEventDestroy(ev);
-  (void)hipFree(A.d_tot2);
-  (void)hipFree(A.d_vsrc);
-  (void)hipFree(A.d_vtile);
 }
 
 // Diagnostic (tile-pass phase probe, OKV_TILE=...d3 / d7): copy the probe buffer to host.
 extern "C" int okv_debug_probe(okv_ctx* ctx, void* host, size_t bytes) {
-  if (!ctx || !ctx->ab.d_vsrc) return OKV_E_ARG;
-  OKV_HIP(hipMemcpy(host, ctx->ab.d_vsrc, std::min(bytes, ctx->ab.cap_vsrc),
+  if (!ctx || !ctx->ab.d_vsrc.data()) return OKV_E_ARG;
+  OKV_HIP(hipMemcpy(host, ctx->ab.d_vsrc.data(), std::min(bytes, ctx->ab.d_vsrc.bytes()),
                     hipMemcpyDeviceToHost));
   return OKV_OK;
 }
@@ -294,7 +289,7 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
     if (group) {
       rc = ensure_group(ctx, (nblk + kGroup - 1) / kGroup);
     } else if (spn) {  // the counts run piece by piece with the gathers below
-      if (!A.d_ptot) OKV_HIP(hipMalloc(&A.d_ptot, 2 * sizeof(Totals)));
+      rc = reserve(ctx, A.d_ptot, 2);
     } else {
       rc = ensure_fused(ctx, nblk);
     }
@@ -312,14 +307,13 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
   if (sweep) {
     sw_tiles = (o->val_cap + kSwTile - 1) / kSwTile;
     const uint64_t rows = std::max<uint64_t>(o->row_cap, 1);
-    if ((rc = grow(ctx, &A.d_vsrc, &A.cap_vsrc, rows * 24 + 256)) ||
-        (rc = grow(ctx, &A.d_vtile, &A.cap_vtile, (sw_tiles + 4) * 4)))
+    if ((rc = reserve(ctx, A.d_vsrc, rows * 24 + 256)) ||
+        (rc = reserve(ctx, A.d_vtile, sw_tiles + 4)))
       return rc;
     // [row] u64 sources, then [row] 16-byte boundary chunks
-    P.vsrc = static_cast<uint64_t*>(A.d_vsrc);
-    P.bchunk = reinterpret_cast<uint4*>(static_cast<uint8_t*>(A.d_vsrc) +
-                                        ((rows * 8 + 255) & ~255ull));
-    P.vtile = static_cast<uint32_t*>(A.d_vtile);
+    P.vsrc = reinterpret_cast<uint64_t*>(A.d_vsrc.data());
+    P.bchunk = reinterpret_cast<uint4*>(A.d_vsrc.data() + ((rows * 8 + 255) & ~255ull));
+    P.vtile = A.d_vtile.data();
   }
   const uint32_t gather = tile    ? OKV_PATH_TILE
                           : sweep ? OKV_PATH_SWEEP | OKV_PATH_STAGED
@@ -363,8 +357,10 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
   } else if (group) {
     A.g_epoch = (A.g_epoch + 1) & 0x3fffffffu;
     if (!A.g_epoch) A.g_epoch = 1;  // (a zero tag would match the zeroed flags)
-    const GroupParams G{w.pre,    ctx->d_cnt, ctx->d_lp,  ctx->d_tile_pre, A.g_flag,
-                        A.g_agg,  A.g_incl,   A.g_epoch,  ctx->d_tot,      big_counter(ctx, 1)};
+    const GroupParams G{w.pre,           ctx->d_cnt.data(), ctx->d_lp.data(),
+                        ctx->d_tile_pre.data(), A.g_flag.data(), A.g_agg.data(),
+                        A.g_incl.data(), A.g_epoch,         ctx->d_tot.data(),
+                        big_counter(ctx, 1)};
     hipLaunchKernelGGL(okv_group_kernel, dim3((nblk + kGroup - 1) / kGroup), dim3(kThreads), 0,
                        ctx->stream, P, G);
     OKV_HIP(hipGetLastError());
@@ -373,8 +369,8 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
     if ((A.tile_diag >= 3 && A.tile_diag <= 5) || A.tile_diag == 7) {
       // phase probe: 8 timestamps per 256th workgroup
       const size_t n = (size_t(nblk) * geo.tpb / 256 + 1) * 64;
-      if ((rc = grow(ctx, &A.d_vsrc, &A.cap_vsrc, n))) return rc;
-      P.vsrc = static_cast<uint64_t*>(A.d_vsrc);
+      if ((rc = reserve(ctx, A.d_vsrc, n))) return rc;
+      P.vsrc = reinterpret_cast<uint64_t*>(A.d_vsrc.data());
     }
     if (b0) {  // the first piece's tile pass, then the second's after its walk
       launch_tile(ctx, piece_params(P, 0, b0), geo);
@@ -389,8 +385,8 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
     if (sw_tiles)
       launch_value_sweep(ctx, A.value_sweep, sw_tiles,
                          SweepParams{w.seg, w.seg_bytes, o->val_off, o->val_len, P.vsrc, P.vtile,
-                                     P.bchunk, o->val_arena, ctx->d_tot, P.big_count, o->row_cap,
-                                     o->key_cap, o->val_cap});
+                                     P.bchunk, o->val_arena, ctx->d_tot.data(), P.big_count,
+                                     o->row_cap, o->key_cap, o->val_cap});
     // the whole pass when the sweep is unsafe on device (big blocks,
     // capacity); otherwise every workgroup returns at once (small grid)
     hipLaunchKernelGGL((okv_gather_staged_kernel<kThreads>), dim3(std::min<uint32_t>(nblk, 2048)),
@@ -398,11 +394,11 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
   } else if (gt == 256 && A.gather_staged && !index_only) {
     hipLaunchKernelGGL((okv_gather_staged_kernel<kThreads>), g, dim3(kThreads), 0, ctx->stream, P);
   } else if (spn && A.gather_staged) {
-    Totals* pt = static_cast<Totals*>(A.d_ptot);
+    Totals* pt = A.d_ptot.data();
     const Totals* base = nullptr;
     for (uint32_t p0 = 0, k = 0; p0 < nblk; p0 += spn, ++k) {
       const uint32_t n = std::min(spn, nblk - p0);
-      Totals* tot = p0 + n == nblk ? ctx->d_tot : pt + (k & 1);
+      Totals* tot = p0 + n == nblk ? ctx->d_tot.data() : pt + (k & 1);
       launch_count_piece(ctx, ctx->stream, w, p0, n, o->row_start, base, tot, k == 0);
       hipLaunchKernelGGL(okv_gather_small_kernel, dim3(n), dim3(64), 0, ctx->stream,
                          piece_params(P, p0, n));

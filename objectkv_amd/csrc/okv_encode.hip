@@ -82,53 +82,43 @@ struct EncTotals {
 };
 
 struct EncScratch {
-  uint64_t* pl = nullptr;        // [n] tile-local inclusive prefix of record sizes
-  uint32_t* nx = nullptr;        // [n] next(a) - a
-  size_t cap_rows = 0;
-  uint64_t* tile_tot = nullptr;  // [ntiles]
-  uint64_t* tile_pre = nullptr;  // [ntiles]
-  size_t cap_tiles = 0;
-  uint32_t* jt = nullptr;        // [levels][nch][W] exit offsets
-  uint32_t* jb = nullptr;        // [levels][nch][W] blocks started
-  size_t cap_jump = 0;
-  uint32_t* entry = nullptr;     // [nch]
-  uint64_t* kbase = nullptr;     // [nch]
-  size_t cap_chunks = 0;
-  uint64_t* first = nullptr;     // [nb+1]
-  Desc* desc = nullptr;          // [nb]
-  uint64_t* hash = nullptr;      // [nb]
-  uint64_t* bsl = nullptr;       // [nb] tile-local inclusive BlockSize scan
-  uint64_t* esl = nullptr;       // [nb] tile-local inclusive meta entry size scan
-  uint64_t* moff = nullptr;      // [nb] meta entry offsets (relative to the meta block)
-  uint64_t* orig = nullptr;      // [nb] OriginalSize (the rows' record bytes) of each block
-  uint16_t* fkl = nullptr;       // [nb] key length of each block's first row (its FirstKey)
-  uint8_t* fk = nullptr;         // [nb][kFkStride] the block's first bytes (the LDS pack kernel)
-  size_t cap_blocks = 0;
-  uint16_t* jts = nullptr;       // [ntiles][kCutS] level-0 chain table of the tile cut
-  uint16_t* jbs = nullptr;       // (exit offsets <= 256, blocks <= 2 048: 16 bits each)
-  uint32_t* tentry = nullptr;    // [ntiles] the tile's entry row, blocks before it
-  uint64_t* tkbase = nullptr;
-  size_t cap_cut = 0;
-  uint64_t* btile = nullptr;     // [4][nbtiles]: BlockSize tot/pre, entry tot/pre
-  size_t cap_btiles = 0;
+  DevBuf<uint64_t> pl;           // [n] tile-local inclusive prefix of record sizes
+  DevBuf<uint32_t> nx;           // [n] next(a) - a
+  DevBuf<uint64_t> tile_tot;     // [ntiles]
+  DevBuf<uint64_t> tile_pre;     // [ntiles]
+  DevBuf<uint32_t> jt;           // [levels][nch][W] exit offsets
+  DevBuf<uint32_t> jb;           // [levels][nch][W] blocks started
+  DevBuf<uint32_t> entry;        // [nch]
+  DevBuf<uint64_t> kbase;        // [nch]
+  DevBuf<uint64_t> first;        // [nb+1]
+  DevBuf<Desc> desc;             // [nb]
+  DevBuf<uint64_t> hash;         // [nb]
+  DevBuf<uint64_t> bsl;          // [nb] tile-local inclusive BlockSize scan
+  DevBuf<uint64_t> esl;          // [nb] tile-local inclusive meta entry size scan
+  DevBuf<uint64_t> moff;         // [nb] meta entry offsets (relative to the meta block)
+  DevBuf<uint64_t> orig;         // [nb] OriginalSize (the rows' record bytes) of each block
+  DevBuf<uint16_t> fkl;          // [nb] key length of each block's first row (its FirstKey)
+  DevBuf<uint8_t> fk;            // [nb][kFkStride] the block's first bytes (the LDS pack kernel)
+  DevBuf<uint16_t> jts;          // [ntiles][kCutS] level-0 chain table of the tile cut
+  DevBuf<uint16_t> jbs;          // (exit offsets <= 256, blocks <= 2 048: 16 bits each)
+  DevBuf<uint32_t> tentry;       // [ntiles] the tile's entry row, blocks before it
+  DevBuf<uint64_t> tkbase;
+  DevBuf<uint64_t> btile;        // [4][capacity / 4]: BlockSize tot/pre, entry tot/pre
   // single-pass plan (okv_enc_plan_kernel): per-chunk look-back state
-  uint32_t* p_flag = nullptr;    // [nch], zeroed once; tags carry p_epoch
-  void* p_inc = nullptr;         // [nch] PlanChunk
-  uint4* p_tab = nullptr;        // [nch][kFuseLook]
-  uint32_t* p_jlim = nullptr;    // [nch]
-  size_t cap_pch = 0;
-  unsigned long long* p_ctr = nullptr;  // chunk claim counter (monotone across calls)
+  DevBuf<uint32_t> p_flag;       // [nch], zeroed once; tags carry p_epoch
+  DevBuf<uint8_t> p_inc;         // [nch] PlanChunk
+  DevBuf<uint4> p_tab;           // [nch][kFuseLook]
+  DevBuf<uint32_t> p_jlim;       // [nch]
+  DevBuf<unsigned long long> p_ctr;  // chunk claim counter (monotone across calls; zeroed once)
   unsigned long long p_base = 0;
   uint32_t p_epoch = 0;
   bool have_pl = false;          // pl / tile_pre hold the row prefix (E1-E2 ran)
-  EncTotals* d_tot = nullptr;
-  EncTotals* h_tot = nullptr;    // pinned
+  DevBuf<EncTotals> d_tot;
+  PinBuf<EncTotals> h_tot;
   // host-mode staging
-  uint8_t* d_in = nullptr;
-  size_t cap_in = 0;
-  uint8_t* d_outseg = nullptr;
-  size_t cap_outseg = 0;
-  uint8_t* close_buf[2] = {nullptr, nullptr};  // pinned D2H chunks of the meta block (Close)
+  DevBuf<uint8_t> d_in;
+  DevBuf<uint8_t> d_outseg;
+  PinBuf<uint8_t> close_buf[2];  // D2H chunks of the meta block (Close)
   hipEvent_t close_ev[2] = {nullptr, nullptr};
   // profiling (okv_encode_profile_read): cut, pack, hash, meta
   std::vector<hipEvent_t> ev;
@@ -140,20 +130,10 @@ struct EncScratch {
 void enc_release(okv_ctx* ctx) {
   EncScratch* e = ctx->enc;
   if (!e) return;
-  void* ps[] = {e->pl, e->nx, e->tile_tot, e->tile_pre, e->jt, e->jb, e->entry, e->kbase,
-                e->first, e->desc, e->hash, e->bsl, e->esl, e->moff, e->orig, e->fkl, e->fk, e->jts,
-                e->jbs, e->tentry, e->tkbase, e->btile,
-                e->d_tot, e->d_in, e->d_outseg, e->p_flag, e->p_inc, e->p_tab, e->p_jlim,
-                e->p_ctr};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  if (e->h_tot) (void)hipHostFree(e->h_tot);
-  for (int i = 0; i < 2; ++i) {
-    if (e->close_buf[i]) (void)hipHostFree(e->close_buf[i]);
-    if (e->close_ev[i]) (void)hipEventDestroy(e->close_ev[i]);
-  }
+  for (hipEvent_t v : e->close_ev)
+    if (v) (void)hipEventDestroy(v);
   for (hipEvent_t v : e->ev) (void)hipEventDestroy(v);
-  delete e;
+  delete e;  // the buffers release themselves
   ctx->enc = nullptr;
 }
 
@@ -1896,94 +1876,50 @@ struct DevRows {
   uint64_t n;
 };
 
-int dev_realloc(okv_ctx* ctx, void** p, size_t bytes) {
-  if (*p) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  OKV_HIP(hipMalloc(p, std::max<size_t>(bytes, 256)));
-  return OKV_OK;
-}
-
 int enc_scratch(okv_ctx* ctx, EncScratch** out) {
-  if (!ctx->enc) {
-    EncScratch* e = new EncScratch();
-    ctx->enc = e;
-    OKV_HIP(hipMalloc(&e->d_tot, sizeof(EncTotals)));
-    OKV_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->h_tot), sizeof(EncTotals), 0));
-  }
-  *out = ctx->enc;
-  return OKV_OK;
+  if (!ctx->enc) ctx->enc = new EncScratch();
+  EncScratch* e = *out = ctx->enc;
+  int rc;
+  if ((rc = reserve(ctx, e->d_tot, 1))) return rc;
+  return reserve(ctx, e->h_tot, 1);
 }
 
 int ensure_tiles(okv_ctx* ctx, EncScratch* e, uint64_t n) {
   const uint64_t nt = (n + kETile - 1) / kETile + 1;
   int rc;
-  if (nt > e->cap_tiles || !e->tile_tot) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->tile_tot), nt * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->tile_pre), nt * 8))) return rc;
-    e->cap_tiles = nt;
-  }
-  return OKV_OK;
+  if ((rc = reserve(ctx, e->tile_tot, nt))) return rc;
+  return reserve(ctx, e->tile_pre, nt);
 }
 
 int ensure_rows(okv_ctx* ctx, EncScratch* e, uint64_t n) {
-  const uint64_t nt = (n + kETile - 1) / kETile + 1;
   int rc;
-  if (n > e->cap_rows || !e->pl) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->pl), n * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->nx), n * 4))) return rc;
-    e->cap_rows = n;
-  }
-  if (nt > e->cap_tiles || !e->tile_tot) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->tile_tot), nt * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->tile_pre), nt * 8))) return rc;
-    e->cap_tiles = nt;
-  }
-  return OKV_OK;
+  if ((rc = reserve(ctx, e->pl, n)) || (rc = reserve(ctx, e->nx, n))) return rc;
+  return ensure_tiles(ctx, e, n);
 }
 
 int ensure_jump(okv_ctx* ctx, EncScratch* e, size_t entries, uint64_t nch) {
   int rc;
-  if (entries > e->cap_jump || !e->jt) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->jt), entries * 4))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->jb), entries * 4))) return rc;
-    e->cap_jump = entries;
-  }
-  if (nch > e->cap_chunks || !e->entry) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->entry), nch * 4))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->kbase), nch * 8))) return rc;
-    e->cap_chunks = nch;
-  }
-  return OKV_OK;
+  if ((rc = reserve(ctx, e->jt, entries)) || (rc = reserve(ctx, e->jb, entries)) ||
+      (rc = reserve(ctx, e->entry, nch)))
+    return rc;
+  return reserve(ctx, e->kbase, nch);
 }
 
 int ensure_blocks_enc(okv_ctx* ctx, EncScratch* e, uint64_t nb) {
   const uint64_t nbt = (nb + kETile - 1) / kETile + 1;
+  const size_t c = nb + 1;
   int rc;
-  if (nb + 1 > e->cap_blocks || !e->first) {
-    const size_t c = nb + 1;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->first), c * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->desc), c * sizeof(Desc)))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->hash), c * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->bsl), c * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->esl), c * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->moff), c * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->orig), c * 8))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->fkl), c * 2))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->fk), c * kFkStride))) return rc;
-    e->cap_blocks = c;
-  }
-  if (nbt > e->cap_btiles || !e->btile) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->btile), 4 * nbt * 8))) return rc;
-    e->cap_btiles = nbt;
-  }
-  return OKV_OK;
+  if ((rc = reserve(ctx, e->first, c)) || (rc = reserve(ctx, e->desc, c)) ||
+      (rc = reserve(ctx, e->hash, c)) || (rc = reserve(ctx, e->bsl, c)) ||
+      (rc = reserve(ctx, e->esl, c)) || (rc = reserve(ctx, e->moff, c)) ||
+      (rc = reserve(ctx, e->orig, c)) || (rc = reserve(ctx, e->fkl, c)) ||
+      (rc = reserve(ctx, e->fk, c * kFkStride)))
+    return rc;
+  return reserve(ctx, e->btile, 4 * nbt);
 }
 
 int read_enc_totals(okv_ctx* ctx, EncScratch* e) {
-  OKV_HIP(hipMemcpyAsync(e->h_tot, e->d_tot, sizeof(EncTotals), hipMemcpyDeviceToHost,
+  OKV_HIP(hipMemcpyAsync(e->h_tot.data(), e->d_tot.data(), sizeof(EncTotals), hipMemcpyDeviceToHost,
                          ctx->stream));
   OKV_HIP(hipStreamSynchronize(ctx->stream));
   return OKV_OK;
@@ -2017,10 +1953,10 @@ int enc_row_prefix(okv_ctx* ctx, EncScratch* e, const DevRows& R, uint64_t T) {
   int rc;
   if ((rc = ensure_rows(ctx, e, R.n))) return rc;
   const uint32_t ntiles = ceil_div(R.n, kETile);
-  hipLaunchKernelGGL(okv_enc_size_next_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
-                     R.kl, R.vl, R.n, T, e->pl, e->tile_tot, e->nx, e->d_tot);
-  hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, e->tile_tot,
-                     uint64_t(ntiles), e->tile_pre, nullptr);
+  hipLaunchKernelGGL(okv_enc_size_next_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, R.kl,
+                     R.vl, R.n, T, e->pl.data(), e->tile_tot.data(), e->nx.data(), e->d_tot.data());
+  hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, e->tile_tot.data(),
+                     uint64_t(ntiles), e->tile_pre.data(), nullptr);
   OKV_HIP(hipGetLastError());
   e->have_pl = true;
   return OKV_OK;
@@ -2032,14 +1968,10 @@ int enc_row_prefix(okv_ctx* ctx, EncScratch* e, const DevRows& R, uint64_t T) {
 
 int ensure_cut(okv_ctx* ctx, EncScratch* e, uint64_t ntiles) {
   int rc;
-  if (ntiles * kCutS > e->cap_cut || !e->jts) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->jts), ntiles * kCutS * 2))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->jbs), ntiles * kCutS * 2))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->tentry), ntiles * 4))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->tkbase), ntiles * 8))) return rc;
-    e->cap_cut = ntiles * kCutS;
-  }
-  return OKV_OK;
+  if ((rc = reserve(ctx, e->jts, ntiles * kCutS)) || (rc = reserve(ctx, e->jbs, ntiles * kCutS)) ||
+      (rc = reserve(ctx, e->tentry, ntiles)))
+    return rc;
+  return reserve(ctx, e->tkbase, ntiles);
 }
 
 // Block boundaries, BlockStat sizes/offsets and meta layout (E1-E9).
@@ -2052,10 +1984,10 @@ int enc_plan(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
   // the tile cut (E1 + E3 + E4 in LDS per tile, no per-row arrays)
   if ((rc = ensure_cut(ctx, e, ntiles)) || (rc = ensure_tiles(ctx, e, n))) return rc;
   e->have_pl = false;
-  hipLaunchKernelGGL(okv_enc_init_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot);
+  hipLaunchKernelGGL(okv_enc_init_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot.data());
   hipLaunchKernelGGL(okv_enc_cut_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, R.kl, R.vl,
-                     n, T, e->jts, e->jbs, e->tile_tot, e->d_tot);
-  hipLaunchKernelGGL(okv_enc_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, e->tile_tot,
+                     n, T, e->jts.data(), e->jbs.data(), e->tile_tot.data(), e->d_tot.data());
+  hipLaunchKernelGGL(okv_enc_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, e->tile_tot.data(),
                      uint64_t(ntiles), &e->d_tot->total_raw);
   OKV_HIP(hipGetLastError());
   if ((rc = read_enc_totals(ctx, e))) return rc;
@@ -2065,14 +1997,14 @@ int enc_plan(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
     // row, E3 over the global prefix)
     if ((rc = ensure_rows(ctx, e, n))) return rc;
     e->have_pl = true;
-    hipLaunchKernelGGL(okv_enc_init_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot);
-    hipLaunchKernelGGL(okv_enc_size_next_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
-                       R.kl, R.vl, n, T, e->pl, e->tile_tot, e->nx, e->d_tot);
-    hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, e->tile_tot,
-                       uint64_t(ntiles), e->tile_pre, &e->d_tot->total_raw);
-    hipLaunchKernelGGL(okv_enc_init_wmax_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot);
-    hipLaunchKernelGGL(okv_enc_next_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, e->pl,
-                       e->tile_pre, n, T, e->nx, e->d_tot);
+    hipLaunchKernelGGL(okv_enc_init_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot.data());
+    hipLaunchKernelGGL(okv_enc_size_next_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, R.kl,
+                       R.vl, n, T, e->pl.data(), e->tile_tot.data(), e->nx.data(), e->d_tot.data());
+    hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, e->tile_tot.data(),
+                       uint64_t(ntiles), e->tile_pre.data(), &e->d_tot->total_raw);
+    hipLaunchKernelGGL(okv_enc_init_wmax_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot.data());
+    hipLaunchKernelGGL(okv_enc_next_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
+                       e->pl.data(), e->tile_pre.data(), n, T, e->nx.data(), e->d_tot.data());
     OKV_HIP(hipGetLastError());
     if ((rc = read_enc_totals(ctx, e))) return rc;
   }
@@ -2093,20 +2025,21 @@ int enc_plan(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
   if (lv >= (uint64_t(1) << 32))  // (the chain-table kernels index with 32 bits)
     return set_err(ctx, OKV_E_ARG, "encode: too many rows for one call (chain table >= 2^32)");
   if ((rc = ensure_jump(ctx, e, lv * std::max<uint32_t>(levels, 1), nch))) return rc;
+  uint32_t *const jt = e->jt.data(), *const jb = e->jb.data();
   if (tile_cut)
     hipLaunchKernelGGL(okv_enc_compose_kernel, dim3(ceil_div(lv, kThreads)), dim3(kThreads), 0,
-                       ctx->stream, e->jts, e->jbs, uint64_t(ntiles), nch, uint32_t(W), e->jt,
-                       e->jb);
+                       ctx->stream, e->jts.data(), e->jbs.data(), uint64_t(ntiles), nch,
+                       uint32_t(W), jt, jb);
   else
     hipLaunchKernelGGL(okv_enc_jump0_kernel, dim3(ceil_div(lv, kThreads)), dim3(kThreads), 0,
-                       ctx->stream, e->nx, n, C, uint32_t(W), nch, e->jt, e->jb);
+                       ctx->stream, e->nx.data(), n, C, uint32_t(W), nch, jt, jb);
   for (uint32_t k = 1; k < levels; ++k)
     hipLaunchKernelGGL(okv_enc_jump_kernel, dim3(ceil_div(lv, kThreads)), dim3(kThreads), 0,
-                       ctx->stream, e->jt + (k - 1) * lv, e->jb + (k - 1) * lv, e->jt + k * lv,
-                       e->jb + k * lv, uint32_t(W), nch, uint64_t(1) << (k - 1), e->d_tot);
+                       ctx->stream, jt + (k - 1) * lv, jb + (k - 1) * lv, jt + k * lv,
+                       jb + k * lv, uint32_t(W), nch, uint64_t(1) << (k - 1), e->d_tot.data());
   hipLaunchKernelGGL(okv_enc_resolve_kernel, dim3(ceil_div(nch, kThreads)), dim3(kThreads), 0,
-                     ctx->stream, e->jt, e->jb, levels, uint32_t(W), nch, e->entry, e->kbase,
-                     e->d_tot);
+                     ctx->stream, e->jt.data(), e->jb.data(), levels, uint32_t(W), nch,
+                     e->entry.data(), e->kbase.data(), e->d_tot.data());
   OKV_HIP(hipGetLastError());
   if ((rc = read_enc_totals(ctx, e))) return rc;
   const uint64_t nb = e->h_tot->nb;
@@ -2114,25 +2047,27 @@ int enc_plan(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
     return set_err(ctx, OKV_E_HIP, "encode: inconsistent block count");
   if ((rc = ensure_blocks_enc(ctx, e, nb))) return rc;
   const uint32_t nbt = ceil_div(nb, kETile);
-  uint64_t* btot = e->btile;
-  uint64_t* bpre = e->btile + e->cap_btiles;
-  uint64_t* etot = e->btile + 2 * e->cap_btiles;
-  uint64_t* epre = e->btile + 3 * e->cap_btiles;
+  const size_t bstride = e->btile.capacity() / 4;
+  uint64_t* btot = e->btile.data();
+  uint64_t* bpre = btot + bstride;
+  uint64_t* etot = btot + 2 * bstride;
+  uint64_t* epre = btot + 3 * bstride;
   if (tile_cut) {
     hipLaunchKernelGGL(okv_enc_tile_entry_kernel, dim3(ceil_div(ntiles, kThreads)), dim3(kThreads),
-                       0, ctx->stream, e->jts, e->jbs, e->entry, e->kbase, uint64_t(ntiles),
-                       e->tentry, e->tkbase);
-    hipLaunchKernelGGL(okv_enc_emit_tile_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
-                       R.kl, R.vl, n, T, e->tentry, e->tkbase, e->first, e->orig, e->fkl, nb,
-                       uint64_t(ntiles), e->d_tot);
+                       0, ctx->stream, e->jts.data(), e->jbs.data(), e->entry.data(),
+                       e->kbase.data(), uint64_t(ntiles), e->tentry.data(), e->tkbase.data());
+    hipLaunchKernelGGL(okv_enc_emit_tile_kernel, dim3(ntiles), dim3(kThreads), 0, ctx->stream, R.kl,
+                       R.vl, n, T, e->tentry.data(), e->tkbase.data(), e->first.data(),
+                       e->orig.data(), e->fkl.data(), nb, uint64_t(ntiles), e->d_tot.data());
   }
   else
     hipLaunchKernelGGL(okv_enc_emit_kernel, dim3(ceil_div(nch, kThreads)), dim3(kThreads), 0,
-                       ctx->stream, e->nx, n, C, nch, e->entry, e->kbase, e->first, nb, e->pl,
-                       e->tile_pre, R.kl, e->orig, e->fkl, e->d_tot);
+                       ctx->stream, e->nx.data(), n, C, nch, e->entry.data(), e->kbase.data(),
+                       e->first.data(), nb, e->pl.data(), e->tile_pre.data(), R.kl, e->orig.data(),
+                       e->fkl.data(), e->d_tot.data());
   StatParams sp;
-  sp.orig = e->orig;
-  sp.fkl = e->fkl;
+  sp.orig = e->orig.data();
+  sp.fkl = e->fkl.data();
   sp.nb = nb;
   sp.D = D;
   sp.dshift = 64;
@@ -2140,20 +2075,21 @@ int enc_plan(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
     for (sp.dshift = 0; (uint64_t(1) << sp.dshift) != D; ++sp.dshift) {
     }
   sp.lz4 = o.compression == OKV_COMP_LZ4;
-  sp.desc = e->desc;
-  sp.bsl = e->bsl;
-  sp.esl = e->esl;
+  sp.desc = e->desc.data();
+  sp.bsl = e->bsl.data();
+  sp.esl = e->esl.data();
   sp.btile_tot = btot;
   sp.etile_tot = etot;
-  sp.tot = e->d_tot;
+  sp.tot = e->d_tot.data();
   hipLaunchKernelGGL(okv_enc_stat_kernel, dim3(nbt), dim3(kThreads), 0, ctx->stream, sp);
   hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, btot,
                      uint64_t(nbt), bpre, &e->d_tot->data_bytes);
   hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, etot,
                      uint64_t(nbt), epre, &e->d_tot->meta_ent);
   hipLaunchKernelGGL(okv_enc_offset_kernel, dim3(ceil_div(nb, kThreads)), dim3(kThreads), 0,
-                     ctx->stream, e->desc, e->bsl, e->esl, bpre, epre, nb, R.kl, n, e->first,
-                     e->moff, e->d_tot, o.bloom ? 8 + o.bloom_len : 0);
+                     ctx->stream, e->desc.data(), e->bsl.data(), e->esl.data(), bpre, epre, nb,
+                     R.kl, n, e->first.data(), e->moff.data(), e->d_tot.data(),
+                     o.bloom ? 8 + o.bloom_len : 0);
   OKV_HIP(hipGetLastError());
   if ((rc = read_enc_totals(ctx, e))) return rc;
   if (e->h_tot->fault) return set_err(ctx, OKV_E_HIP, "encode: block chain inconsistent");
@@ -2200,12 +2136,12 @@ int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
   // none), so the parameters take its buffers after the call
   if ((rc = enc_row_prefix(ctx, e, R, o.threshold_bytes))) return rc;
   PackParams q = pp;
-  q.pl = e->pl;
-  q.tp = e->tile_pre;
+  q.pl = e->pl.data();
+  q.tp = e->tile_pre.data();
   // precondition of every kernel below: the row prefix exists (round 5 launched
   // them with a null prefix after the tile cut stopped writing it -- an illegal
   // address on the device)
-  if (!e->have_pl || !q.pl || !q.tp || e->cap_rows < R.n)
+  if (!e->have_pl || !q.pl || !q.tp || e->pl.capacity() < R.n)
     return set_err(ctx, OKV_E_ARG, "enc_pack: row prefix missing for the chunk-major kernels");
   if (aligned && G >= 1) {  // large records: chunk-major regions
     hipLaunchKernelGGL(okv_enc_pack_region_kernel<0>, dim3(ceil_div(pl.nb, G)), dim3(kThreads), 0,
@@ -2236,15 +2172,15 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
   pp.val_arena = R.va;
   pp.val_off = R.vo;
   pp.val_len = R.vl;
-  pp.pl = e->pl;  // (null until the row prefix is computed: enc_pack / the ablation arms)
-  pp.tp = e->tile_pre;
-  pp.first = e->first;
-  pp.desc = e->desc;
+  pp.pl = e->pl.data();  // (null until the row prefix is computed: enc_pack / the ablation arms)
+  pp.tp = e->tile_pre.data();
+  pp.first = e->first.data();
+  pp.desc = e->desc.data();
   pp.seg = seg;
-  pp.hash = e->hash;
+  pp.hash = e->hash.data();
   pp.meta = nullptr;
-  pp.moff = e->moff;
-  pp.fk = e->fk;
+  pp.moff = e->moff.data();
+  pp.fk = e->fk.data();
   bool hashed = false, meta_done = false, fk_done = false;
   int rc;
 #ifdef OKV_ABLATE
@@ -2254,25 +2190,26 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
 #endif
     if ((rc = enc_pack(ctx, e, R, o, pl, seg, pp, &hashed, &fk_done))) return rc;
   enc_mark(ctx, e, 2);
-  if (!hashed) launch_hash(ctx->stream, seg, pl.data_bytes, e->desc, uint32_t(pl.nb), e->hash);
+  if (!hashed)
+    launch_hash(ctx->stream, seg, pl.data_bytes, e->desc.data(), uint32_t(pl.nb), e->hash.data());
   enc_mark(ctx, e, 3);
   MetaParams mp;
   mp.key_arena = R.ka;
   mp.key_off = R.ko;
   mp.key_len = R.kl;
   mp.n = R.n;
-  mp.first = e->first;
-  mp.desc = e->desc;
-  mp.hash = e->hash;
-  mp.moff = e->moff;
+  mp.first = e->first.data();
+  mp.desc = e->desc.data();
+  mp.hash = e->hash.data();
+  mp.moff = e->moff.data();
   mp.nb = pl.nb;
   mp.count = pl.nb;
   mp.comp_byte = o.compression == OKV_COMP_LZ4 ? 2 : 0;
   mp.meta = seg + pl.data_bytes;
   mp.bloom_len = o.bloom ? o.bloom_len : ~uint64_t(0);
   mp.seg = o.compression == OKV_COMP_NONE ? seg : nullptr;
-  mp.fk = fk_done ? e->fk : nullptr;
-  mp.fkl = e->fkl;
+  mp.fk = fk_done ? e->fk.data() : nullptr;
+  mp.fkl = e->fkl.data();
   if (o.bloom && o.bloom_len)  // BloomFilter.WriteTo bytes at head - 10 - len (after flag + u64)
     OKV_HIP(hipMemcpyAsync(mp.meta + pl.head - 10 - o.bloom_len, o.bloom, o.bloom_len,
                            hipMemcpyHostToDevice, ctx->stream));
@@ -2367,15 +2304,14 @@ int close_device(okv_ctx* ctx, EncScratch* e, okv_encode_out* out) {
   constexpr uint64_t kPiece = 8ull << 20;  // multiple of 32 (XXH64 stripes)
   uint8_t* meta = out->seg + out->data_bytes;
   for (int i = 0; i < 2; ++i) {
-    if (!e->close_buf[i]) OKV_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->close_buf[i]),
-                                                kPiece, 0));
+    if (int rc = reserve(ctx, e->close_buf[i], kPiece)) return rc;
     if (!e->close_ev[i]) OKV_HIP(hipEventCreateWithFlags(&e->close_ev[i],
                                                          hipEventDisableTiming));
   }
   const uint64_t mb = out->meta_bytes, np = (mb + kPiece - 1) / kPiece;
   auto issue = [&](uint64_t k) -> int {
     const uint64_t o = k * kPiece, n = std::min(kPiece, mb - o);
-    OKV_HIP(hipMemcpyAsync(e->close_buf[k & 1], meta + o, n, hipMemcpyDeviceToHost,
+    OKV_HIP(hipMemcpyAsync(e->close_buf[k & 1].data(), meta + o, n, hipMemcpyDeviceToHost,
                            ctx->stream));
     OKV_HIP(hipEventRecord(e->close_ev[k & 1], ctx->stream));
     return OKV_OK;
@@ -2388,8 +2324,8 @@ int close_device(okv_ctx* ctx, EncScratch* e, okv_encode_out* out) {
     if (k + 1 < np && (rc = issue(k + 1))) return rc;
     const uint64_t n = std::min(kPiece, mb - k * kPiece);
     const uint64_t whole = k + 1 < np ? n : n & ~uint64_t(31);
-    xs.stripes(e->close_buf[k & 1], whole);
-    if (k + 1 == np) out->meta_hash = xs.finish(e->close_buf[k & 1] + whole, n - whole);
+    xs.stripes(e->close_buf[k & 1].data(), whole);
+    if (k + 1 == np) out->meta_hash = xs.finish(e->close_buf[k & 1].data() + whole, n - whole);
   }
   if (!np) out->meta_hash = xs.finish(nullptr, 0);
   static thread_local uint8_t t[25];
@@ -2455,8 +2391,8 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
     const size_t oka = 0, ova = oka + al(rows->key_arena_bytes),
                  oko = ova + al(rows->val_arena_bytes), okl = oko + al(n * 8),
                  ovo = okl + al(n * 2), ovl = ovo + al(n * 8), end = ovl + al(n * 4);
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&e->d_in), &e->cap_in, end + 64))) return rc;
-    uint8_t* b = e->d_in;
+    if ((rc = reserve(ctx, e->d_in, end + 64))) return rc;
+    uint8_t* b = e->d_in.data();
     const hipMemcpyKind h2d = hipMemcpyHostToDevice;
     if (rows->key_arena_bytes)
       OKV_HIP(hipMemcpyAsync(b + oka, rows->key_arena, rows->key_arena_bytes, h2d, ctx->stream));
@@ -2499,19 +2435,17 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
     return set_err(ctx, OKV_E_CAPACITY, "encode output capacity too small (sizes set)");
   uint8_t* seg = out->seg;
   if (!dev) {
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&e->d_outseg), &e->cap_outseg,
-                   pl.file_bytes + 64)))
-      return rc;
-    seg = e->d_outseg;
+    if ((rc = reserve(ctx, e->d_outseg, pl.file_bytes + 64))) return rc;
+    seg = e->d_outseg.data();
   }
   if ((rc = enc_write(ctx, e, R, *opts, pl, seg))) return rc;
   const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (out->blk_first_row)
-    OKV_HIP(hipMemcpyAsync(out->blk_first_row, e->first, (pl.nb + 1) * 8, k, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(out->blk_first_row, e->first.data(), (pl.nb + 1) * 8, k, ctx->stream));
   if (out->blk_desc)
-    OKV_HIP(hipMemcpyAsync(out->blk_desc, e->desc, pl.nb * sizeof(Desc), k, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(out->blk_desc, e->desc.data(), pl.nb * sizeof(Desc), k, ctx->stream));
   if (out->blk_hash)
-    OKV_HIP(hipMemcpyAsync(out->blk_hash, e->hash, pl.nb * 8, k, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(out->blk_hash, e->hash.data(), pl.nb * 8, k, ctx->stream));
   if (!dev) {
     OKV_HIP(hipMemcpyAsync(out->seg, seg, pl.data_bytes + pl.meta_bytes, k, ctx->stream));
     OKV_HIP(hipStreamSynchronize(ctx->stream));

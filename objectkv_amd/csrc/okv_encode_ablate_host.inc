@@ -10,28 +10,27 @@ int enc_plan_fast(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encod
   int rc;
   *general = false;
   e->have_pl = false;
-  if (nch > e->cap_pch || !e->p_flag) {
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->p_flag), nch * 4))) return rc;
-    OKV_HIP(hipMemsetAsync(e->p_flag, 0, nch * 4, ctx->stream));
-    if ((rc = dev_realloc(ctx, &e->p_inc, nch * sizeof(PlanChunk)))) return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->p_tab), nch * kFuseLook * 16)))
-      return rc;
-    if ((rc = dev_realloc(ctx, reinterpret_cast<void**>(&e->p_jlim), nch * 4))) return rc;
-    e->cap_pch = nch;
-  }
-  if (!e->p_ctr) {
-    OKV_HIP(hipMalloc(&e->p_ctr, sizeof(unsigned long long)));
-    OKV_HIP(hipMemsetAsync(e->p_ctr, 0, sizeof(unsigned long long), ctx->stream));
+  bool fresh = false;
+  if ((rc = reserve(ctx, e->p_flag, nch, &fresh))) return rc;
+  if (fresh) OKV_HIP(hipMemsetAsync(e->p_flag.data(), 0, e->p_flag.bytes(), ctx->stream));
+  if ((rc = reserve(ctx, e->p_inc, nch * sizeof(PlanChunk))) ||
+      (rc = reserve(ctx, e->p_tab, nch * kFuseLook)) || (rc = reserve(ctx, e->p_jlim, nch)))
+    return rc;
+  fresh = false;
+  if ((rc = reserve(ctx, e->p_ctr, 1, &fresh))) return rc;
+  if (fresh) {
+    OKV_HIP(hipMemsetAsync(e->p_ctr.data(), 0, e->p_ctr.bytes(), ctx->stream));
     e->p_base = 0;
   }
   // per-block outputs: the last capacity, or a guess (a block of 4 KiB holds
   // tens of small rows); a launch that finds more blocks is rerun once
-  uint64_t cap = std::max<uint64_t>(e->cap_blocks ? e->cap_blocks - 1 : 0, n / 32 + 1024);
+  uint64_t cap = std::max<uint64_t>(e->first.capacity() ? e->first.capacity() - 1 : 0,
+                                    n / 32 + 1024);
   cap = std::min<uint64_t>(cap, n);
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = ensure_blocks_enc(ctx, e, cap))) return rc;
     enc_mark(ctx, e, 0);
-    hipLaunchKernelGGL(okv_enc_init_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot);
+    hipLaunchKernelGGL(okv_enc_init_kernel, dim3(1), dim3(1), 0, ctx->stream, e->d_tot.data());
     PlanParams P;
     P.key_len = R.kl;
     P.val_len = R.vl;
@@ -41,19 +40,19 @@ int enc_plan_fast(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encod
     P.lz4 = o.compression == OKV_COMP_LZ4;
     P.bloom_extra = o.bloom ? 8 + o.bloom_len : 0;
     P.nch = nch;
-    P.flag = e->p_flag;
-    P.inc = static_cast<PlanChunk*>(e->p_inc);
-    P.tab = e->p_tab;
-    P.jlim = e->p_jlim;
-    P.ctr = e->p_ctr;
+    P.flag = e->p_flag.data();
+    P.inc = reinterpret_cast<PlanChunk*>(e->p_inc.data());
+    P.tab = e->p_tab.data();
+    P.jlim = e->p_jlim.data();
+    P.ctr = e->p_ctr.data();
     P.base = e->p_base;
     e->p_epoch = (e->p_epoch % 0x3fffffffu) + 1;  // never 0 (the zeroed flags)
     P.epoch = e->p_epoch;
     P.cap = cap;
-    P.first = e->first;
-    P.desc = e->desc;
-    P.moff = e->moff;
-    P.tot = e->d_tot;
+    P.first = e->first.data();
+    P.desc = e->desc.data();
+    P.moff = e->moff.data();
+    P.tot = e->d_tot.data();
     hipLaunchKernelGGL(okv_enc_plan_kernel, dim3(uint32_t(nch)), dim3(kThreads), 0, ctx->stream,
                        P);
     const hipError_t le = hipGetLastError();

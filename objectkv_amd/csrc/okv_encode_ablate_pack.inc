@@ -46,20 +46,20 @@ int enc_pack_ablate(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_enc
   if (!(lds && (EV == 7 || EV == 10) && (img == kImage || img == 65536 || img == 32768)) &&
       (rc = enc_row_prefix(ctx, e, R, o.threshold_bytes)))
     return rc;
-  pp.pl = e->pl;  // (allocated by the call above)
-  pp.tp = e->tile_pre;
+  pp.pl = e->pl.data();  // (allocated by the call above)
+  pp.tp = e->tile_pre.data();
   const dim3 blk(kThreads);
   if (lds) {
     const dim3 grid(ceil_div(pl.nb, GLa));
     if (img == 65536) {
-      pp.fk = e->fk;
+      pp.fk = e->fk.data();
       hipLaunchKernelGGL((okv_enc_pack_lds_kernel<65536, 7, false, 1024>), grid, dim3(1024), 0,
                          ctx->stream, pp, pl.nb, uint32_t(GLa));
       *hashed = true;
       return OKV_OK;
     }
     if (img == 32768 && EV == 10) {  // 32 KiB image, 512 threads: one wave hashes 8 blocks
-      pp.fk = e->fk;
+      pp.fk = e->fk.data();
       hipLaunchKernelGGL((okv_enc_pack_lds_kernel<32768, 7, false, 512>), grid, dim3(512), 0,
                          ctx->stream, pp, pl.nb, uint32_t(GLa));
       *hashed = true;

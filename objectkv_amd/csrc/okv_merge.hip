@@ -67,27 +67,23 @@ struct Key16 {
 };
 
 struct Scratch {
-  uint64_t cap_rows = 0;
-  uint64_t* kaddr = nullptr;  // [N] key address
-  Key16* pfx = nullptr;       // [N] big-endian first 16 key bytes (zero padded)
-  uint32_t* klen = nullptr;   // [N]
-  uint64_t* pos = nullptr;    // [N] merged position
-  uint8_t* own = nullptr;     // [N] owns its key
-  uint64_t* mg = nullptr;     // [N] merged order -> global row
-  uint32_t* mown = nullptr;   // [N + 1] owner flag in merged order, then its exclusive scan
-  uint64_t* uniq = nullptr;   // [N] unique key -> owning global row
-  uint8_t* ev = nullptr;      // [N] outcome per unique key, direction order
-  uint32_t* escan = nullptr;  // [N + 1] emit flags, then their exclusive scan
-  uint32_t cap_blk = 0;
-  uint32_t* bsum = nullptr;   // scan block sums
-  uint64_t* split = nullptr;  // [ceil(N / 256)][K][2] rank-kernel search windows
-  size_t cap_split = 0;
-  Src* d_src = nullptr;
-  uint64_t* d_base = nullptr;  // [K + 1] stream offsets in the global row numbering
-  uint8_t* d_bound = nullptr;
-  size_t cap_bound = 0;
-  uint64_t* d_misc = nullptr;  // [0] first termination, [1] its code, [2..] per-stream end key index
-  uint64_t* h_misc = nullptr;  // pinned
+  DevBuf<uint64_t> kaddr;   // [N] key address
+  DevBuf<Key16> pfx;        // [N] big-endian first 16 key bytes (zero padded)
+  DevBuf<uint32_t> klen;    // [N]
+  DevBuf<uint64_t> pos;     // [N] merged position
+  DevBuf<uint8_t> own;      // [N] owns its key
+  DevBuf<uint64_t> mg;      // [N] merged order -> global row
+  DevBuf<uint32_t> mown;    // [N + 1] owner flag in merged order, then its exclusive scan
+  DevBuf<uint64_t> uniq;    // [N] unique key -> owning global row
+  DevBuf<uint8_t> ev;       // [N] outcome per unique key, direction order
+  DevBuf<uint32_t> escan;   // [N + 1] emit flags, then their exclusive scan
+  DevBuf<uint32_t> bsum;    // scan block sums
+  DevBuf<uint64_t> split;   // [ceil(N / 256)][K][2] rank-kernel search windows
+  DevBuf<Src> d_src;
+  DevBuf<uint64_t> d_base;  // [K + 1] stream offsets in the global row numbering
+  DevBuf<uint8_t> d_bound;
+  DevBuf<uint64_t> d_misc;  // [0] first termination, [1] its code, [2..] per-stream end key index
+  PinBuf<uint64_t> h_misc;
 };
 
 __device__ __forceinline__ uint32_t find_src(const uint64_t* __restrict__ base, uint32_t k,
@@ -521,66 +517,44 @@ namespace {
 
 int scan_u32(okv_ctx* ctx, mrg::Scratch* m, uint32_t* x, uint64_t n, uint32_t* total) {
   const uint32_t nb = uint32_t((n + 4095) / 4096);
-  if (nb > m->cap_blk) {
-    OKV_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(m->bsum);
-    OKV_HIP(hipMalloc(&m->bsum, (size_t(nb) + 1) * 4));
-    m->cap_blk = nb;
-  }
+  if (nb)
+    if (int rc = reserve(ctx, m->bsum, size_t(nb) + 1)) return rc;
   if (nb) {
     hipLaunchKernelGGL(okv_mscan_block_kernel, dim3(nb), dim3(1024), 0, ctx->stream, x, n,
-                       m->bsum);
-    hipLaunchKernelGGL(okv_mscan_sums_kernel, dim3(1), dim3(1024), 0, ctx->stream, m->bsum, nb,
-                       total);
-    hipLaunchKernelGGL(okv_mscan_add_kernel, dim3(nb), dim3(1024), 0, ctx->stream, x, n, m->bsum);
+                       m->bsum.data());
+    hipLaunchKernelGGL(okv_mscan_sums_kernel, dim3(1), dim3(1024), 0, ctx->stream, m->bsum.data(),
+                       nb, total);
+    hipLaunchKernelGGL(okv_mscan_add_kernel, dim3(nb), dim3(1024), 0, ctx->stream, x, n,
+                       m->bsum.data());
   } else {
     OKV_HIP(hipMemsetAsync(total, 0, 4, ctx->stream));
   }
   return OKV_OK;
 }
 
+// Every per-row array holds n + 16 elements; one that has to grow is given an
+// eighth more rows than asked (at least 4096), so that a merge a little larger
+// than the last does not allocate again.
 int ensure(okv_ctx* ctx, mrg::Scratch* m, uint64_t n) {
-  if (!m->d_src) {
-    OKV_HIP(hipMalloc(&m->d_src, sizeof(mrg::Src) * mrg::kMaxSrc));
-    OKV_HIP(hipMalloc(&m->d_base, 8 * (mrg::kMaxSrc + 1)));
-    OKV_HIP(hipMalloc(&m->d_misc, 8 * (mrg::kMaxSrc + 8)));
-    OKV_HIP(hipHostMalloc(&m->h_misc, 8 * (mrg::kMaxSrc + 8)));
-  }
-  if (n <= m->cap_rows && m->kaddr) return OKV_OK;
-  OKV_HIP(hipStreamSynchronize(ctx->stream));
-  void** ps[] = {reinterpret_cast<void**>(&m->kaddr), reinterpret_cast<void**>(&m->pfx),
-                 reinterpret_cast<void**>(&m->klen),  reinterpret_cast<void**>(&m->pos),
-                 reinterpret_cast<void**>(&m->own),   reinterpret_cast<void**>(&m->mg),
-                 reinterpret_cast<void**>(&m->mown),  reinterpret_cast<void**>(&m->uniq),
-                 reinterpret_cast<void**>(&m->ev),    reinterpret_cast<void**>(&m->escan)};
-  const size_t sz[] = {8, sizeof(mrg::Key16), 4, 8, 1, 8, 4, 8, 1, 4};
-  const uint64_t c = std::max<uint64_t>(n + n / 8, 4096);
-  for (int q = 0; q < 10; ++q) {
-    (void)hipFree(*ps[q]);
-    *ps[q] = nullptr;
-    OKV_HIP(hipMalloc(ps[q], sz[q] * (c + 16)));
-  }
-  m->cap_rows = c;
+  int rc;
+  if ((rc = reserve(ctx, m->d_src, mrg::kMaxSrc)) ||
+      (rc = reserve(ctx, m->d_base, mrg::kMaxSrc + 1)) ||
+      (rc = reserve(ctx, m->d_misc, mrg::kMaxSrc + 8)) ||
+      (rc = reserve(ctx, m->h_misc, mrg::kMaxSrc + 8)))
+    return rc;
+  const size_t room = std::max<uint64_t>(n + n / 8, 4096) + 16;
+  auto rows = [&](auto& b) { return n + 16 <= b.capacity() ? OKV_OK : reserve(ctx, b, room); };
+  if ((rc = rows(m->kaddr)) || (rc = rows(m->pfx)) || (rc = rows(m->klen)) ||
+      (rc = rows(m->pos)) || (rc = rows(m->own)) || (rc = rows(m->mg)) || (rc = rows(m->mown)) ||
+      (rc = rows(m->uniq)) || (rc = rows(m->ev)) || (rc = rows(m->escan)))
+    return rc;
   return OKV_OK;
 }
 
 }  // namespace
 
 void merge_release(okv_ctx* ctx) {
-  mrg::Scratch* m = ctx->merge;
-  if (!m) return;
-  for (void* p : {static_cast<void*>(m->kaddr), static_cast<void*>(m->pfx),
-                  static_cast<void*>(m->klen), static_cast<void*>(m->pos),
-                  static_cast<void*>(m->own), static_cast<void*>(m->mg),
-                  static_cast<void*>(m->mown), static_cast<void*>(m->uniq),
-                  static_cast<void*>(m->ev), static_cast<void*>(m->escan),
-                  static_cast<void*>(m->bsum), static_cast<void*>(m->split),
-                  static_cast<void*>(m->d_src),
-                  static_cast<void*>(m->d_base), static_cast<void*>(m->d_bound),
-                  static_cast<void*>(m->d_misc)})
-    (void)hipFree(p);
-  if (m->h_misc) (void)hipHostFree(m->h_misc);
-  delete m;
+  delete ctx->merge;  // the buffers release themselves
   ctx->merge = nullptr;
 }
 
@@ -612,62 +586,67 @@ int okv_merge_rows(okv_ctx* ctx, const okv_merge_src* srcs, uint32_t nsrc,
   if ((rc = ensure(ctx, m, n))) return rc;
   hipStream_t s = ctx->stream;
   if (nsrc) {
-    OKV_HIP(hipMemcpyAsync(m->d_src, srcs, sizeof(mrg::Src) * nsrc, hipMemcpyHostToDevice, s));
-    OKV_HIP(hipMemcpyAsync(m->d_base, base.data(), 8 * (nsrc + 1), hipMemcpyHostToDevice, s));
+    OKV_HIP(hipMemcpyAsync(m->d_src.data(), srcs, sizeof(mrg::Src) * nsrc, hipMemcpyHostToDevice,
+                           s));
+    OKV_HIP(hipMemcpyAsync(m->d_base.data(), base.data(), 8 * (nsrc + 1), hipMemcpyHostToDevice,
+                           s));
   }
   const uint32_t blen = opts->mode == OKV_MERGE_GETRANGE ? uint32_t(opts->bound_len) : 0;
   if (opts->bound_len > 0xffff) return OKV_E_ARG;  // keys are at most 65535 bytes
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&m->d_bound), &m->cap_bound, blen + 16))) return rc;
-  if (blen) OKV_HIP(hipMemcpyAsync(m->d_bound, opts->bound, blen, hipMemcpyHostToDevice, s));
+  if ((rc = reserve(ctx, m->d_bound, blen + 16))) return rc;
+  if (blen) OKV_HIP(hipMemcpyAsync(m->d_bound.data(), opts->bound, blen, hipMemcpyHostToDevice, s));
   const dim3 b256(256);
   const dim3 gn(uint32_t((n + 255) / 256));
   out->n_rows = 0;
   out->n_unique = 0;
   out->status = 0;
   if (n == 0) return OKV_OK;
-  hipLaunchKernelGGL(okv_merge_pfx_kernel, gn, b256, 0, s, m->d_src, m->d_base, nsrc, n, m->kaddr,
-                     m->pfx, m->klen);
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&m->split), &m->cap_split,
-                 8 * 2 * nsrc * ((n + 255) / 256))))
-    return rc;
+  hipLaunchKernelGGL(okv_merge_pfx_kernel, gn, b256, 0, s, m->d_src.data(), m->d_base.data(), nsrc,
+                     n, m->kaddr.data(), m->pfx.data(), m->klen.data());
+  if ((rc = reserve(ctx, m->split, 2 * nsrc * ((n + 255) / 256)))) return rc;
   {
     const uint64_t ns = 2 * nsrc * ((n + 255) / 256);
     hipLaunchKernelGGL(okv_merge_split_kernel, dim3(uint32_t((ns + 255) / 256)), b256, 0, s,
-                       m->d_base, nsrc, n, m->kaddr, m->pfx, m->klen, m->split);
+                       m->d_base.data(), nsrc, n, m->kaddr.data(), m->pfx.data(), m->klen.data(),
+                       m->split.data());
   }
   static const int stage = [] {
     const char* e = okv::knob("OKV_MERGE_STAGE");  // A/B knob: 0 = windows searched in HBM / L2
     return e ? atoi(e) : 1;
   }();
-  hipLaunchKernelGGL(okv_merge_rank_kernel, gn, b256, 0, s, m->d_base, nsrc, n, m->kaddr, m->pfx,
-                     m->klen, m->split, stage, m->pos, m->own);
-  hipLaunchKernelGGL(okv_merge_scatter_kernel, gn, b256, 0, s, n, m->pos, m->own, m->mg, m->mown);
-  OKV_HIP(hipMemsetAsync(m->mown + n, 0, 4, s));
-  uint32_t* d_tot = reinterpret_cast<uint32_t*>(m->d_misc + 2 + mrg::kMaxSrc);
-  if ((rc = scan_u32(ctx, m, m->mown, n + 1, d_tot))) return rc;  // mown[n] = 0 pad -> total
-  hipLaunchKernelGGL(okv_merge_uniq_kernel, gn, b256, 0, s, n, m->mown, m->mg, m->uniq);
-  hipLaunchKernelGGL(okv_merge_ends_kernel, dim3(1), dim3(64), 0, s, m->d_base, nsrc,
-                     opts->direction, m->pos, m->mown, m->d_misc + 2);
-  OKV_HIP(hipMemcpyAsync(m->h_misc, d_tot, 4, hipMemcpyDeviceToHost, s));
+  hipLaunchKernelGGL(okv_merge_rank_kernel, gn, b256, 0, s, m->d_base.data(), nsrc, n,
+                     m->kaddr.data(), m->pfx.data(), m->klen.data(), m->split.data(), stage,
+                     m->pos.data(), m->own.data());
+  hipLaunchKernelGGL(okv_merge_scatter_kernel, gn, b256, 0, s, n, m->pos.data(), m->own.data(),
+                     m->mg.data(), m->mown.data());
+  OKV_HIP(hipMemsetAsync(m->mown.data() + n, 0, 4, s));
+  uint32_t* d_tot = reinterpret_cast<uint32_t*>(m->d_misc.data() + 2 + mrg::kMaxSrc);
+  if ((rc = scan_u32(ctx, m, m->mown.data(), n + 1, d_tot))) return rc;  // mown[n] = 0 pad -> total
+  hipLaunchKernelGGL(okv_merge_uniq_kernel, gn, b256, 0, s, n, m->mown.data(), m->mg.data(),
+                     m->uniq.data());
+  hipLaunchKernelGGL(okv_merge_ends_kernel, dim3(1), dim3(64), 0, s, m->d_base.data(), nsrc,
+                     opts->direction, m->pos.data(), m->mown.data(), m->d_misc.data() + 2);
+  OKV_HIP(hipMemcpyAsync(m->h_misc.data(), d_tot, 4, hipMemcpyDeviceToHost, s));
   OKV_HIP(hipStreamSynchronize(s));
-  const uint64_t nu = *reinterpret_cast<uint32_t*>(m->h_misc);
+  const uint64_t nu = *reinterpret_cast<uint32_t*>(m->h_misc.data());
   out->n_unique = nu;
   const dim3 gu(uint32_t((nu + 255) / 256));
-  hipLaunchKernelGGL(okv_merge_event_kernel, gu, b256, 0, s, m->d_src, m->d_base, nsrc, nu,
-                     opts->direction, opts->mode, opts->drop_tombstones, m->uniq, m->kaddr,
-                     m->pfx, m->klen, m->d_bound, blen, m->d_misc + 2, m->ev, m->escan);
-  OKV_HIP(hipMemsetAsync(m->escan + nu, 0, 4, s));
+  hipLaunchKernelGGL(okv_merge_event_kernel, gu, b256, 0, s, m->d_src.data(), m->d_base.data(),
+                     nsrc, nu, opts->direction, opts->mode, opts->drop_tombstones, m->uniq.data(),
+                     m->kaddr.data(), m->pfx.data(), m->klen.data(), m->d_bound.data(), blen,
+                     m->d_misc.data() + 2, m->ev.data(), m->escan.data());
+  OKV_HIP(hipMemsetAsync(m->escan.data() + nu, 0, 4, s));
   uint32_t* d_etot = d_tot + 1;
-  if ((rc = scan_u32(ctx, m, m->escan, nu + 1, d_etot))) return rc;
+  if ((rc = scan_u32(ctx, m, m->escan.data(), nu + 1, d_etot))) return rc;
   uint64_t stop = nu;
   int32_t status = 0;
   if (opts->mode == OKV_MERGE_GETRANGE) {
-    OKV_HIP(hipMemsetAsync(m->d_misc, 0xff, 8, s));
-    hipLaunchKernelGGL(okv_merge_term_kernel, gu, b256, 0, s, nu, m->ev, m->escan, opts->limit,
-                       reinterpret_cast<unsigned long long*>(m->d_misc));
-    OKV_HIP(hipMemcpyAsync(m->h_misc, m->d_misc, 8, hipMemcpyDeviceToHost, s));
+    OKV_HIP(hipMemsetAsync(m->d_misc.data(), 0xff, 8, s));
+    hipLaunchKernelGGL(okv_merge_term_kernel, gu, b256, 0, s, nu, m->ev.data(), m->escan.data(),
+                       opts->limit, reinterpret_cast<unsigned long long*>(m->d_misc.data()));
+    OKV_HIP(hipMemcpyAsync(m->h_misc.data(), m->d_misc.data(), 8, hipMemcpyDeviceToHost, s));
     OKV_HIP(hipStreamSynchronize(s));
-    const uint64_t t = m->h_misc[0];
+    const uint64_t t = m->h_misc.data()[0];
     if (t != ~0ull) {
       stop = t >> 3;
       const uint32_t code = uint32_t(t & 7);
@@ -675,18 +654,18 @@ int okv_merge_rows(okv_ctx* ctx, const okv_merge_src* srcs, uint32_t nsrc,
     }
   }
   // rows emitted before stop = escan[stop]
-  OKV_HIP(hipMemcpyAsync(m->h_misc, m->escan + stop, 4, hipMemcpyDeviceToHost, s));
+  OKV_HIP(hipMemcpyAsync(m->h_misc.data(), m->escan.data() + stop, 4, hipMemcpyDeviceToHost, s));
   OKV_HIP(hipStreamSynchronize(s));
-  const uint64_t nrows = *reinterpret_cast<uint32_t*>(m->h_misc);
+  const uint64_t nrows = *reinterpret_cast<uint32_t*>(m->h_misc.data());
   out->n_rows = nrows;
   out->status = status;
   if (status) return OKV_OK;  // Go returns (nil, err): no rows
   if (nrows > out->row_cap) return OKV_E_CAPACITY;
   if (nrows)
-    hipLaunchKernelGGL(okv_merge_out_kernel, gu, b256, 0, s, m->d_src, m->d_base, nsrc, nu,
-                       opts->direction, m->uniq, m->ev, m->escan, stop, out->row_cap, out->src,
-                       out->row, out->key_off, out->key_len, out->val_off, out->val_len,
-                       out->key_base, out->val_base);
+    hipLaunchKernelGGL(okv_merge_out_kernel, gu, b256, 0, s, m->d_src.data(), m->d_base.data(),
+                       nsrc, nu, opts->direction, m->uniq.data(), m->ev.data(), m->escan.data(),
+                       stop, out->row_cap, out->src, out->row, out->key_off, out->key_len,
+                       out->val_off, out->val_len, out->key_base, out->val_base);
   OKV_HIP(hipGetLastError());
   if (!(flags & OKV_F_ASYNC)) OKV_HIP(hipStreamSynchronize(s));
   return OKV_OK;

@@ -2849,47 +2849,38 @@ int zstd_regrow(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc
                 uint32_t nblk, uint64_t* total_io) {
   hipStream_t s = ctx->stream;
   int rc;
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_list), &ctx->z_cap_list,
-                 (size_t(nblk) + 1) * 4 + 64)))
-    return rc;
-  uint32_t* d_count = ctx->z_list + nblk;
+  if ((rc = reserve(ctx, ctx->z_list, size_t(nblk) + 1 + 16))) return rc;
+  uint32_t* d_count = ctx->z_list.data() + nblk;
   OKV_HIP(hipMemsetAsync(d_count, 0, 4, s));
-  hipLaunchKernelGGL(okv_zstd_list_kernel, dim3((nblk + 255) / 256), dim3(256), 0, s, ctx->z_status,
-                     nblk, ctx->z_list, d_count);
+  hipLaunchKernelGGL(okv_zstd_list_kernel, dim3((nblk + 255) / 256), dim3(256), 0, s,
+                     ctx->z_status.data(), nblk, ctx->z_list.data(), d_count);
   uint32_t n = 0;
   OKV_HIP(hipMemcpyAsync(&n, d_count, 4, hipMemcpyDeviceToHost, s));
   OKV_HIP(hipStreamSynchronize(s));
   ctx->z_retried = n;
   if (n == 0) return OKV_OK;
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_need), &ctx->z_cap_need,
-                 (size_t(n) * 2 + 2) * 8)))
-    return rc;
-  uint64_t* need = ctx->z_need;
-  uint64_t* roff = ctx->z_need + n;
+  if ((rc = reserve(ctx, ctx->z_need, size_t(n) * 2 + 2))) return rc;
+  uint64_t* need = ctx->z_need.data();
+  uint64_t* roff = ctx->z_need.data() + n;
   const uint32_t grid = std::min<uint32_t>(n, 2048);
   // the literal scratch is sized for the first pass's grid (>= this one)
   hipLaunchKernelGGL(okv_zstd_kernel, dim3(grid), dim3(64), 0, s, seg, seg_bytes, descs, nblk,
-                     ctx->z_cap_off, ctx->z_dec, ctx->z_dec_len, ctx->z_status, ctx->z_lit, nullptr,
-                     nullptr, ZRetry{ctx->z_list, n, 1, nullptr, need, nullptr});
+                     ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
+                     ctx->z_status.data(), ctx->z_lit.data(), nullptr, nullptr,
+                     ZRetry{ctx->z_list.data(), n, 1, nullptr, need, nullptr});
   const uint64_t base = (*total_io + 15) & ~uint64_t(15);
   hipLaunchKernelGGL(okv_zstd_roff_kernel, dim3(1), dim3(1024), 0, s, need, n, base, roff);
   OKV_HIP(hipGetLastError());
   uint64_t end = 0;
   OKV_HIP(hipMemcpyAsync(&end, roff + n, 8, hipMemcpyDeviceToHost, s));
   OKV_HIP(hipStreamSynchronize(s));
-  if (end + 64 > ctx->z_cap_dec) {  // grow the scratch, keeping the first pass's bytes
-    uint8_t* nd = nullptr;
-    const size_t c = (size_t(end) + 64 + 4095) & ~size_t(4095);
-    OKV_HIP(hipMalloc(&nd, c));
-    OKV_HIP(hipMemcpyAsync(nd, ctx->z_dec, *total_io, hipMemcpyDeviceToDevice, s));
-    OKV_HIP(hipStreamSynchronize(s));
-    (void)hipFree(ctx->z_dec);
-    ctx->z_dec = nd;
-    ctx->z_cap_dec = c;
-  }
+  // grow the scratch, keeping the first pass's bytes
+  if (const hipError_t e = ctx->z_dec.reserve_keep(s, size_t(end) + 64, *total_io))
+    return set_err(ctx, OKV_E_HIP, "zstd scratch allocation", e);
   hipLaunchKernelGGL(okv_zstd_kernel, dim3(grid), dim3(64), 0, s, seg, seg_bytes, descs, nblk,
-                     ctx->z_cap_off, ctx->z_dec, ctx->z_dec_len, ctx->z_status, ctx->z_lit, nullptr,
-                     nullptr, ZRetry{ctx->z_list, n, 0, roff, nullptr, ctx->z_cap_off});
+                     ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
+                     ctx->z_status.data(), ctx->z_lit.data(), nullptr, nullptr,
+                     ZRetry{ctx->z_list.data(), n, 0, roff, nullptr, ctx->z_cap_off.data()});
   OKV_HIP(hipGetLastError());
   *total_io = end;
   return OKV_OK;
@@ -2912,44 +2903,35 @@ int zstd_run(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* d
     for (auto& e : ev) (void)hipEventCreate(&e);
   if (prof) (void)hipEventRecord(ev[0], s);
   zst::ZBlk* zb = nullptr;
-  static unsigned long long* eprof_buf = nullptr;
-  unsigned long long* eprof = nullptr;
+  unsigned long long *eprof = nullptr, *pprof = nullptr;  // phase cycles (diagnostics)
   if (prof) {
-    if (!eprof_buf) (void)hipMalloc(&eprof_buf, 16 * 8 * kExecGridMax);
-    eprof = eprof_buf;
+    if ((rc = reserve(ctx, ctx->z_eprof, 16 * kExecGridMax)) ||
+        (rc = reserve(ctx, ctx->z_pprof, 16)))
+      return rc;
+    eprof = ctx->z_eprof.data();
+    pprof = ctx->z_pprof.data();
     (void)hipMemsetAsync(eprof, 0, 16 * 8 * kExecGridMax, s);
-  }
-  static unsigned long long* pprof_buf = nullptr;  // prologue phase cycles (diagnostics)
-  unsigned long long* pprof = nullptr;
-  if (prof) {
-    if (!pprof_buf) (void)hipMalloc(&pprof_buf, 16 * 8);
-    pprof = pprof_buf;
     (void)hipMemsetAsync(pprof, 0, 16 * 8, s);
   }
   if (!general) {
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_zb), &ctx->z_cap_zb,
-                   size_t(nblk) * sizeof(zst::ZBlk))))
+    if ((rc = reserve(ctx, ctx->z_zb, size_t(nblk) * sizeof(zst::ZBlk))) ||
+        (rc = reserve(ctx, ctx->z_tabs, size_t(nblk) * (zst::kTabEnt + zst::kHufSlot) + 8)) ||
+        (rc = reserve(ctx, ctx->z_blit, total + 64)) ||
+        (rc = reserve(ctx, ctx->z_seq_off, size_t(nblk) + 1)))
       return rc;
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_tabs), &ctx->z_cap_tabs,
-                   size_t(nblk) * (zst::kTabEnt + zst::kHufSlot) * 2 + 16)))
-      return rc;
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_blit), &ctx->z_cap_blit, total + 64)))
-      return rc;
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_seq_off), &ctx->z_cap_seq_off,
-                   (size_t(nblk) + 1) * 8)))
-      return rc;
-    zb = reinterpret_cast<zst::ZBlk*>(ctx->z_zb);
-    uint16_t* htab = reinterpret_cast<uint16_t*>(ctx->z_tabs) + size_t(nblk) * zst::kTabEnt;
+    zb = reinterpret_cast<zst::ZBlk*>(ctx->z_zb.data());
+    uint16_t* htab = ctx->z_tabs.data() + size_t(nblk) * zst::kTabEnt;
     // one workgroup per block (no per-workgroup scratch; OKV_ZSTD_PRO_GRID: A/B)
     const uint32_t pgrid = okv::knob("OKV_ZSTD_PRO_GRID") ? uint32_t(atoi(okv::knob("OKV_ZSTD_PRO_GRID")))
                                                        : nblk;
-    hipLaunchKernelGGL(okv_zstd_pro_kernel, dim3(std::max(1u, std::min(nblk, pgrid))), dim3(64), 0, s,
-                       seg, seg_bytes, descs, nblk, ctx->z_cap_off, ctx->z_dec, ctx->z_dec_len,
-                       ctx->z_status, ctx->z_blit, reinterpret_cast<uint16_t*>(ctx->z_tabs), htab, zb,
-                       ctx->z_seq_off, pprof);
-    hipLaunchKernelGGL(okv_zstd_seqoff_kernel, dim3(1), dim3(1024), 0, s, nblk, ctx->z_seq_off);
+    hipLaunchKernelGGL(okv_zstd_pro_kernel, dim3(std::max(1u, std::min(nblk, pgrid))), dim3(64), 0,
+                       s, seg, seg_bytes, descs, nblk, ctx->z_cap_off.data(), ctx->z_dec.data(),
+                       ctx->z_dec_len.data(), ctx->z_status.data(), ctx->z_blit.data(),
+                       ctx->z_tabs.data(), htab, zb, ctx->z_seq_off.data(), pprof);
+    hipLaunchKernelGGL(okv_zstd_seqoff_kernel, dim3(1), dim3(1024), 0, s, nblk,
+                       ctx->z_seq_off.data());
     uint64_t nseq_total = 0;
-    OKV_HIP(hipMemcpyAsync(&nseq_total, ctx->z_seq_off + nblk, 8, hipMemcpyDeviceToHost, s));
+    OKV_HIP(hipMemcpyAsync(&nseq_total, ctx->z_seq_off.data() + nblk, 8, hipMemcpyDeviceToHost, s));
     if (!ctx->z_ev) OKV_HIP(hipEventCreateWithFlags(&ctx->z_ev, hipEventDisableTiming));
     OKV_HIP(hipEventRecord(ctx->z_ev, s));
     // the literal streams decode while the host reads the sequence count
@@ -2958,24 +2940,23 @@ int zstd_run(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* d
                                                         : kHufBlocks;
     if (hb == 16)
       hipLaunchKernelGGL(okv_zstd_huf_kernel<16>, dim3((nblk + 15) / 16), dim3(64), 0, s, zb, nblk,
-                         htab, seg, ctx->z_blit, ctx->z_cap_off);
+                         htab, seg, ctx->z_blit.data(), ctx->z_cap_off.data());
     else if (hb == 8)
       hipLaunchKernelGGL(okv_zstd_huf_kernel<8>, dim3((nblk + 7) / 8), dim3(64), 0, s, zb, nblk,
-                         htab, seg, ctx->z_blit, ctx->z_cap_off);
+                         htab, seg, ctx->z_blit.data(), ctx->z_cap_off.data());
     else if (hb == 2)
       hipLaunchKernelGGL(okv_zstd_huf_kernel<2>, dim3((nblk + 1) / 2), dim3(64), 0, s, zb, nblk,
-                         htab, seg, ctx->z_blit, ctx->z_cap_off);
+                         htab, seg, ctx->z_blit.data(), ctx->z_cap_off.data());
     else
 #endif
     hipLaunchKernelGGL(okv_zstd_huf_kernel<kHufBlocks>, dim3((nblk + kHufBlocks - 1) / kHufBlocks),
-                       dim3(64), 0, s, zb, nblk, htab, seg, ctx->z_blit, ctx->z_cap_off);
+                       dim3(64), 0, s, zb, nblk, htab, seg, ctx->z_blit.data(),
+                       ctx->z_cap_off.data());
     OKV_HIP(hipEventSynchronize(ctx->z_ev));
     if (prof) (void)hipEventRecord(ev[1], s);
-    if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_seqs), &ctx->z_cap_seqs,
-                   nseq_total * 8 + 64)))
-      return rc;
+    if ((rc = reserve(ctx, ctx->z_seqs, nseq_total + 8))) return rc;
     hipLaunchKernelGGL(okv_zstd_seq_kernel, dim3((nblk + 63) / 64), dim3(64), 0, s, zb, nblk,
-                       reinterpret_cast<const uint16_t*>(ctx->z_tabs), ctx->z_seq_off, ctx->z_seqs);
+                       ctx->z_tabs.data(), ctx->z_seq_off.data(), ctx->z_seqs.data());
     if (prof) (void)hipEventRecord(ev[2], s);
     // one workgroup per block by default: the dispatcher balances blocks of
     // unequal work better than a grid-stride loop (16 384 x 64 KiB: 3.8 ms vs
@@ -2988,18 +2969,17 @@ int zstd_run(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* d
 #define OKV_ZSTD_EXEC_PAD 0  // (18 / 16 / 11 per CU: slower, zstd_seq_chain_ab.log)
 #endif
     hipLaunchKernelGGL(okv_zstd_exec_kernel, dim3(std::min<uint32_t>(nblk, egrid)), dim3(64),
-                       OKV_ZSTD_EXEC_PAD, s,
-                       zb, nblk, ctx->z_seq_off, ctx->z_seqs, ctx->z_cap_off, ctx->z_dec,
-                       ctx->z_dec_len, ctx->z_status, eprof);
+                       OKV_ZSTD_EXEC_PAD, s, zb, nblk, ctx->z_seq_off.data(), ctx->z_seqs.data(),
+                       ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
+                       ctx->z_status.data(), eprof);
   }
   if (prof) (void)hipEventRecord(ev[3], s);
   const uint32_t grid = std::min<uint32_t>(nblk, 2048);
-  if ((rc = grow(ctx, reinterpret_cast<void**>(&ctx->z_lit), &ctx->z_cap_lit,
-                 size_t(grid) * kZstdLitBytes)))
-    return rc;
+  if ((rc = reserve(ctx, ctx->z_lit, size_t(grid) * kZstdLitBytes))) return rc;
   hipLaunchKernelGGL(okv_zstd_kernel, dim3(grid), dim3(64), 0, s, seg, seg_bytes, descs, nblk,
-                     ctx->z_cap_off, ctx->z_dec, ctx->z_dec_len, ctx->z_status, ctx->z_lit,
-                     nullptr, zb, ZRetry{nullptr, 0, 0, nullptr, nullptr, nullptr});
+                     ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
+                     ctx->z_status.data(), ctx->z_lit.data(), nullptr, zb,
+                     ZRetry{nullptr, 0, 0, nullptr, nullptr, nullptr});
   OKV_HIP(hipGetLastError());
   if ((rc = zstd_regrow(ctx, seg, seg_bytes, descs, nblk, total_io))) return rc;
   if (prof) {

@@ -727,3 +727,48 @@ def test_dispatcher_routes(decoder, nofused_decoder):
     finally:
         a.close()
         b.close()
+
+
+@pytest.mark.parametrize("flags", [_lib.OPEN_NO_POINT, _lib.OPEN_NO_POINT | _lib.OPEN_NO_FUSED],
+                         ids=["fused", "no_fused"])
+def test_scratch_grows_and_is_reused(flags):
+    """One context walked through grow and reuse of its scratch buffers
+    (okv::Buf): host-mode batches of 8, 300 and 8 blocks of 4 KiB, then 8, 64
+    and 8 (all under the fused limit: the look-back words), then 8, 300 and 8
+    with the segment buffer padded so that the blocks average over 16 KiB (the
+    tile pass and its record key lengths).  Every decode equals the oracle and
+    ran the intended route."""
+    nofused = bool(flags & _lib.OPEN_NO_FUSED)
+    batches = {n: _mixed_segment(["s"] * n, 900 + n) for n in (8, 64, 300)}
+    refs = {}
+    FUSED, GATHER, TILE = _lib.PATH_FUSED, _lib.PATH_BIG | _lib.PATH_SMALL, \
+        _lib.PATH_BIG | _lib.PATH_TILE
+    dec = okv.Decoder(0, flags=flags)
+    try:
+        for large, walk in ((False, (8, 300, 8)), (False, (8, 64, 8)), (True, (8, 300, 8))):
+            for n in walk:
+                seg, d = batches[n]
+                if large:
+                    seg = seg + bytes(16385 * n - len(seg) + 4096)
+                got = dec.decode(seg, d)
+                lp = dec.last_path()
+                print(f"scratch walk nofused={nofused} large={large} blocks={n}: last_path={lp}")
+                if large:
+                    assert lp == TILE, (n, lp)
+                elif nofused:
+                    assert lp == GATHER, (n, lp)
+                elif n <= 64:
+                    assert lp == FUSED, (n, lp)
+                else:  # fused up to the context's resident-capacity bound, else the gather
+                    assert lp in (FUSED, GATHER), (n, lp)
+                if (n, large) not in refs:
+                    refs[n, large] = _assert_same_as_oracle(got, seg, d, 0, False)
+                    continue
+                ref = refs[n, large]
+                assert np.array_equal(got.status, ref["status"])
+                for k in SOA + ("key_base", "val_base"):
+                    assert np.array_equal(getattr(got, k), ref[k]), (n, k)
+                assert got.key_arena.tobytes() == ref["key_arena"].tobytes()
+                assert got.val_arena.tobytes() == ref["val_arena"].tobytes()
+    finally:
+        dec.close()

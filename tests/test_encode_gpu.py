@@ -410,3 +410,48 @@ def test_tile_cut_boundaries_and_general_path(enc, T):
     if rc == 0:
         assert got.seg.tobytes() == want
         assert got.meta() == meta
+
+
+def _sized_rows(seed, n, vmax):
+    """n rows of 8-byte keys and 0..vmax-byte values, built from one random buffer."""
+    rng = np.random.default_rng(seed)
+    vl = rng.integers(0, vmax + 1, n)
+    buf = rng.integers(0, 256, int(vl.sum()) + 1, dtype=np.uint8).tobytes()
+    off = np.concatenate([[0], np.cumsum(vl)])
+    return [(b"%08d" % i, buf[off[i]:off[i + 1]]) for i in range(n)]
+
+
+def test_scratch_grows_and_is_reused():
+    """One context walked through grow and reuse of the encode scratch
+    (okv::Buf): 1 000 rows, 200 000 rows, 1 000 rows with host pointers, a
+    call whose blocks hold ~1 300 rows (past the tile cut's 256-row lookahead:
+    tot->far, the general plan and its per-row and jump tables), then 1 000,
+    200 000 and 1 000 rows with device pointers.  Every segment is byte-equal
+    to the oracle writer's."""
+    cases = {"small": (_sized_rows(1, 1000, 120), 3584),
+             "large": (_sized_rows(2, 200_000, 120), 3584),
+             "far": (_sized_rows(3, 20_000, 8), 20000)}
+    want = {}
+    for name, (rows, T) in cases.items():
+        rc, seg, meta = oracle_segment(rows, T, 4096)
+        assert rc == 0, name
+        want[name] = (seg, meta)
+    e = okv.Encoder(0)
+    try:
+        for name in ("small", "large", "small", "far", "small"):
+            rows, T = cases[name]
+            got = e.encode(rows, T, 4096)
+            assert got.seg.tobytes() == want[name][0], name
+            assert got.meta() == want[name][1], name
+        for name in ("small", "large", "small", "far", "small"):
+            rows, T = cases[name]
+            r = okv.pack_rows(rows)
+            dev = {k: torch.from_numpy(v.copy()).cuda() for k, v in r.items()}
+            for k in ("key_off", "val_off"):
+                dev[k] = dev[k].view(torch.int64)
+            seg_t = torch.zeros(len(want[name][0]) + 4096, dtype=torch.uint8, device="cuda")
+            eo = e.encode_device(dev, len(rows), {"seg": seg_t}, threshold=T, block_size=4096)
+            assert eo.file_bytes == len(want[name][0]), name
+            assert seg_t[:eo.file_bytes].cpu().numpy().tobytes() == want[name][0], name
+    finally:
+        e.close()

@@ -716,6 +716,36 @@ def test_scratch_reuse_after_larger_call():
         dec.close()
 
 
+def _getrange_walk_rows(seed, nsrc, n):
+    """nsrc streams of n rows: 9-digit keys drawn from one range (so the
+    streams share some keys and all end near the range's end), short values."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for s in range(nsrc):
+        ks = np.unique(rng.integers(0, 3 * nsrc * n, size=n + n // 4 + 8))[:n]
+        assert ks.size == n
+        out.append([(b"%09d" % k, b"v%d" % s) for k in ks.tolist()])
+    return out
+
+
+def test_getrange_scratch_grows_and_is_reused():
+    """One context walked through grow and reuse of the merge scratch
+    (okv::Buf): a GETRANGE of 2 streams x 100 rows, then 8 streams x 20 000
+    rows (40 scan blocks of 4096: every per-row array, the block sums and the
+    rank windows grow), then the first again over the buffers the larger call
+    left full -- each equal to the Go loop's rows."""
+    small = [stream_of_rows(rs, level=1) for rs in _getrange_walk_rows(61, 2, 100)]
+    large = [stream_of_rows(rs, level=1) for rs in _getrange_walk_rows(62, 8, 20_000)]
+    assert (sum(s.hi - s.lo for s in large) + 1 + 4095) // 4096 > 1
+    dec = okv.Decoder(0)
+    try:
+        for streams in (small, large, small):
+            end = check_getrange(dec, streams, ASC, b"\xff", 1 << 63, soa=True)
+            assert end == SO.END_STALE
+    finally:
+        dec.close()
+
+
 def _raw_call(dec, streams, nsrc=None, flags=L.F_DEVICE_PTRS, mode=GETRANGE, direction=ASC,
               limit=1, bound=b"k", bound_len=None, ranges=None):
     nsrc = len(streams) if nsrc is None else nsrc

@@ -109,3 +109,34 @@ def test_ablation_build_carries_the_alternatives():
         assert name in data, name
     for knob in (b"OKV_VALUE_SWEEP", b"OKV_TILE", b"OKV_ZSTD_PROF"):
         assert knob in data, knob
+
+
+def _strip_comments(src):
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def test_allocation_calls_are_confined():
+    """Every device and pinned allocation is an okv::Buf (okv_buf.hpp): outside
+    comments, the HIP allocation calls appear in that header and in the four
+    public allocators of okv_decode.hip, nowhere else under csrc/."""
+    csrc = os.path.join(ROOT, "objectkv_amd", "csrc")
+    calls = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\s*\(")
+    public = ("okv_device_alloc", "okv_device_free", "okv_host_alloc", "okv_host_free")
+    seen_public = set()
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if name == "okv_buf.hpp" or not os.path.isfile(path):
+            continue
+        src = _strip_comments(open(path, errors="replace").read())
+        if name == "okv_decode.hip":
+            for fn in public:  # cut the allocator's definition out: signature to closing brace
+                m = re.search(r"\n[^\n;{}]*\b" + fn + r"\s*\([^)]*\)\s*\{.*?\n\}", src, flags=re.S)
+                assert m, fn
+                assert calls.search(m.group(0)), fn
+                seen_public.add(fn)
+                src = src[:m.start()] + src[m.end():]
+        found = calls.findall(src)
+        assert not found, (name, found)
+    assert seen_public == set(public)
+    assert calls.search(_strip_comments(open(os.path.join(csrc, "okv_buf.hpp")).read()))

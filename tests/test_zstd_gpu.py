@@ -217,3 +217,33 @@ def test_zstd_past_original_size(zdec, case):
     got = _check(zdec, seg, descs)
     assert [int(x) for x in got.status] == want, name
     assert bool(zdec.last_path() & okv._lib.PATH_ZSTD_REGROW) == regrow, name
+
+
+def test_zstd_scratch_grows_and_is_reused():
+    """One context walked through grow and reuse of the zstd scratch
+    (okv::Buf): batches of 8, 300 and 8 blocks of 4 KiB, each equal to the
+    oracle.  Then a fresh context whose first decode is past_original_cases'
+    "mixed": its first block inflates 300 KiB past its first region, so the
+    retry moves the decompressed-block scratch and has to keep the bytes of the
+    blocks already decoded there."""
+    seg, _, _ = ZC.Z.zstd_segment(ZC._rows(51, 7500), 3584, 4096, level=3)
+    descs = [st.desc() for st in P.bytes_to_metadata(ZC._meta_of(seg)).entries]
+    assert len(descs) >= 308
+    dec = okv.Decoder(0)
+    try:
+        for lo, hi in ((300, 308), (0, 300), (300, 308)):
+            got = _check(dec, seg, descs[lo:hi])
+            assert int(got.status.max()) == 0
+            assert dec.last_path() & okv._lib.PATH_ZSTD
+            assert not dec.last_path() & okv._lib.PATH_ZSTD_REGROW
+    finally:
+        dec.close()
+    name, seg, descs, want, regrow = [c for c in ZC.past_original_cases() if c[0] == "mixed"][0]
+    assert regrow
+    dec = okv.Decoder(0)
+    try:
+        got = _check(dec, seg, descs)
+        assert [int(x) for x in got.status] == want
+        assert dec.last_path() & okv._lib.PATH_ZSTD_REGROW
+    finally:
+        dec.close()
