@@ -1,7 +1,11 @@
-// okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip)
-// and encode (okv_encode.hip) translation units.  Internal header.
+// okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip), encode
+// (okv_encode.hip), zstd (okv_zstd.hip) and merge (okv_merge.hip) translation units.
+// Internal header.
 // Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
-// its capacity and frees itself with its owner; kernels get raw pointers from data().
+// its capacity and frees itself with its owner; kernels get raw pointers from data().  The
+// owners are okv_ctx (decode), AblateState (the decode ablation arms) and, each defined in its
+// own file behind a forward declaration here and released by okv_close: EncScratch,
+// zst::Scratch and mrg::Scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #define OKV_BUF_HIP
@@ -25,15 +29,23 @@ void merge_release(okv_ctx* ctx);
 // okv_decode.hip: enqueue XXH64 of each block's BlockSize bytes (device pointers).
 void launch_hash(hipStream_t stream, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
                  uint32_t nblk, uint64_t* out);
-// okv_zstd.hip: zstd block decompression into per-block scratch regions.
-void launch_zstd_cap(hipStream_t s, const Desc* descs, uint32_t nblk, uint64_t* cap_off);
-// total: in, the first regions' total (cap_off[nblk]); out, the scratch bytes
-// in use after the frames that outgrew their regions were decoded again
-int zstd_run(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
-             uint32_t nblk, uint64_t* total);
-void launch_zstd_desc(hipStream_t s, const Desc* descs, uint32_t nblk, const uint64_t* cap_off,
-                      const uint64_t* dec_len, Desc* out);
-constexpr uint32_t kZstdLitBytes = 1u << 17;  // per-wave literal scratch (Block_Maximum_Size)
+// okv_zstd.hip: the zstd stage.  Every block of the batch (device pointers) is decompressed into
+// the stage's own scratch; passes 1-3 then walk `bytes` by `descs` (offset into bytes,
+// BlockSize = decompressed length), with `status` as each block's outcome so far.  The
+// pointers hold until the context's next zstd decode.
+namespace zst {
+struct Scratch;  // okv_zstd.hip
+}
+struct ZstdOut {
+  const uint8_t* bytes;
+  uint64_t n_bytes;
+  const Desc* descs;
+  const int32_t* status;
+  uint32_t retried;  // blocks that outgrew their first region and were decoded again
+};
+int zstd_stage(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
+               uint32_t nblk, ZstdOut* out);
+void zstd_release(okv_ctx* ctx);
 }  // namespace okv
 
 namespace okv {
@@ -131,25 +143,7 @@ struct okv_ctx {
   okv::AblateState ab;             // the ablation build's arms (unused by the product)
   okv::EncScratch* enc = nullptr;  // encode scratch (okv_encode.hip)
   okv::mrg::Scratch* merge = nullptr;  // merge scratch (okv_merge.hip)
-  // zstd decompression scratch (okv_zstd.hip)
-  okv::DevBuf<uint64_t> z_cap_off;   // [nblk + 1] decompressed-region offsets
-  okv::DevBuf<uint64_t> z_dec_len;   // [nblk]
-  okv::DevBuf<int32_t> z_status;     // [nblk]
-  okv::DevBuf<okv::Desc> z_desc;     // [nblk] descriptors of the decompressed blocks
-  okv::DevBuf<uint8_t> z_dec;        // decompressed blocks
-  okv::DevBuf<uint8_t> z_lit;        // per-wave literal scratch (general kernel)
-  okv::DevBuf<uint8_t> z_blit;       // per-block literal scratch (prologue -> executor)
-  okv::DevBuf<uint16_t> z_tabs;      // per-block FSE tables (prologue -> sequence stage), then
-                                     // kHufSlot u16 per block: Huffman tables (prologue -> stream stage)
-  hipEvent_t z_ev = nullptr;         // the sequence count's copy (zstd_run)
-  okv::DevBuf<uint8_t> z_zb;         // per-block zst::ZBlk
-  okv::DevBuf<uint64_t> z_seq_off;   // [nblk + 1] sequence offsets
-  okv::DevBuf<uint64_t> z_seqs;      // packed sequences
-  okv::DevBuf<uint32_t> z_list;      // [nblk] blocks decoded again (+ the count after them)
-  okv::DevBuf<uint64_t> z_need;      // [n] measured outputs, [n + 1] their regions
-  okv::DevBuf<unsigned long long> z_eprof;  // OKV_ZSTD_PROF only: executor phase cycles
-  okv::DevBuf<unsigned long long> z_pprof;  // OKV_ZSTD_PROF only: prologue phase cycles
-  uint32_t z_retried = 0;            // blocks the last zstd decode decoded again
+  okv::zst::Scratch* zstd = nullptr;   // zstd stage scratch (okv_zstd.hip)
 };
 
 namespace okv {

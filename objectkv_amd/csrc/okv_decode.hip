@@ -2320,31 +2320,17 @@ struct Work {
   const Desc* descs;
   int comp;
   const int32_t* pre;
+  uint32_t retried;  // zstd blocks decoded again into a larger region (0: no zstd stage ran)
 };
 
 int prepare(okv_ctx* ctx, const uint8_t* d_seg, uint64_t seg_bytes, const Desc* d_desc,
             uint32_t nblk, int comp, bool index_only, Work* w) {
-  *w = Work{d_seg, seg_bytes, d_desc, comp, nullptr};
-  ctx->z_retried = 0;
+  *w = Work{d_seg, seg_bytes, d_desc, comp, nullptr, 0};
   if (comp != OKV_COMP_ZSTD || index_only || nblk == 0) return OKV_OK;
-  int rc;
-  const size_t n = size_t(nblk) + 1;
-  if ((rc = reserve(ctx, ctx->z_cap_off, n)) || (rc = reserve(ctx, ctx->z_dec_len, n)) ||
-      (rc = reserve(ctx, ctx->z_status, n)) || (rc = reserve(ctx, ctx->z_desc, n)))
-    return rc;
-  launch_zstd_cap(ctx->stream, d_desc, nblk, ctx->z_cap_off.data());
-  uint64_t total = 0;
-  OKV_HIP(hipMemcpyAsync(&total, ctx->z_cap_off.data() + nblk, 8, hipMemcpyDeviceToHost,
-                         ctx->stream));
-  OKV_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = reserve(ctx, ctx->z_dec, total + 64))) return rc;
-  if ((rc = zstd_run(ctx, d_seg, seg_bytes, d_desc, nblk, &total))) return rc;
-  launch_zstd_desc(ctx->stream, d_desc, nblk, ctx->z_cap_off.data(), ctx->z_dec_len.data(),
-                   ctx->z_desc.data());
-  OKV_HIP(hipGetLastError());
-  // offsets <= total < seg_bytes, so no decompressed block reads as EOF
-  *w = Work{ctx->z_dec.data(), total + 16, ctx->z_desc.data(), OKV_COMP_NONE,
-            ctx->z_status.data()};
+  ZstdOut z;
+  const int rc = zstd_stage(ctx, d_seg, seg_bytes, d_desc, nblk, &z);
+  if (rc) return rc;
+  *w = Work{z.bytes, z.n_bytes, z.descs, OKV_COMP_NONE, z.status, z.retried};
   return OKV_OK;
 }
 
@@ -2567,9 +2553,10 @@ int finish_decode(okv_ctx* ctx, okv_decode_out* o, uint32_t flags) {
 }
 
 // okv_last_path of a decode: the compression stage's bits and the kernels'.
-uint32_t path_bits(const okv_ctx* ctx, int comp, bool index_only, uint32_t kernels) {
+// w: the decode's prepared inputs (the zstd stage's retry count).
+uint32_t path_bits(const Work& w, int comp, bool index_only, uint32_t kernels) {
   return (comp ? OKV_PATH_ZSTD : 0u) |
-         (comp == OKV_COMP_ZSTD && !index_only && ctx->z_retried ? OKV_PATH_ZSTD_REGROW : 0u) |
+         (comp == OKV_COMP_ZSTD && !index_only && w.retried ? OKV_PATH_ZSTD_REGROW : 0u) |
          kernels;
 }
 
@@ -2619,7 +2606,7 @@ int decode_device(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const De
   if (tile && (rc = ensure_hdr(ctx, nblk, &rt_kl))) return rc;
   if (route == Route::kFused && (rc = ensure_fused(ctx, nblk))) return rc;
   const CopyParams P = copy_params(ctx, w, nblk, index_only, rt_kl, geo.span_cap, *o);
-  ctx->last_path = path_bits(ctx, comp, index_only, uint32_t(route));
+  ctx->last_path = path_bits(w, comp, index_only, uint32_t(route));
   // passes 1-2.  When they are the count launch, the big-block kernel runs
   // right behind it: before the chained context's pass-3 wait, so with decodes
   // in flight it runs under the other decode's pass 3 (the list is empty on
@@ -3036,12 +3023,12 @@ void okv_close(okv_ctx* ctx) {
     auto& v = ctx->chain->chained_by;
     v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
   }
-  for (hipEvent_t e : {ctx->p3_done, ctx->z_ev})
-    if (e) (void)hipEventDestroy(e);
+  if (ctx->p3_done) (void)hipEventDestroy(ctx->p3_done);
 #ifdef OKV_ABLATE
   ablate_close(ctx);  // the arms' second stream and events
 #endif
   okv::enc_release(ctx);
+  okv::zstd_release(ctx);
   okv::merge_release(ctx);
   const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;
   delete ctx;  // every scratch buffer releases itself

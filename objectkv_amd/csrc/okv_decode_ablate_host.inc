@@ -320,7 +320,7 @@ int ablate_decode(okv_ctx* ctx, const Work& w, uint32_t nblk, int comp, okv_deco
                           : gt == 256 && A.gather_staged && !index_only ? OKV_PATH_STAGED
                           : gt == 64 && A.gather_staged                 ? OKV_PATH_SMALL
                                                                         : OKV_PATH_GATHER;
-  ctx->last_path = path_bits(ctx, comp, index_only,
+  ctx->last_path = path_bits(w, comp, index_only,
                              !nblk    ? 0u
                              : fused  ? OKV_PATH_FUSED
                              : stream ? OKV_PATH_STREAM

@@ -2338,9 +2338,6 @@ constexpr int kGQ = OKV_ZSTD_GQ;  // gather: output dwords per lane per step (2 
 constexpr int kGB = OKV_ZSTD_GB;  // source resolution: 64-byte groups per batch
 static_assert(kExecOut <= zst::kChunkOut && kExecOut % 1024 == 0 && (kExecOut & (kExecOut - 1)) == 0,
               "exec chunk");
-// Executor grid (blocks are strided over it); the profiling slots are sized
-// for the largest grid.
-constexpr uint32_t kExecGridMax = 16384;
 // Registers capped for 5 waves per SIMD (with one output dword per lane and
 // 4-group batches: 96 registers + 52 B of spills, executor 2.35-2.38 vs
 // 2.43-2.51 ms for 2 dwords / 8 groups uncapped, profiles/r3/r3z).  A build
@@ -2352,6 +2349,9 @@ constexpr uint32_t kExecGridMax = 16384;
 #define OKV_ZSTD_EXEC_ATTR __attribute__((amdgpu_waves_per_eu(OKV_ZSTD_EXEC_WPE)))
 #else
 #define OKV_ZSTD_EXEC_ATTR
+#endif
+#ifndef OKV_ZSTD_EXEC_PAD  // A/B builds: dynamic LDS per workgroup to lower the executor's occupancy
+#define OKV_ZSTD_EXEC_PAD 0  // (18 / 16 / 11 per CU: slower, zstd_seq_chain_ab.log)
 #endif
 __global__ __launch_bounds__(64) OKV_ZSTD_EXEC_ATTR void okv_zstd_exec_kernel(
     const zst::ZBlk* __restrict__ zb, uint32_t nblk, const uint64_t* __restrict__ seq_off,
@@ -2837,6 +2837,72 @@ __global__ void okv_zstd_desc_kernel(const Desc* __restrict__ descs, uint32_t nb
   out[b] = d;
 }
 
+// ---- host side ----------------------------------------------------------------
+
+// The Huffman stream stage, kHB blocks per wave.
+template <uint32_t kHB>
+void launch_huf(hipStream_t s, zst::ZBlk* zb, uint32_t nblk, const uint16_t* htab,
+                const uint8_t* seg, uint8_t* blit, const uint64_t* cap_off) {
+  hipLaunchKernelGGL(okv_zstd_huf_kernel<kHB>, dim3((nblk + kHB - 1) / kHB), dim3(64), 0, s, zb,
+                     nblk, htab, seg, blit, cap_off);
+}
+
+namespace zst {
+// What one run of the stages (zstd_run) may vary.  The product fills in its
+// constants; the ablation build's diag_begin may overwrite them.
+struct Plan {
+  bool general;        // every block by the general kernel (OKV_OPEN_ZSTD_ONE_PASS)
+  // prologue and executor workgroups: one per block, no per-workgroup scratch;
+  // the dispatcher balances blocks of unequal work better than a grid-stride
+  // loop (16 384 x 64 KiB: 3.8 ms vs 4.6 ms at 4096 workgroups, 5.6 at 2816)
+  uint32_t pro_grid, exec_grid;
+  decltype(&launch_huf<kHufBlocks>) huf;  // the stream stage's launch
+  unsigned long long *pprof, *eprof;      // prologue / executor phase counters (product: null)
+};
+
+// The ablation build's hooks into zstd_run: its knobs, phase counters and
+// reports (okv_zstd_ablate_host.inc).  diag_begin is entered before the first
+// launch, diag_mark(k) after stage k's launches, 4 being the last.
+#ifdef OKV_ABLATE
+#include "okv_zstd_ablate_host.inc"
+#else
+struct Diag {};
+inline int diag_begin(okv_ctx*, Diag&, uint32_t, Plan*) { return OKV_OK; }
+inline void diag_mark(okv_ctx*, Diag&, int) {}
+#endif
+
+// The stage's scratch: one per context, made by its first zstd decode
+// (zstd_stage), released by okv_close (zstd_release).
+struct Scratch {
+  DevBuf<uint64_t> cap_off;  // [nblk + 1] decompressed-region offsets
+  DevBuf<uint64_t> dec_len;  // [nblk]
+  DevBuf<int32_t> status;    // [nblk]
+  DevBuf<Desc> desc;         // [nblk] descriptors of the decompressed blocks
+  DevBuf<uint8_t> dec;       // decompressed blocks
+  DevBuf<uint8_t> lit;       // per-wave literal scratch (general kernel)
+  DevBuf<uint8_t> blit;      // per-block literal scratch (prologue -> executor)
+  DevBuf<uint16_t> tabs;     // per-block FSE tables (prologue -> sequence stage), then
+                             // kHufSlot u16 per block: Huffman tables (prologue -> stream stage)
+  hipEvent_t ev = nullptr;   // the sequence count's copy (zstd_run)
+  DevBuf<uint8_t> zb;        // per-block ZBlk
+  DevBuf<uint64_t> seq_off;  // [nblk + 1] sequence offsets
+  DevBuf<uint64_t> seqs;     // packed sequences
+  DevBuf<uint32_t> list;     // [nblk] blocks decoded again (+ the count after them)
+  DevBuf<uint64_t> need;     // [n] measured outputs, [n + 1] their regions
+  uint32_t retried = 0;      // blocks the last run decoded again (zstd_regrow)
+  Diag diag;                 // the ablation build's state (empty in the product)
+};
+constexpr uint32_t kLitBytes = 1u << 17;  // per-wave literal scratch (Block_Maximum_Size)
+}  // namespace zst
+
+void zstd_release(okv_ctx* ctx) {
+  zst::Scratch* z = ctx->zstd;
+  if (!z) return;
+  if (z->ev) (void)hipEventDestroy(z->ev);
+  delete z;  // the buffers release themselves
+  ctx->zstd = nullptr;
+}
+
 // Frames that decompress past their first region (first_region): the general
 // kernel measures each one's whole output (a pass that reads and writes no
 // byte), then decodes it into a region of that size appended to the scratch
@@ -2845,29 +2911,29 @@ __global__ void okv_zstd_desc_kernel(const Desc* __restrict__ descs, uint32_t nb
 // these blocks decode and walk like any other; no OKV_BLK_CAPACITY status
 // leaves the zstd stage.  One extra host round trip per zstd decode (the
 // retry count); Go-written blocks never need the retry.
-int zstd_regrow(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
-                uint32_t nblk, uint64_t* total_io) {
+int zstd_regrow(okv_ctx* ctx, zst::Scratch* z, const uint8_t* seg, uint64_t seg_bytes,
+                const Desc* descs, uint32_t nblk, uint64_t* total_io) {
   hipStream_t s = ctx->stream;
   int rc;
-  if ((rc = reserve(ctx, ctx->z_list, size_t(nblk) + 1 + 16))) return rc;
-  uint32_t* d_count = ctx->z_list.data() + nblk;
+  if ((rc = reserve(ctx, z->list, size_t(nblk) + 1 + 16))) return rc;
+  uint32_t* d_count = z->list.data() + nblk;
   OKV_HIP(hipMemsetAsync(d_count, 0, 4, s));
   hipLaunchKernelGGL(okv_zstd_list_kernel, dim3((nblk + 255) / 256), dim3(256), 0, s,
-                     ctx->z_status.data(), nblk, ctx->z_list.data(), d_count);
+                     z->status.data(), nblk, z->list.data(), d_count);
   uint32_t n = 0;
   OKV_HIP(hipMemcpyAsync(&n, d_count, 4, hipMemcpyDeviceToHost, s));
   OKV_HIP(hipStreamSynchronize(s));
-  ctx->z_retried = n;
+  z->retried = n;
   if (n == 0) return OKV_OK;
-  if ((rc = reserve(ctx, ctx->z_need, size_t(n) * 2 + 2))) return rc;
-  uint64_t* need = ctx->z_need.data();
-  uint64_t* roff = ctx->z_need.data() + n;
+  if ((rc = reserve(ctx, z->need, size_t(n) * 2 + 2))) return rc;
+  uint64_t* need = z->need.data();
+  uint64_t* roff = z->need.data() + n;
   const uint32_t grid = std::min<uint32_t>(n, 2048);
   // the literal scratch is sized for the first pass's grid (>= this one)
   hipLaunchKernelGGL(okv_zstd_kernel, dim3(grid), dim3(64), 0, s, seg, seg_bytes, descs, nblk,
-                     ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
-                     ctx->z_status.data(), ctx->z_lit.data(), nullptr, nullptr,
-                     ZRetry{ctx->z_list.data(), n, 1, nullptr, need, nullptr});
+                     z->cap_off.data(), z->dec.data(), z->dec_len.data(),
+                     z->status.data(), z->lit.data(), nullptr, nullptr,
+                     ZRetry{z->list.data(), n, 1, nullptr, need, nullptr});
   const uint64_t base = (*total_io + 15) & ~uint64_t(15);
   hipLaunchKernelGGL(okv_zstd_roff_kernel, dim3(1), dim3(1024), 0, s, need, n, base, roff);
   OKV_HIP(hipGetLastError());
@@ -2875,151 +2941,99 @@ int zstd_regrow(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc
   OKV_HIP(hipMemcpyAsync(&end, roff + n, 8, hipMemcpyDeviceToHost, s));
   OKV_HIP(hipStreamSynchronize(s));
   // grow the scratch, keeping the first pass's bytes
-  if (const hipError_t e = ctx->z_dec.reserve_keep(s, size_t(end) + 64, *total_io))
+  if (const hipError_t e = z->dec.reserve_keep(s, size_t(end) + 64, *total_io))
     return set_err(ctx, OKV_E_HIP, "zstd scratch allocation", e);
   hipLaunchKernelGGL(okv_zstd_kernel, dim3(grid), dim3(64), 0, s, seg, seg_bytes, descs, nblk,
-                     ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
-                     ctx->z_status.data(), ctx->z_lit.data(), nullptr, nullptr,
-                     ZRetry{ctx->z_list.data(), n, 0, roff, nullptr, ctx->z_cap_off.data()});
+                     z->cap_off.data(), z->dec.data(), z->dec_len.data(),
+                     z->status.data(), z->lit.data(), nullptr, nullptr,
+                     ZRetry{z->list.data(), n, 0, roff, nullptr, z->cap_off.data()});
   OKV_HIP(hipGetLastError());
   *total_io = end;
   return OKV_OK;
 }
 
 // Decompress every block into dec + cap_off[b] (capacities already scanned;
-// total = cap_off[nblk]).  Stages: prologue -> sequence offsets -> sequences ->
-// executor -> general kernel for the blocks the prologue handed over.
-// OKV_ZSTD_GENERAL=1 sends every block through the general kernel (A/B);
-// OKV_ZSTD_PROF=1 prints per-stage milliseconds to stderr (diagnostics only).
-int zstd_run(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
-             uint32_t nblk, uint64_t* total_io) {
+// total = cap_off[nblk]; out, the scratch bytes in use after the regrow).
+// Stages: prologue -> sequence offsets, whose total the host reads while the
+// Huffman streams decode -> sequences -> executor -> general kernel for the
+// blocks the prologue handed over (every block in a one-pass context) ->
+// regrow.
+int zstd_run(okv_ctx* ctx, zst::Scratch* z, const uint8_t* seg, uint64_t seg_bytes,
+             const Desc* descs, uint32_t nblk, uint64_t* total_io) {
   hipStream_t s = ctx->stream;
   int rc;
   const uint64_t total = *total_io;
-  const bool general = ctx->zstd_one_pass || okv::knob("OKV_ZSTD_GENERAL") != nullptr;
-  const bool prof = okv::knob("OKV_ZSTD_PROF") != nullptr;
-  hipEvent_t ev[6] = {};
-  if (prof)
-    for (auto& e : ev) (void)hipEventCreate(&e);
-  if (prof) (void)hipEventRecord(ev[0], s);
+  zst::Plan plan{ctx->zstd_one_pass, nblk, nblk, launch_huf<kHufBlocks>, nullptr, nullptr};
+  if ((rc = zst::diag_begin(ctx, z->diag, nblk, &plan))) return rc;
   zst::ZBlk* zb = nullptr;
-  unsigned long long *eprof = nullptr, *pprof = nullptr;  // phase cycles (diagnostics)
-  if (prof) {
-    if ((rc = reserve(ctx, ctx->z_eprof, 16 * kExecGridMax)) ||
-        (rc = reserve(ctx, ctx->z_pprof, 16)))
+  if (!plan.general) {
+    if ((rc = reserve(ctx, z->zb, size_t(nblk) * sizeof(zst::ZBlk))) ||
+        (rc = reserve(ctx, z->tabs, size_t(nblk) * (zst::kTabEnt + zst::kHufSlot) + 8)) ||
+        (rc = reserve(ctx, z->blit, total + 64)) ||
+        (rc = reserve(ctx, z->seq_off, size_t(nblk) + 1)))
       return rc;
-    eprof = ctx->z_eprof.data();
-    pprof = ctx->z_pprof.data();
-    (void)hipMemsetAsync(eprof, 0, 16 * 8 * kExecGridMax, s);
-    (void)hipMemsetAsync(pprof, 0, 16 * 8, s);
-  }
-  if (!general) {
-    if ((rc = reserve(ctx, ctx->z_zb, size_t(nblk) * sizeof(zst::ZBlk))) ||
-        (rc = reserve(ctx, ctx->z_tabs, size_t(nblk) * (zst::kTabEnt + zst::kHufSlot) + 8)) ||
-        (rc = reserve(ctx, ctx->z_blit, total + 64)) ||
-        (rc = reserve(ctx, ctx->z_seq_off, size_t(nblk) + 1)))
-      return rc;
-    zb = reinterpret_cast<zst::ZBlk*>(ctx->z_zb.data());
-    uint16_t* htab = ctx->z_tabs.data() + size_t(nblk) * zst::kTabEnt;
-    // one workgroup per block (no per-workgroup scratch; OKV_ZSTD_PRO_GRID: A/B)
-    const uint32_t pgrid = okv::knob("OKV_ZSTD_PRO_GRID") ? uint32_t(atoi(okv::knob("OKV_ZSTD_PRO_GRID")))
-                                                       : nblk;
-    hipLaunchKernelGGL(okv_zstd_pro_kernel, dim3(std::max(1u, std::min(nblk, pgrid))), dim3(64), 0,
-                       s, seg, seg_bytes, descs, nblk, ctx->z_cap_off.data(), ctx->z_dec.data(),
-                       ctx->z_dec_len.data(), ctx->z_status.data(), ctx->z_blit.data(),
-                       ctx->z_tabs.data(), htab, zb, ctx->z_seq_off.data(), pprof);
+    zb = reinterpret_cast<zst::ZBlk*>(z->zb.data());
+    uint16_t* htab = z->tabs.data() + size_t(nblk) * zst::kTabEnt;
+    hipLaunchKernelGGL(okv_zstd_pro_kernel, dim3(plan.pro_grid), dim3(64), 0, s, seg, seg_bytes,
+                       descs, nblk, z->cap_off.data(), z->dec.data(), z->dec_len.data(),
+                       z->status.data(), z->blit.data(), z->tabs.data(), htab, zb,
+                       z->seq_off.data(), plan.pprof);
     hipLaunchKernelGGL(okv_zstd_seqoff_kernel, dim3(1), dim3(1024), 0, s, nblk,
-                       ctx->z_seq_off.data());
+                       z->seq_off.data());
     uint64_t nseq_total = 0;
-    OKV_HIP(hipMemcpyAsync(&nseq_total, ctx->z_seq_off.data() + nblk, 8, hipMemcpyDeviceToHost, s));
-    if (!ctx->z_ev) OKV_HIP(hipEventCreateWithFlags(&ctx->z_ev, hipEventDisableTiming));
-    OKV_HIP(hipEventRecord(ctx->z_ev, s));
+    OKV_HIP(hipMemcpyAsync(&nseq_total, z->seq_off.data() + nblk, 8, hipMemcpyDeviceToHost, s));
+    if (!z->ev) OKV_HIP(hipEventCreateWithFlags(&z->ev, hipEventDisableTiming));
+    OKV_HIP(hipEventRecord(z->ev, s));
     // the literal streams decode while the host reads the sequence count
-#ifdef OKV_ABLATE
-    const uint32_t hb = okv::knob("OKV_ZSTD_HUF_BLOCKS") ? uint32_t(atoi(okv::knob("OKV_ZSTD_HUF_BLOCKS")))
-                                                        : kHufBlocks;
-    if (hb == 16)
-      hipLaunchKernelGGL(okv_zstd_huf_kernel<16>, dim3((nblk + 15) / 16), dim3(64), 0, s, zb, nblk,
-                         htab, seg, ctx->z_blit.data(), ctx->z_cap_off.data());
-    else if (hb == 8)
-      hipLaunchKernelGGL(okv_zstd_huf_kernel<8>, dim3((nblk + 7) / 8), dim3(64), 0, s, zb, nblk,
-                         htab, seg, ctx->z_blit.data(), ctx->z_cap_off.data());
-    else if (hb == 2)
-      hipLaunchKernelGGL(okv_zstd_huf_kernel<2>, dim3((nblk + 1) / 2), dim3(64), 0, s, zb, nblk,
-                         htab, seg, ctx->z_blit.data(), ctx->z_cap_off.data());
-    else
-#endif
-    hipLaunchKernelGGL(okv_zstd_huf_kernel<kHufBlocks>, dim3((nblk + kHufBlocks - 1) / kHufBlocks),
-                       dim3(64), 0, s, zb, nblk, htab, seg, ctx->z_blit.data(),
-                       ctx->z_cap_off.data());
-    OKV_HIP(hipEventSynchronize(ctx->z_ev));
-    if (prof) (void)hipEventRecord(ev[1], s);
-    if ((rc = reserve(ctx, ctx->z_seqs, nseq_total + 8))) return rc;
+    plan.huf(s, zb, nblk, htab, seg, z->blit.data(), z->cap_off.data());
+    OKV_HIP(hipEventSynchronize(z->ev));
+    zst::diag_mark(ctx, z->diag, 1);
+    if ((rc = reserve(ctx, z->seqs, nseq_total + 8))) return rc;
     hipLaunchKernelGGL(okv_zstd_seq_kernel, dim3((nblk + 63) / 64), dim3(64), 0, s, zb, nblk,
-                       ctx->z_tabs.data(), ctx->z_seq_off.data(), ctx->z_seqs.data());
-    if (prof) (void)hipEventRecord(ev[2], s);
-    // one workgroup per block by default: the dispatcher balances blocks of
-    // unequal work better than a grid-stride loop (16 384 x 64 KiB: 3.8 ms vs
-    // 4.6 ms at 4096 workgroups, 5.6 at 2816); profiling caps it at its slots
-    uint32_t egrid = okv::knob("OKV_ZSTD_EXEC_GRID") ? uint32_t(atoi(okv::knob("OKV_ZSTD_EXEC_GRID")))
-                                                  : nblk;
-    if (prof) egrid = std::min(egrid, kExecGridMax);
-    egrid = std::max(egrid, 1u);
-#ifndef OKV_ZSTD_EXEC_PAD  // A/B builds: dynamic LDS per workgroup to lower the executor's occupancy
-#define OKV_ZSTD_EXEC_PAD 0  // (18 / 16 / 11 per CU: slower, zstd_seq_chain_ab.log)
-#endif
-    hipLaunchKernelGGL(okv_zstd_exec_kernel, dim3(std::min<uint32_t>(nblk, egrid)), dim3(64),
-                       OKV_ZSTD_EXEC_PAD, s, zb, nblk, ctx->z_seq_off.data(), ctx->z_seqs.data(),
-                       ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
-                       ctx->z_status.data(), eprof);
+                       z->tabs.data(), z->seq_off.data(), z->seqs.data());
+    zst::diag_mark(ctx, z->diag, 2);
+    hipLaunchKernelGGL(okv_zstd_exec_kernel, dim3(plan.exec_grid), dim3(64), OKV_ZSTD_EXEC_PAD, s,
+                       zb, nblk, z->seq_off.data(), z->seqs.data(), z->cap_off.data(),
+                       z->dec.data(), z->dec_len.data(), z->status.data(), plan.eprof);
   }
-  if (prof) (void)hipEventRecord(ev[3], s);
+  zst::diag_mark(ctx, z->diag, 3);
   const uint32_t grid = std::min<uint32_t>(nblk, 2048);
-  if ((rc = reserve(ctx, ctx->z_lit, size_t(grid) * kZstdLitBytes))) return rc;
+  if ((rc = reserve(ctx, z->lit, size_t(grid) * zst::kLitBytes))) return rc;
   hipLaunchKernelGGL(okv_zstd_kernel, dim3(grid), dim3(64), 0, s, seg, seg_bytes, descs, nblk,
-                     ctx->z_cap_off.data(), ctx->z_dec.data(), ctx->z_dec_len.data(),
-                     ctx->z_status.data(), ctx->z_lit.data(), nullptr, zb,
-                     ZRetry{nullptr, 0, 0, nullptr, nullptr, nullptr});
+                     z->cap_off.data(), z->dec.data(), z->dec_len.data(), z->status.data(),
+                     z->lit.data(), nullptr, zb, ZRetry{nullptr, 0, 0, nullptr, nullptr, nullptr});
   OKV_HIP(hipGetLastError());
-  if ((rc = zstd_regrow(ctx, seg, seg_bytes, descs, nblk, total_io))) return rc;
-  if (prof) {
-    (void)hipEventRecord(ev[4], s);
-    (void)hipStreamSynchronize(s);
-    float t[4] = {};
-    for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&t[k], ev[k], ev[k + 1]);
-    fprintf(stderr,
-            "[zstd prof] %u blocks: prologue+seqoff %.3f ms, sequences %.3f ms, executor %.3f ms, "
-            "general %.3f ms\n",
-            nblk, t[0], t[1], t[2], t[3]);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    static unsigned long long hs[16 * kExecGridMax];
-    (void)hipMemcpy(hs, eprof, sizeof(hs), hipMemcpyDeviceToHost);
-    unsigned long long h[16] = {};
-    for (uint32_t w = 0; w < kExecGridMax; ++w)
-      for (int k = 0; k < 16; ++k) h[k] += hs[w * 16 + k];
-    const double c = h[9] ? double(h[9]) : 1.0;
-    fprintf(stderr,
-            "[zstd exec] chunks %llu, cycles/chunk: load+scan %.0f map %.0f sources %.0f jump %.0f "
-            "(rounds %.2f) gather %.0f commit %.0f\n",
-            h[9], h[0] / c, h[1] / c, h[2] / c, h[3] / c, h[8] / c, h[4] / c, h[5] / c);
-    unsigned long long pp[16] = {};
-    (void)hipMemcpy(pp, pprof, sizeof(pp), hipMemcpyDeviceToHost);
-    const double nb = pp[13] ? double(pp[13]) : 1.0;
-    fprintf(stderr,
-            "[zstd pro] blocks %llu, cycles/block: whole %.0f literals %.0f (huffman tree %.0f) "
-            "sequence tables %.0f\n",
-            pp[13], pp[11] / nb, pp[0] / nb, pp[12] / nb, pp[10] / nb);
-  }
+  if ((rc = zstd_regrow(ctx, z, seg, seg_bytes, descs, nblk, total_io))) return rc;
+  zst::diag_mark(ctx, z->diag, 4);
   return OKV_OK;
 }
-void launch_zstd_cap(hipStream_t s, const Desc* descs, uint32_t nblk, uint64_t* cap_off) {
-  hipLaunchKernelGGL(okv_zstd_cap_kernel, dim3(1), dim3(1024), 0, s, descs, nblk, cap_off);
-}
-void launch_zstd_desc(hipStream_t s, const Desc* descs, uint32_t nblk, const uint64_t* cap_off,
-                      const uint64_t* dec_len, Desc* out) {
+
+// The whole stage for a batch of nblk >= 1 zstd blocks: first regions scanned
+// and their total read (one host round trip), the stages and the regrow
+// (zstd_run), then the decompressed blocks' descriptors.
+int zstd_stage(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
+               uint32_t nblk, ZstdOut* out) {
+  if (!ctx->zstd) ctx->zstd = new zst::Scratch();
+  zst::Scratch* z = ctx->zstd;
+  hipStream_t s = ctx->stream;
+  int rc;
+  const size_t n = size_t(nblk) + 1;
+  if ((rc = reserve(ctx, z->cap_off, n)) || (rc = reserve(ctx, z->dec_len, n)) ||
+      (rc = reserve(ctx, z->status, n)) || (rc = reserve(ctx, z->desc, n)))
+    return rc;
+  hipLaunchKernelGGL(okv_zstd_cap_kernel, dim3(1), dim3(1024), 0, s, descs, nblk,
+                     z->cap_off.data());
+  uint64_t total = 0;
+  OKV_HIP(hipMemcpyAsync(&total, z->cap_off.data() + nblk, 8, hipMemcpyDeviceToHost, s));
+  OKV_HIP(hipStreamSynchronize(s));
+  if ((rc = reserve(ctx, z->dec, total + 64))) return rc;
+  if ((rc = zstd_run(ctx, z, seg, seg_bytes, descs, nblk, &total))) return rc;
   hipLaunchKernelGGL(okv_zstd_desc_kernel, dim3((nblk + 255) / 256), dim3(256), 0, s, descs, nblk,
-                     cap_off, dec_len, out);
+                     z->cap_off.data(), z->dec_len.data(), z->desc.data());
+  OKV_HIP(hipGetLastError());
+  // offsets <= total < n_bytes, so no decompressed block reads as EOF
+  *out = ZstdOut{z->dec.data(), total + 16, z->desc.data(), z->status.data(), z->retried};
+  return OKV_OK;
 }
 
 }  // namespace okv

@@ -27,7 +27,9 @@ KNOBS = [b"OKV_GATHER_THREADS", b"OKV_GATHER_GRID", b"OKV_DECODE_FUSED", b"OKV_G
          b"OKV_VALUE_SWEEP", b"OKV_TILE", b"OKV_ZSTD_GENERAL", b"OKV_ZSTD_PROF",
          b"OKV_ENC_VARIANT", b"OKV_ENC_IMAGE", b"OKV_DECODE_PIECES", b"OKV_DECODE_STREAM",
          b"OKV_SMALL_PIECE_MB", b"OKV_COUNT_PREFETCH", b"OKV_ENC_ONEPASS", b"OKV_ENC_META_FUSED",
-         b"OKV_ZSTD_HUF_BLOCKS", b"OKV_DECODE_GROUP"]
+         b"OKV_ZSTD_HUF_BLOCKS", b"OKV_DECODE_GROUP", b"OKV_ZSTD_PRO_GRID", b"OKV_ZSTD_EXEC_GRID"]
+# the zstd stage's diagnostic reports (okv_zstd_ablate_host.inc): ablation build only
+ZSTD_REPORTS = [b"[zstd prof]", b"[zstd exec]", b"[zstd pro]"]
 
 
 def _bytes(path):
@@ -95,7 +97,7 @@ def test_decode_ablation_enters_through_hooks():
 
 def test_product_reads_no_environment():
     data = _bytes(PRODUCT)
-    for knob in KNOBS:
+    for knob in KNOBS + ZSTD_REPORTS:
         assert knob not in data, knob
     dyn = subprocess.run(["nm", "-D", "--undefined-only", PRODUCT], capture_output=True,
                          text=True, check=True).stdout
@@ -107,13 +109,43 @@ def test_ablation_build_carries_the_alternatives():
     for name in (b"okv_value_sweep_kernel", b"okv_gather_staged_kernel", b"okv_tile_kernel_w7",
                  b"okv_decode_stream_kernel", b"okv_enc_plan_kernel"):
         assert name in data, name
-    for knob in (b"OKV_VALUE_SWEEP", b"OKV_TILE", b"OKV_ZSTD_PROF"):
+    for knob in [b"OKV_VALUE_SWEEP", b"OKV_TILE", b"OKV_ZSTD_PROF"] + ZSTD_REPORTS:
         assert knob in data, knob
 
 
 def _strip_comments(src):
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return re.sub(r"//[^\n]*", "", src)
+
+
+def test_zstd_stage_owns_its_scratch_and_diagnostics_are_out_of_line():
+    """okv_zstd.hip's host part (everything after its last kernel) is the
+    product sequence: the knobs, the profiling and the reports live in
+    okv_zstd_ablate_host.inc, entered through hooks; the stage's scratch is
+    zst::Scratch in okv_zstd.hip, and neither the shared context nor
+    okv_decode.hip names a field of it."""
+    csrc = os.path.join(ROOT, "objectkv_amd", "csrc")
+    src = open(os.path.join(csrc, "okv_zstd.hip")).read()
+    inc = src.index('#include "okv_zstd_ablate_host.inc"')
+    assert src.rfind("#ifdef OKV_ABLATE", 0, inc) > src.rfind("#endif", 0, inc)
+    last_kernel = [m.start() for m in re.finditer(r"__global__", src)][-1]
+    assert inc > last_kernel
+    host = _strip_comments(src[last_kernel:])
+    for word in (r"\bknob\s*\(", r"\bgetenv\b", r"\batoi\b", r"\bfprintf\b", r"\bstatic\b"):
+        assert not re.search(word, host), word
+    assert src[last_kernel:].count("OKV_ABLATE") <= 3
+    m = re.search(r"\nint zstd_run\([^)]*\)\s*\{\n(.*?)\n\}\n", src, flags=re.S)
+    assert m and m.group(1).count("\n") + 1 <= 80
+    # the sequence launches each kernel from one place, the stream stage through launch_huf
+    launched = re.findall(r"hipLaunchKernelGGL\(\s*(\w+)", m.group(1))
+    assert len(launched) == len(set(launched)) == 5, launched
+    assert len(re.findall(r"hipLaunchKernelGGL\(\s*okv_zstd_huf_kernel\b", host)) == 1
+    assert "struct Scratch" in host and "#define" not in host
+    ctx = _strip_comments(open(os.path.join(csrc, "okv_ctx.hpp")).read())
+    assert not re.findall(r"\bz_[a-z_]+", ctx)
+    assert not re.search(r"\bkZstdLitBytes\b|\blaunch_zstd_\w+|\bzstd_run\b", ctx)
+    dec = _strip_comments(open(os.path.join(csrc, "okv_decode.hip")).read())
+    assert not re.findall(r"\bz_[a-z_]+", dec)
 
 
 def test_allocation_calls_are_confined():

@@ -35,10 +35,10 @@ def zdec(request, decoder, one_pass_decoder):
 SOA = ("row_start", "key_off", "key_len", "val_off", "val_len", "key_base", "val_base")
 
 
-def _check(decoder, seg, descs, index_only=False):
+def _check(decoder, seg, descs, index_only=False, comp=P.COMP_ZSTD):
     d = np.array(descs, np.uint64).reshape(-1, 4)
-    got = decoder.decode(np.frombuffer(seg, np.uint8), d, P.COMP_ZSTD, index_only=index_only)
-    ref = CO.decode_soa(seg, CO.descs_array(descs), P.COMP_ZSTD, index_only)
+    got = decoder.decode(np.frombuffer(seg, np.uint8), d, comp, index_only=index_only)
+    ref = CO.decode_soa(seg, CO.descs_array(descs), comp, index_only)
     assert np.array_equal(got.status, ref["status"])
     for k in SOA:
         if index_only and k in ("key_base", "val_base"):
@@ -247,3 +247,41 @@ def test_zstd_scratch_grows_and_is_reused():
         assert dec.last_path() & okv._lib.PATH_ZSTD_REGROW
     finally:
         dec.close()
+
+
+def test_zstd_state_is_per_context_and_per_decode():
+    """The stage's scratch and its retry count belong to one context and one
+    decode: two fresh contexts interleave regrowing, plain and index-only zstd
+    decodes with uncompressed ones (16 x 4 KiB; a context that has never seen
+    zstd has no zstd scratch at all), each equal to the oracle, and
+    okv_last_path reports the zstd stage and its regrow pass of that decode
+    alone."""
+    ZSTD, REGROW = okv._lib.PATH_ZSTD, okv._lib.PATH_ZSTD_REGROW
+    _, mixed, mixed_descs, want, regrow = [c for c in ZC.past_original_cases()
+                                           if c[0] == "mixed"][0]
+    assert regrow
+    _, zseg, zdescs, _ = ZC.cases()[0]
+    w = okv.synth_segment(okv.sst.SYNTH_FIXED, 1, nblocks=16, threshold=3584, block_size=4096)
+    raw, raw_descs = w.data().tobytes(), [tuple(int(x) for x in d) for d in w.descs()[:16]]
+    a, b = okv.Decoder(0), okv.Decoder(0)
+    try:
+        got = _check(a, mixed, mixed_descs)
+        assert [int(x) for x in got.status] == want
+        assert a.last_path() & REGROW
+        _check(b, raw, raw_descs, comp=P.COMP_NONE)
+        assert not b.last_path() & (ZSTD | REGROW)
+        got = _check(a, zseg, zdescs)
+        assert int(got.status.max()) == 0
+        assert a.last_path() & ZSTD and not a.last_path() & REGROW
+        _check(a, zseg, zdescs, index_only=True)
+        assert not a.last_path() & REGROW
+        _check(a, raw, raw_descs, comp=P.COMP_NONE)
+        assert not a.last_path() & (ZSTD | REGROW)
+        got = _check(b, mixed, mixed_descs)
+        assert [int(x) for x in got.status] == want
+        assert b.last_path() & REGROW
+        got = _check(a, mixed, mixed_descs)
+        assert [int(x) for x in got.status] == want
+    finally:
+        b.close()
+        a.close()
