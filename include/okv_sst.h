@@ -36,7 +36,10 @@ extern "C" {
                              3: okv_open_ex / okv_open_opts
                              4: okv_decode_chain
                              5: OKV_OPEN_NO_POINT / OKV_PATH_POINT (host-mode point path)
-                             6: okv_point_get (GetRow's block step, one row back) */
+                             6: okv_point_get (GetRow's block step, one row back);
+                                still 6 with the device bloom filter (okv_bloom_*,
+                                OKV_F_BLOOM_DEVICE): purely additive -- new symbols and one
+                                new flag bit, no struct layout or behaviour change */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -79,6 +82,8 @@ extern "C" {
                                 totals are NOT filled (call okv_decode_totals after okv_sync) */
 #define OKV_F_NO_CLOSE 8u    /* encode: stop after blocks + block index + meta block; the
                                 meta XXH64 and the 25-byte trailer are left to okv_encode_close */
+#define OKV_F_BLOOM_DEVICE 16u /* okv_encode_rows: opts->bloom is a DEVICE pointer (copied device
+                                to device on the ctx stream); independent of OKV_F_DEVICE_PTRS */
 
 /* One data-block index entry: BlockStat (sst/block_stat.go:9-24) without
  * FirstKey and Hash, which the decode does not need. */
@@ -252,10 +257,12 @@ typedef struct okv_rows {
   uint64_t key_arena_bytes, val_arena_bytes;
 } okv_rows;
 
-/* SegmentWriterOptions (segment_writer_option.go:5-16).  The bloom filter is
- * an opaque pass-through: the caller runs BloomFilter.Add per row
- * (segment_writer.go:133-136) and hands over BloomFilter.WriteTo's bytes; the
- * meta block then carries [1][u64 LE length][bytes] (:295-300), else [0]. */
+/* SegmentWriterOptions (segment_writer_option.go:5-16).  The encoder treats the
+ * bloom filter as opaque bytes: BloomFilter.WriteTo's output after Add has run
+ * for every row (segment_writer.go:133-136), either from the caller's host
+ * filter or, with OKV_F_BLOOM_DEVICE, from okv_bloom_add_rows +
+ * okv_bloom_write_to on the device; the meta block then carries
+ * [1][u64 LE length][bytes] (:295-300), else [0]. */
 typedef struct okv_encode_opts {
   uint64_t threshold_bytes; /* DataBlockThresholdBytes (default 3584) */
   uint64_t block_size;      /* DataBlockSize (default 4096) */
@@ -264,7 +271,8 @@ typedef struct okv_encode_opts {
                                OKV_COMP_ZSTD -> OKV_W_UNSUPPORTED */
   int strict_go;            /* 1: a Close with no open block panics in Go (Q1) ->
                                OKV_W_NIL_WRITER; 0: write the footer normally */
-  const uint8_t *bloom;     /* host bytes of BloomFilter.WriteTo, or NULL (BloomFilter nil) */
+  const uint8_t *bloom;     /* bytes of BloomFilter.WriteTo (host memory; device memory with
+                               OKV_F_BLOOM_DEVICE), or NULL (BloomFilter nil) */
   uint64_t bloom_len;
 } okv_encode_opts;
 
@@ -294,7 +302,7 @@ typedef struct okv_encode_out {
 /*
  * Encode rows into one segment on the GPU.  flags: OKV_F_DEVICE_PTRS (rows and
  * every output pointer are device pointers; seg must be 16-byte aligned),
- * OKV_F_NO_CLOSE.  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
+ * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE.  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
  * written: call again with seg_cap >= file_bytes and blk_cap >= n_blocks --
  * a call with zero capacities is the size query); OKV_W_INVALID_KEY (bad_row
  * set); OKV_W_NIL_WRITER (strict_go and the last row closed a block, or no
@@ -324,6 +332,66 @@ int okv_synth_rows_fixed(okv_ctx *ctx, uint64_t seed, uint64_t first_row, uint64
                          uint32_t key_len, uint32_t val_len, uint8_t *key_arena,
                          uint64_t *key_off, uint16_t *key_len_out, uint8_t *val_arena,
                          uint64_t *val_off, uint32_t *val_len_out);
+
+/* ======================================================================== *
+ * Bloom filter on the device: bloom.BloomFilter (bits-and-blooms v2.0.3 over
+ * murmur3 v1.1.0 and bitset v1.1.11), the filter DefaultSegmentWriterOptions
+ * carries (segment_writer_option.go:20).  WriteRow's Add per row
+ * (segment_writer.go:133-136) becomes okv_bloom_add_rows over rows in device
+ * memory, generateMetaBlock's WriteTo (:295-300) okv_bloom_write_to, and the
+ * bytes go to okv_encode_rows with OKV_F_BLOOM_DEVICE: in stream order, with no
+ * host copy of keys or filter.  Bytes equal Go's WriteTo (PARITY UNPINNED as in
+ * okv_host.cpp: no reference test asserts filter bytes).  DESIGN.md 19.
+ *
+ * flags: OKV_F_DEVICE_PTRS (the arrays of okv_rows, `maybe` and `dst` are device
+ * pointers) and OKV_F_ASYNC (with DEVICE_PTRS: enqueue on the ctx stream and
+ * return); host mode stages the key arrays, runs and synchronises.  Of okv_rows
+ * only key_arena, key_off, key_len, n_rows and key_arena_bytes are read (the
+ * value fields may be NULL); empty keys are legal (Add accepts them);
+ * n_rows == 0 succeeds and launches nothing.  The kernels read a key as aligned
+ * 8-byte words that each contain at least one byte of it.
+ * A filter belongs to the context that created it (another one: OKV_E_ARG) and
+ * must be freed before that context is closed.
+ *
+ * Divergences from Go, all OKV_E_ARG: k > 4096 on add and test (Go has no cap;
+ * a ReadFrom header must not size an unbounded loop); add on a filter whose
+ * bitset length != m (Go's bitset.Set would grow the set); test with m == 0
+ * and k > 0 (Go's integer-division panic; the host probe: OKV_R_PANIC).
+ * ======================================================================== */
+typedef struct okv_bloom okv_bloom; /* bloom.BloomFilter resident on the device */
+#define OKV_BLOOM_FORCE_LDS 32u    /* okv_bloom_add_rows: the LDS-sliced form (filters of up to
+                                      1 MiB of words; larger: OKV_E_ARG) */
+#define OKV_BLOOM_FORCE_GLOBAL 64u /* okv_bloom_add_rows: one global atomic OR per location */
+#define OKV_BLOOM_PATH_LDS 1u      /* okv_bloom_add_lds_kernel */
+#define OKV_BLOOM_PATH_GLOBAL 2u   /* okv_bloom_add_global_kernel */
+
+/* bloom.EstimateParameters(n, p); host only, no context */
+void okv_bloom_estimate(uint64_t n, double p, uint64_t *m, uint64_t *k);
+/* bloom.New: max(1, m), max(1, k), bitset length = m, every bit zero */
+int okv_bloom_new(okv_ctx *ctx, uint64_t m, uint64_t k, okv_bloom **out);
+/* BloomFilter.ReadFrom of host bytes (big-endian m, k, bitset length, words): a
+ * short input or too few words is OKV_E_ARG and no object; trailing bytes are
+ * ignored */
+int okv_bloom_read_from(okv_ctx *ctx, const uint8_t *host_bytes, uint64_t len, okv_bloom **out);
+void okv_bloom_free(okv_bloom *f);
+/* write_to_bytes = 24 + 8 * wordsNeeded(length); any output pointer may be NULL */
+int okv_bloom_info(const okv_bloom *f, uint64_t *m, uint64_t *k, uint64_t *length,
+                   uint64_t *write_to_bytes);
+/* ClearAll (enqueued on the ctx stream) */
+int okv_bloom_clear(okv_ctx *ctx, okv_bloom *f);
+/* Add(key) for every row.  flags also takes OKV_BLOOM_FORCE_LDS / _GLOBAL */
+int okv_bloom_add_rows(okv_ctx *ctx, okv_bloom *f, const okv_rows *rows, uint32_t flags);
+/* Test(key) for every row: maybe[i] = 1 (maybe present) or 0 (absent); k == 0
+ * gives 1 for every key */
+int okv_bloom_test_rows(okv_ctx *ctx, const okv_bloom *f, const okv_rows *rows, uint8_t *maybe,
+                        uint32_t flags);
+/* WriteTo: write_to_bytes bytes into dst (a device dst must be 8-byte aligned:
+ * else OKV_E_ARG); cap too small: OKV_E_CAPACITY */
+int okv_bloom_write_to(okv_ctx *ctx, const okv_bloom *f, uint8_t *dst, uint64_t cap,
+                       uint32_t flags);
+/* The form the filter's last okv_bloom_add_rows took (OKV_BLOOM_PATH_*; 0: it
+ * launched nothing), in the manner of okv_last_path */
+uint32_t okv_bloom_last_path(const okv_bloom *f);
 
 /* ======================================================================== *
  * Merge: snapshot_reader.Reader.GetRange's k-way merge

@@ -8,7 +8,9 @@ from ._lib import build, lib  # noqa: F401
 from .sst import (Decoded, Decoder, Encoded, Encoder, GpuSegmentWriter, Metadata,  # noqa: F401
                   OkvError, SegmentWriter, bytes_to_metadata, fetch_metadata, pack_rows,
                   synth_segment, xxh64)
+from .bloom import DeviceBloom  # noqa: F401
 
-__all__ = ["build", "lib", "Decoder", "Decoded", "Encoder", "Encoded", "GpuSegmentWriter",
+__all__ = ["build", "lib", "Decoder", "Decoded", "DeviceBloom", "Encoder", "Encoded",
+           "GpuSegmentWriter",
            "Metadata", "OkvError", "SegmentWriter", "pack_rows",
            "bytes_to_metadata", "fetch_metadata", "synth_segment", "xxh64"]

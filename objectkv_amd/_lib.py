@@ -27,6 +27,9 @@ OKV_OK, OKV_E_ARG, OKV_E_HIP, OKV_E_CAPACITY, OKV_E_NOMEM, OKV_E_NODEV = 0, -1, 
 BLK_OK, BLK_EOF, BLK_SHORT, BLK_PANIC, BLK_UNSUPPORTED, BLK_CAPACITY = 0, 1, 2, 3, 4, 5
 COMP_NONE, COMP_ZSTD, COMP_LZ4 = 0, 1, 2
 F_DEVICE_PTRS, F_INDEX_ONLY, F_ASYNC, F_NO_CLOSE = 1, 2, 4, 8
+F_BLOOM_DEVICE = 16
+BLOOM_FORCE_LDS, BLOOM_FORCE_GLOBAL = 32, 64
+BLOOM_PATH_LDS, BLOOM_PATH_GLOBAL = 1, 2
 OPEN_NO_FUSED, OPEN_ZSTD_ONE_PASS, OPEN_NO_POINT = 1, 2, 4
 # okv_last_path bits (include/okv_sst.h OKV_PATH_*)
 PATH_FUSED, PATH_SMALL, PATH_TILE, PATH_SWEEP = 1, 2, 4, 8
@@ -51,6 +54,9 @@ SYMBOLS = [
     "okv_decode_chain",
     "okv_encode_rows", "okv_encode_close", "okv_encode_profile_read", "okv_encode_profile_reset",
     "okv_synth_rows_fixed", "okv_merge_rows",
+    "okv_bloom_estimate", "okv_bloom_new", "okv_bloom_read_from", "okv_bloom_free",
+    "okv_bloom_info", "okv_bloom_clear", "okv_bloom_add_rows", "okv_bloom_test_rows",
+    "okv_bloom_write_to", "okv_bloom_last_path",
     "okv_writer_new", "okv_writer_write_row", "okv_writer_close", "okv_writer_data",
     "okv_writer_meta", "okv_writer_num_blocks", "okv_writer_block", "okv_writer_free",
     "okv_writer_set_bloom",
@@ -202,6 +208,17 @@ def lib():
         "okv_synth_rows_fixed": (i32, [p, u64, u64, u64, u32, u32, p, p, p, p, p, p]),
         "okv_merge_rows": (i32, [p, C.POINTER(MergeSrc), u32, C.POINTER(MergeOpts),
                                  C.POINTER(MergeOut), u32]),
+        "okv_bloom_estimate": (None, [u64, C.c_double, C.POINTER(u64), C.POINTER(u64)]),
+        "okv_bloom_new": (i32, [p, u64, u64, C.POINTER(p)]),
+        "okv_bloom_read_from": (i32, [p, p, u64, C.POINTER(p)]),
+        "okv_bloom_free": (None, [p]),
+        "okv_bloom_info": (i32, [p, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64),
+                                 C.POINTER(u64)]),
+        "okv_bloom_clear": (i32, [p, p]),
+        "okv_bloom_add_rows": (i32, [p, p, C.POINTER(Rows), u32]),
+        "okv_bloom_test_rows": (i32, [p, p, C.POINTER(Rows), p, u32]),
+        "okv_bloom_write_to": (i32, [p, p, p, u64, u32]),
+        "okv_bloom_last_path": (C.c_uint32, [p]),
         "okv_writer_new": (p, [u64, u64, i32, i32]),
         "okv_writer_write_row": (i32, [p, p, C.c_size_t, p, C.c_size_t]),
         "okv_writer_close": (i32, [p, i32, C.POINTER(u64), C.POINTER(u64)]),

@@ -1707,7 +1707,7 @@ __global__ __launch_bounds__(kThreads) void okv_enc_meta_kernel(MetaParams P) {
     put_le(p, kz, 2);
     put_bytes(p + 2, P.key_arena + P.key_off[P.n - 1], kz);
     p += 2 + kz;
-    if (P.bloom_len != ~uint64_t(0)) {  // :295-300 (the filter bytes: a host copy)
+    if (P.bloom_len != ~uint64_t(0)) {  // :295-300 (the filter bytes: a copy enqueued by enc_write)
       p[0] = 1;
       put_le(p + 1, P.bloom_len, 8);
       p += 9 + P.bloom_len;
@@ -2163,7 +2163,7 @@ int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
 
 // Data blocks, block hashes and the meta block into seg (E10-E12).
 int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
-              const Plan& pl, uint8_t* seg) {
+              const Plan& pl, uint8_t* seg, bool bloom_dev) {
   enc_mark(ctx, e, 1);
   PackParams pp;
   pp.key_arena = R.ka;
@@ -2212,7 +2212,8 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
   mp.fkl = e->fkl.data();
   if (o.bloom && o.bloom_len)  // BloomFilter.WriteTo bytes at head - 10 - len (after flag + u64)
     OKV_HIP(hipMemcpyAsync(mp.meta + pl.head - 10 - o.bloom_len, o.bloom, o.bloom_len,
-                           hipMemcpyHostToDevice, ctx->stream));
+                           bloom_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                           ctx->stream));
   if (meta_done || (reinterpret_cast<uintptr_t>(mp.meta) & 15) == 0) {
     // head bytes by the first lane of a one-block launch (nb = 0); entries via
     // LDS unless the pack kernel wrote them
@@ -2438,7 +2439,7 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
     if ((rc = reserve(ctx, e->d_outseg, pl.file_bytes + 64))) return rc;
     seg = e->d_outseg.data();
   }
-  if ((rc = enc_write(ctx, e, R, *opts, pl, seg))) return rc;
+  if ((rc = enc_write(ctx, e, R, *opts, pl, seg, flags & OKV_F_BLOOM_DEVICE))) return rc;
   const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (out->blk_first_row)
     OKV_HIP(hipMemcpyAsync(out->blk_first_row, e->first.data(), (pl.nb + 1) * 8, k, ctx->stream));

@@ -419,6 +419,11 @@ class Encoded:
         return self.seg[self.data_bytes:self.data_bytes + self.meta_bytes].tobytes()
 
 
+def _is_device_bloom(bloom) -> bool:
+    from .bloom import DeviceBloom  # (bloom.py imports this module)
+    return isinstance(bloom, DeviceBloom)
+
+
 def pack_rows(rows):
     """[(key, value), ...] -> SoA numpy arrays (okv_rows layout)."""
     keys = [bytes(k) for k, _ in rows]
@@ -450,11 +455,25 @@ class Encoder(Decoder):
     def profile_reset_encode(self):
         self._check(lib().okv_encode_profile_reset(self._ctx), "okv_encode_profile_reset")
 
+    def _device_bloom(self, bloom, rows, **kw):
+        """A DeviceBloom given as bloom=: the rows of the call are added on the
+        device (in stream order before the encode) -> OKV_F_BLOOM_DEVICE, else 0."""
+        if not _is_device_bloom(bloom):
+            return 0
+        if bloom._owner._ctx != self._ctx:
+            raise OkvError(_lib.OKV_E_ARG, "bloom: the filter belongs to another context")
+        bloom.add_rows(rows, **kw)
+        return _lib.F_BLOOM_DEVICE
+
     @staticmethod
     def _opts(threshold, block_size, compression, strict_go, bloom=None):
-        """bloom: BloomFilter.WriteTo bytes (kept alive on the returned struct)."""
+        """bloom: BloomFilter.WriteTo bytes (kept alive on the returned struct), or
+        a DeviceBloom, whose WriteTo is enqueued into device memory."""
         o = _lib.EncodeOpts(threshold, block_size, compression, int(strict_go), None, 0)
-        if bloom is not None:
+        if _is_device_bloom(bloom):
+            o._bloom = bloom
+            o.bloom, o.bloom_len = bloom.write_to_device(sync=False)
+        elif bloom is not None:
             o._bloom = np.frombuffer(bytes(bloom), np.uint8) if len(bloom) else \
                 np.zeros(1, np.uint8)
             o.bloom, o.bloom_len = o._bloom.ctypes.data, len(bloom)
@@ -463,15 +482,17 @@ class Encoder(Decoder):
     def encode(self, rows, threshold=3584, block_size=4096, compression=COMP_NONE,
                strict_go=True, bloom=None) -> Encoded:
         """Host-buffer encode: rows is a list of (key, value) pairs or the dict
-        of SoA arrays from pack_rows().  bloom: the filter's WriteTo bytes."""
+        of SoA arrays from pack_rows().  bloom: the filter's WriteTo bytes, or a
+        DeviceBloom (the rows are added to it on the device)."""
         r = rows if isinstance(rows, dict) else pack_rows(rows)
         n = int(r["key_len"].size)
         R = _lib.Rows(_ptr(r["key_arena"]), _ptr(r["key_off"]), _ptr(r["key_len"]),
                       _ptr(r["val_arena"]), _ptr(r["val_off"]), _ptr(r["val_len"]), n,
                       int(r["key_arena"].size), int(r["val_arena"].size))
+        flags = self._device_bloom(bloom, r)
         o = self._opts(threshold, block_size, compression, strict_go, bloom)
         out = _lib.EncodeOut()
-        rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(out), 0)
+        rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(out), flags)
         if rc != OKV_E_CAPACITY:
             self._check(rc, "okv_encode_rows(size)")
         nb = out.n_blocks
@@ -480,7 +501,7 @@ class Encoder(Decoder):
         descs = np.zeros((nb, 4), np.uint64)
         hashes = np.zeros(nb, np.uint64)
         out = _lib.EncodeOut(_ptr(seg), seg.size, _ptr(first), _ptr(descs), _ptr(hashes), nb)
-        rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(out), 0)
+        rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(out), flags)
         self._check(rc, "okv_encode_rows")
         return Encoded(seg, out.file_bytes, out.data_bytes, out.meta_bytes, out.meta_hash,
                        first, descs, hashes)
@@ -496,6 +517,8 @@ class Encoder(Decoder):
         R = _lib.Rows(_ptr(rows["key_arena"]), _ptr(rows["key_off"]), _ptr(rows["key_len"]),
                       _ptr(rows["val_arena"]), _ptr(rows["val_off"]), _ptr(rows["val_len"]),
                       n_rows, key_arena_bytes, val_arena_bytes)
+        bflag = self._device_bloom(bloom, rows, n_rows=n_rows, key_arena_bytes=key_arena_bytes,
+                                   sync=False)
         o = self._opts(threshold, block_size, compression, strict_go, bloom)
         g = out.get
         caps = [t.shape[0] for t in (g("first_row"), g("desc"), g("hash")) if t is not None]
@@ -503,7 +526,7 @@ class Encoder(Decoder):
             if caps else 0
         eo = _lib.EncodeOut(_ptr(g("seg")), g("seg").numel() if g("seg") is not None else 0,
                             _ptr(g("first_row")), _ptr(g("desc")), _ptr(g("hash")), blk_cap)
-        flags = F_DEVICE_PTRS | (0 if close else _lib.F_NO_CLOSE)
+        flags = F_DEVICE_PTRS | (0 if close else _lib.F_NO_CLOSE) | bflag
         rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(eo), flags)
         if rc:
             err = OkvError(rc, f"okv_encode_rows(device): {self.error()}")
@@ -532,7 +555,8 @@ class GpuSegmentWriter:
     it; Close runs okv_encode_rows over the buffered rows and returns
     (file length, meta block bytes).  ``data()`` is what the Go writer's sink
     holds afterwards.  bloom: as SegmentWriter's (add per row, WriteTo bytes
-    into the meta block)."""
+    into the meta block), or a DeviceBloom: no per-row add, Close adds the
+    buffered rows on the device."""
 
     def __init__(self, encoder: Encoder, threshold=3584, block_size=4096, zstd_level=0,
                  lz4=False, strict_go=True, bloom=None):
@@ -557,13 +581,14 @@ class GpuSegmentWriter:
         if not key:
             raise OkvError(_lib.W_INVALID_KEY, "key cannot be empty: ErrInvalidKey")
         self._rows.append((key, val))
-        if self.bloom is not None:
+        if self.bloom is not None and not _is_device_bloom(self.bloom):
             self.bloom.add(key)
 
     def Close(self):
         if self._closed:  # Go: blockWriter is nil after the first Close -> panic (Q1)
             raise OkvError(_lib.W_NIL_WRITER, "Close on a closed writer")
-        bloom = self.bloom.to_bytes() if self.bloom is not None else None
+        bloom = self.bloom if self.bloom is None or _is_device_bloom(self.bloom) \
+            else self.bloom.to_bytes()
         self.result = self._enc.encode(self._rows, bloom=bloom, **self._opts)
         self._closed = True
         return self.result.file_bytes, self.result.meta()
