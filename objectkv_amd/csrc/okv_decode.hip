@@ -1631,7 +1631,7 @@ struct GlobalSrc {
 //   row i bytes = src[spos_i, spos_i + len_i) -> arena[dbase + pre_i, ...).
 // Lane groups of G lanes own one row; each lane writes 16-byte aligned
 // destination chunks (dwordx4), masked head/tail chunks with narrow stores.
-template <int V, class Src>
+template <class Src>
 __device__ __forceinline__ void copy_region(const Src& src, uint8_t* __restrict__ arena,
                                             uint64_t dbase, const uint64_t* pre,
                                             const uint64_t* rec, const uint32_t* klen,
@@ -1647,20 +1647,20 @@ __device__ __forceinline__ void copy_region(const Src& src, uint8_t* __restrict_
     const uint64_t c0 = d0 & ~uint64_t(15), c1 = (d0 + L + 15) & ~uint64_t(15);
     for (uint64_t ca = c0 + 16ull * sub; ca < c1; ca += 16ull * G) {
       const int64_t rel = int64_t(ca) - int64_t(d0);
-      const uint4 v = (V == 5) ? make_uint4(uint32_t(ca), 0, 0, 0) : src.load16(s0 + rel);
+      const uint4 v = src.load16(s0 + rel);
       const uint32_t lo = ca < d0 ? uint32_t(d0 - ca) : 0u;
       const uint64_t end = d0 + L - ca;
       const uint32_t hi = end < 16 ? uint32_t(end) : 16u;
       if (lo == 0 && hi == 16) {
         *reinterpret_cast<uint4*>(arena + ca) = v;
-      } else if (V != 4) {
+      } else {
         store_partial(arena + ca, v, lo, hi);
       }
     }
   }
 }
 
-template <int V, class Src>
+template <class Src>
 __device__ __forceinline__ void materialise(const Src& src, const CopyParams& P,
                                            CopySmem& sm, uint64_t rows, uint64_t kbytes,
                                            uint64_t vbytes, uint64_t row0, uint64_t kb0,
@@ -1701,8 +1701,8 @@ __device__ __forceinline__ void materialise(const Src& src, const CopyParams& P,
       P.val_off[g] = vb0 + sm.s.vpre[i];
       P.val_len[g] = sm.s.vlen[i];
     }
-    copy_region<V>(src, P.key_arena, kb0, sm.s.kpre, sm.s.rec, sm.s.klen, sm.s.klen, false, nb, Gk);
-    copy_region<V>(src, P.val_arena, vb0, sm.s.vpre, sm.s.rec, sm.s.klen, sm.s.vlen, true, nb, Gv);
+    copy_region(src, P.key_arena, kb0, sm.s.kpre, sm.s.rec, sm.s.klen, sm.s.klen, false, nb, Gk);
+    copy_region(src, P.val_arena, vb0, sm.s.vpre, sm.s.rec, sm.s.klen, sm.s.vlen, true, nb, Gv);
     __syncthreads();
   }
   // zero the 16-byte padding tail of each arena region
@@ -1720,7 +1720,7 @@ __device__ __forceinline__ void materialise(const Src& src, const CopyParams& P,
 // registers, merging bytes of the following rows when the chunk spills past
 // its row (no partial stores, so neighbouring chunks never race).  The last
 // chunk of a region is zero-filled past the region end (16-byte padding).
-template <bool kVal, int V = 3>
+template <bool kVal>
 __device__ __forceinline__ void copy_region_fast(const uint4* __restrict__ s4, uint32_t bias,
                                                  uint8_t* __restrict__ arena, uint64_t dbase,
                                                  const FastRows& t, int rows, uint32_t G) {
@@ -1734,10 +1734,6 @@ __device__ __forceinline__ void copy_region_fast(const uint4* __restrict__ s4, u
     const uint32_t si = bias + t.rec[i] + 6 + (kVal ? t.kpre[i + 1] - t.kpre[i] : 0u);
     for (uint32_t c = cfirst + sub; c <= clast; c += G) {
       const uint32_t cs = c << 4, ce = cs + 16;
-      if (V == 6) {  // diagnostic: stores only
-        *reinterpret_cast<uint4*>(arena + dbase + cs) = make_uint4(cs, i, 0, 0);
-        continue;
-      }
       uint4 out = load16_lds_b128(s4, si + (cs - p0));
       if (ce > p1) {  // spills past row i: keep [0, p1-cs), gather the rest
         out = merge_bytes(make_uint4(0, 0, 0, 0), out, 0, int32_t(p1 - cs));
@@ -1749,10 +1745,6 @@ __device__ __forceinline__ void copy_region_fast(const uint4* __restrict__ s4, u
           out = merge_bytes(out, v, int32_t(q0 - cs), int32_t((q1 < ce ? q1 : ce) - cs));
         }
       }
-      if (V == 7) {  // diagnostic: no stores
-        asm volatile("" ::"v"(out.x), "v"(out.y), "v"(out.z), "v"(out.w));
-        continue;
-      }
       *reinterpret_cast<uint4*>(arena + dbase + cs) = out;
     }
   }
@@ -1760,7 +1752,6 @@ __device__ __forceinline__ void copy_region_fast(const uint4* __restrict__ s4, u
 
 // SoA rows and both arena regions of a block staged in LDS whose row table
 // (rec / kpre / vpre, <= kFastRows rows) is built.
-template <int V>
 __device__ __forceinline__ void emit_fast(const CopyParams& P, CopySmem& sm, uint32_t bias,
                                           int rows, uint64_t kbytes, uint64_t vbytes,
                                           uint64_t row0, uint64_t kb0, uint64_t vb0) {
@@ -1773,13 +1764,11 @@ __device__ __forceinline__ void emit_fast(const CopyParams& P, CopySmem& sm, uin
     P.val_off[g] = vb0 + t.vpre[i];
     P.val_len[g] = t.vpre[i + 1] - t.vpre[i];
   }
-  if (V < 3) return;
   const uint32_t Gk = group_size(kbytes / rows), Gv = group_size(vbytes / rows);
-  copy_region_fast<false, V>(sm.stage, bias, P.key_arena, kb0, t, rows, Gk);
-  copy_region_fast<true, V>(sm.stage, bias, P.val_arena, vb0, t, rows, Gv);
+  copy_region_fast<false>(sm.stage, bias, P.key_arena, kb0, t, rows, Gk);
+  copy_region_fast<true>(sm.stage, bias, P.val_arena, vb0, t, rows, Gv);
 }
 
-template <int V>
 __device__ __forceinline__ void materialise_fast(const CopyParams& P, CopySmem& sm,
                                                 uint32_t bias, int rows, uint64_t kbytes,
                                                 uint64_t vbytes, uint64_t row0, uint64_t kb0,
@@ -1809,8 +1798,7 @@ __device__ __forceinline__ void materialise_fast(const CopyParams& P, CopySmem& 
     t.vpre[rows] = va;
   }
   __syncthreads();
-  if (V < 2) return;  // diagnostic ablation (okv_copy_kernel<V>)
-  emit_fast<V>(P, sm, bias, rows, kbytes, vbytes, row0, kb0, vb0);
+  emit_fast(P, sm, bias, rows, kbytes, vbytes, row0, kb0, vb0);
 }
 
 __global__ __launch_bounds__(kThreads) void okv_copy_kernel(CopyParams P) {
@@ -1831,15 +1819,15 @@ __global__ __launch_bounds__(kThreads) void okv_copy_kernel(CopyParams P) {
       for (uint32_t ci = tid; ci < nch; ci += kThreads) sm.stage[1 + ci] = load_nt16(g + ci);
       __syncthreads();
       if (c.rows <= uint64_t(kFastRows)) {
-        materialise_fast<3>(P, sm, 16u + shift, int(c.rows), c.kbytes, c.vbytes, B.row0, B.kb0,
+        materialise_fast(P, sm, 16u + shift, int(c.rows), c.kbytes, c.vbytes, B.row0, B.kb0,
                             B.vb0);
       } else {
         LdsSrc src{reinterpret_cast<const uint32_t*>(sm.stage), 16u + shift};
-        materialise<3>(src, P, sm, c.rows, c.kbytes, c.vbytes, B.row0, B.kb0, B.vb0, c.pend);
+        materialise(src, P, sm, c.rows, c.kbytes, c.vbytes, B.row0, B.kb0, B.vb0, c.pend);
       }
     } else {
       GlobalSrc src{P.seg, P.seg_bytes, d.offset};
-      materialise<3>(src, P, sm, c.rows, c.kbytes, c.vbytes, B.row0, B.kb0, B.vb0, c.pend);
+      materialise(src, P, sm, c.rows, c.kbytes, c.vbytes, B.row0, B.kb0, B.vb0, c.pend);
     }
     __syncthreads();  // LDS is reused by the next big block
   }
@@ -2103,7 +2091,7 @@ __global__ __launch_bounds__(kThreads) void okv_point_kernel(CopyParams P, Total
         vb = vtot;
         __syncthreads();
         OKV_POINT_STAMP(3);
-        emit_fast<3>(P, sm, bias, int(rows), kb, vb, row0, kb0, vb0);
+        emit_fast(P, sm, bias, int(rows), kb, vb, row0, kb0, vb0);
       } else {
         // more rows than the row table holds: the byte totals by a second
         // walk (the block passed its checks), then the batched row tables
@@ -2123,7 +2111,7 @@ __global__ __launch_bounds__(kThreads) void okv_point_kernel(CopyParams P, Total
         kb = s_walk[1];
         vb = s_walk[2];
         LdsSrc src{sw, bias};
-        materialise<3>(src, P, sm, rows, kb, vb, row0, kb0, vb0, pend);
+        materialise(src, P, sm, rows, kb, vb, row0, kb0, vb0, pend);
       }
     }
     row0 += rows;

@@ -225,13 +225,13 @@ okv_block_kernel(CopyParams P, FusedParams F) {
   }
   if (B.st != OKV_BLK_OK || rows == 0) return;
   if (staged && rows <= uint64_t(kFastRows)) {
-    emit_fast<3>(P, sm, bias, int(rows), kb, vb, B.row0, B.kb0, B.vb0);
+    emit_fast(P, sm, bias, int(rows), kb, vb, B.row0, B.kb0, B.vb0);
   } else if (staged) {
     LdsSrc src{reinterpret_cast<const uint32_t*>(sm.stage), bias};
-    materialise<3>(src, P, sm, rows, kb, vb, B.row0, B.kb0, B.vb0, pend);
+    materialise(src, P, sm, rows, kb, vb, B.row0, B.kb0, B.vb0, pend);
   } else {
     GlobalSrc src{P.seg, P.seg_bytes, off};
-    materialise<3>(src, P, sm, rows, kb, vb, B.row0, B.kb0, B.vb0, pend);
+    materialise(src, P, sm, rows, kb, vb, B.row0, B.kb0, B.vb0, pend);
   }
 }
 

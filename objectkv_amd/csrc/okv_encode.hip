@@ -1067,8 +1067,8 @@ struct PackParams {
   const Desc* desc;
   uint8_t* seg;
   uint64_t* hash;  // BlockStat.Hash, written by kernels that hash in LDS
-  uint8_t* meta;   // non-null: okv_enc_pack_lds_kernel also writes the blocks' meta
-                   // index entries (BlockStat.toBytes, block_stat.go:27-42) here
+  uint8_t* meta;   // non-null (ablation build, the fused-meta arm): the pack kernel also writes
+                   // the blocks' meta index entries (BlockStat.toBytes, block_stat.go:27-42) here
   const uint64_t* moff;  // [nb] entry offsets within the meta block
   uint8_t* fk = nullptr;  // non-null: the LDS kernel keeps each block's first kFkStride bytes
 };
@@ -1242,8 +1242,23 @@ struct __align__(16) RegionSmem {
   uint64_t bbase[kMaxRegion];   // P(first row - 1)
 };
 
-template <int V>  // diagnostic ablation (OKV_ENC_VARIANT): 0 product, 1 tables only,
-                 // 2 tables + zero stores
+// The block of a region of g blocks that holds x: the last b with tab[b] <= x.
+// tab = bfirst finds the block of a row, tab = brel the block of a byte of the
+// region (T = uint32_t: offsets within an LDS image compare in 32 bits).
+template <class T>
+__device__ __forceinline__ uint32_t region_block(const uint64_t* tab, uint32_t g, T x) {
+  uint32_t lo = 0, hi = g;  // tab[lo] <= x < tab[hi]
+  while (hi - lo > 1) {
+    const uint32_t m = (lo + hi) >> 1;
+    if (T(tab[m]) <= x)
+      lo = m;
+    else
+      hi = m;
+  }
+  return lo;
+}
+
+// (its diagnostic arms: okv_enc_pack_region_arm_kernel, okv_encode_ablate_pack.inc)
 __global__ __launch_bounds__(kThreads) void okv_enc_pack_region_kernel(PackParams P, uint64_t nb,
                                                                        uint32_t G) {
   __shared__ RegionSmem sm;
@@ -1266,14 +1281,7 @@ __global__ __launch_bounds__(kThreads) void okv_enc_pack_region_kernel(PackParam
   const uint32_t nrow = uint32_t(sm.bfirst[g] - R0);
   for (uint32_t i = threadIdx.x; i < nrow; i += kThreads) {
     const uint64_t r = R0 + i;
-    uint32_t lo = 0, hi = g;  // block of row r: bfirst[lo] <= r < bfirst[hi]
-    while (hi - lo > 1) {
-      const uint32_t m = (lo + hi) >> 1;
-      if (sm.bfirst[m] <= r)
-        lo = m;
-      else
-        hi = m;
-    }
+    const uint32_t lo = region_block(sm.bfirst, g, r);
     sm.out[i] = sm.brel[lo] + Pg(P.pl, P.tp, int64_t(r) - 1) - sm.bbase[lo];
     sm.ko[i] = P.key_off[r];
     sm.kl[i] = P.key_len[r];
@@ -1298,13 +1306,9 @@ __global__ __launch_bounds__(kThreads) void okv_enc_pack_region_kernel(PackParam
     return r;
   };
   uint8_t* dst = P.seg + O0;
-  if (V == 1) return;
   for (uint32_t q = threadIdx.x; q < nq; q += kThreads) {
     const uint64_t pos = uint64_t(q) << 4;
-    if (V == 2)
-      *reinterpret_cast<uint4*>(dst + pos) = make_uint4(sm.qrow[q], 0, 0, 0);
-    else
-      *reinterpret_cast<uint4*>(dst + pos) = assemble_chunk(P, pos, sm.qrow[q], nrow, rec);
+    *reinterpret_cast<uint4*>(dst + pos) = assemble_chunk(P, pos, sm.qrow[q], nrow, rec);
   }
 }
 
@@ -1376,65 +1380,84 @@ __device__ __forceinline__ void lds_copy_field(uint32_t* img, uint32_t d, const 
   }
 }
 
-template <uint32_t IMG, int V = 0, bool kMeta = false, uint32_t NT = kThreads>  // V: diagnostic ablation (OKV_ENC_VARIANT 4: no hash,
-                                   // 5: headers only, 6: loads without LDS writes;
-                                   // 7: row positions by a workgroup scan, no pl reads (the product);
-                                   // 8: 7 with registers capped for 8 waves)
-                                   // kMeta (ablation, OKV_ENC_META_FUSED=1): the meta index
-                                   // entries written here too (measured slower: 5.16-5.30
-                                   // vs 4.31-4.39 ms pack, + 0.23 ms meta kernel saved)
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(V == 8 ? 8 : 1)))
-void okv_enc_pack_lds_kernel(PackParams P, uint64_t nb, uint32_t G) {
-  // V == 7, the product form (70 registers, 7 waves per SIMD); V == 8
-  // (ablation) is the same code capped at 64 registers for 8 waves: it spills
-  // (9 registers) and measured 4.88 vs 3.85 ms (profiles/r3/r3g/ablate_enc.log)
-  // V == 9 (ablation): 7 with the block hashes computed by wave 0 from the
-  // raw image while waves 1-3 store it (no second barrier, no precompute)
-  constexpr bool kOverlap = V == 9;
-  constexpr int VL = (V == 8 || V == 9) ? 7 : V;
-  __shared__ uint4 img4[IMG / 16];
-  __shared__ uint64_t bfirst[kMaxRegion + 1], brel[kMaxRegion], bbase[kMaxRegion];
-  __shared__ uint32_t slim[kMaxRegion], blen[kMaxRegion];  // end of whole stripes, BlockSize
-  __shared__ uint64_t borig[kMaxRegion], bcsz[kMaxRegion], bmoff[kMaxRegion];
-  __shared__ uint32_t bfkl[kMaxRegion];  // key length of each block's first row (its FirstKey)
-  uint32_t* img = reinterpret_cast<uint32_t*>(img4);
-  const uint64_t k0 = uint64_t(blockIdx.x) * G;
-  const uint32_t g = uint32_t(std::min<uint64_t>(G, nb - k0));
+// One record into the image at byte d: the 6 header bytes, the key (at ka + ko),
+// the value (at va + vo).
+__device__ __forceinline__ void lds_put_record(uint32_t* img, uint32_t d, const uint8_t* ka,
+                                               uint64_t ko, uint32_t kl, const uint8_t* va,
+                                               uint64_t vo, uint32_t vl) {
+  if (kl <= 64 && vl <= 64) {  // all source lines of the record in flight at once
+    const Lines5 K = load_lines5(ka + ko, kl);
+    const Lines5 Vl = load_lines5(va + vo, vl);
+    lds_or16(img, d, make_uint4(kl | (vl << 16), vl >> 16, 0, 0));
+    lds_put5(img, d + 6, K, kl);
+    if (vl) lds_put5(img, d + 6 + kl, Vl, vl);
+  } else {
+    lds_or16(img, d, make_uint4(kl | (vl << 16), vl >> 16, 0, 0));
+    lds_copy_field(img, d + 6, ka + ko, kl);
+    if (vl) lds_copy_field(img, d + 6 + kl, va + vo, vl);
+  }
+}
+
+struct __align__(16) LdsPackSmem {
+  uint4 img4[kImage / 16];          // the region's blocks, as the segment holds them
+  uint64_t bfirst[kMaxRegion + 1];  // each block's first row; [g] = the row after the region
+  uint64_t brel[kMaxRegion];        // block offset - region offset
+  uint64_t bbase[kMaxRegion];       // record bytes of the region's blocks before this one
+  uint32_t slim[kMaxRegion];        // image offset where the block's whole 32-byte stripes end
+  uint32_t blen[kMaxRegion];        // BlockSize
+  uint32_t wt[2][kThreads / 64];    // per-wave record-size totals of a pass, by pass parity
+};
+
+struct LdsPackRegion {  // (workgroup-uniform)
+  uint64_t k0;  // the region's first block
+  uint32_t g;   // its blocks (<= kMaxRegion)
+  uint64_t O0;  // segment offset of block k0
+  uint32_t nq;  // 16-byte chunks of the image
+};
+
+// Open the region: the block tables and a zeroed image (the padding).
+__device__ __forceinline__ LdsPackRegion pack_open(const PackParams& P, uint64_t nb, uint32_t G,
+                                                   LdsPackSmem& sm) {
+  LdsPackRegion rg;
+  rg.k0 = uint64_t(blockIdx.x) * G;
+  rg.g = uint32_t(std::min<uint64_t>(G, nb - rg.k0));
   // one HBM trip for everything that needs only the region's index: its
   // blocks' first rows and descriptors (clamped addresses, issued together;
   // round 4 waited for the region's extent before loading first[])
-  const uint64_t frow = P.first[k0 + std::min<uint32_t>(threadIdx.x, g)];
+  const uint64_t frow = P.first[rg.k0 + std::min<uint32_t>(threadIdx.x, rg.g)];
   Desc dt{};
-  if (threadIdx.x < 64) dt = P.desc[k0 + std::min<uint32_t>(threadIdx.x, g - 1)];
-  const uint64_t O0 = P.desc[k0].offset;
-  const Desc dl = P.desc[k0 + g - 1];
-  const uint32_t nq = uint32_t((dl.offset + dl.block_size - O0) >> 4);
-  if (threadIdx.x <= g) bfirst[threadIdx.x] = frow;
-  for (uint32_t q = threadIdx.x; q < nq; q += NT) img4[q] = make_uint4(0, 0, 0, 0);
+  if (threadIdx.x < 64) dt = P.desc[rg.k0 + std::min<uint32_t>(threadIdx.x, rg.g - 1)];
+  rg.O0 = P.desc[rg.k0].offset;
+  const Desc dl = P.desc[rg.k0 + rg.g - 1];
+  rg.nq = uint32_t((dl.offset + dl.block_size - rg.O0) >> 4);
+  if (threadIdx.x <= rg.g) sm.bfirst[threadIdx.x] = frow;
+  for (uint32_t q = threadIdx.x; q < rg.nq; q += kThreads) sm.img4[q] = make_uint4(0, 0, 0, 0);
   if (threadIdx.x < 64) {  // g <= kMaxRegion = 64: wave 0
     const uint32_t t = threadIdx.x;
     uint64_t orig = 0;
-    if (t < g) {  // (with first[], and the meta entry offset)
-      brel[t] = dt.offset - O0;
-      blen[t] = uint32_t(dt.block_size);
-      slim[t] = uint32_t(dt.offset - O0 + (dt.block_size & ~uint64_t(31)));
+    if (t < rg.g) {
+      sm.brel[t] = dt.offset - rg.O0;
+      sm.blen[t] = uint32_t(dt.block_size);
+      sm.slim[t] = uint32_t(dt.offset - rg.O0 + (dt.block_size & ~uint64_t(31)));
       orig = dt.original_size;
-      if constexpr (kMeta) {
-        borig[t] = orig;
-        bcsz[t] = dt.compressed_size;
-        bmoff[t] = P.moff[k0 + t];
-      }
     }
     // each block's start in the region's row stream: the OriginalSizes before it
     const uint64_t incl = wave_incl_scan(orig, int(t));
-    if (t < g) bbase[t] = incl - orig;
+    if (t < rg.g) sm.bbase[t] = incl - orig;
   }
-  __shared__ uint32_t s_wt[2][NT / 64];  // VL == 7: per-wave record-size totals
   __syncthreads();
-  const uint64_t R0 = bfirst[0], R1 = bfirst[g];
-  const uint64_t abs0 = VL == 7 ? 0 : Pg(P.pl, P.tp, int64_t(R0) - 1);
-  uint32_t carry = 0;  // VL == 7: image bytes of the rows before this pass
-  for (uint64_t base = R0; base < R1; base += NT) {  // uniform trip count (VL == 7 barriers)
+  return rg;
+}
+
+// Fill the image: one row per lane and pass.  A row's place in the region's
+// row stream is the exclusive scan of the record sizes in row order (no read
+// of the row prefix); its block's offset and base turn that into an image byte.
+__device__ __forceinline__ void pack_fill(const PackParams& P, const LdsPackRegion& rg,
+                                          LdsPackSmem& sm) {
+  uint32_t* img = reinterpret_cast<uint32_t*>(sm.img4);
+  const uint64_t R0 = sm.bfirst[0], R1 = sm.bfirst[rg.g];
+  uint32_t carry = 0;  // image bytes of the rows before this pass
+  for (uint64_t base = R0; base < R1; base += kThreads) {  // uniform trip count (the barrier)
     const uint64_t r = base + threadIdx.x;
     const bool live = r < R1;
     uint32_t kl = 0, vl = 0;
@@ -1445,183 +1468,133 @@ void okv_enc_pack_lds_kernel(PackParams P, uint64_t nb, uint32_t G) {
       ko = P.key_off[r];
       vo = P.val_off[r];
     }
-    uint32_t srel = 0;  // VL == 7: region-relative start of record r's row stream
-    if constexpr (VL == 7) {
-      // exclusive scan of the record sizes in row order (< IMG bytes: u32)
-      const uint32_t sz = live ? 6 + kl + vl : 0u;
-      const uint32_t inc = wave_scan_dpp(sz);
-      const uint32_t wave = threadIdx.x >> 6, par = uint32_t((base - R0) / NT) & 1;
-      if ((threadIdx.x & 63) == 63) s_wt[par][wave] = inc;
-      __syncthreads();
-      uint32_t before = carry, tot = 0;
+    const uint32_t sz = live ? 6 + kl + vl : 0u;  // (a region is < kImage bytes: u32)
+    const uint32_t inc = wave_scan_dpp(sz);
+    const uint32_t wave = threadIdx.x >> 6, par = uint32_t((base - R0) / kThreads) & 1;
+    if ((threadIdx.x & 63) == 63) sm.wt[par][wave] = inc;
+    __syncthreads();
+    uint32_t before = carry, tot = 0;
 #pragma unroll
-      for (uint32_t w = 0; w < NT / 64; ++w) {
-        const uint32_t t = s_wt[par][w];
-        before += w < wave ? t : 0u;
-        tot += t;
-      }
-      srel = before + inc - sz;
-      carry += tot;
+    for (uint32_t w = 0; w < kThreads / 64; ++w) {
+      const uint32_t t = sm.wt[par][w];
+      before += w < wave ? t : 0u;
+      tot += t;
     }
+    const uint32_t srel = before + inc - sz;  // region-relative start in the row stream
+    carry += tot;
     if (!live) continue;
-    uint32_t lo = 0, hi = g;  // block of row r
-    while (hi - lo > 1) {
-      const uint32_t m = (lo + hi) >> 1;
-      if (bfirst[m] <= r)
-        lo = m;
-      else
-        hi = m;
-    }
-    if (kMeta && r == bfirst[lo]) bfkl[lo] = kl;
-    // (the other arms: the row's absolute row-stream position from the row
-    // prefix, less the block's -- the region's first row's absolute position
-    // abs0 plus the block's region-relative base)
-    const uint32_t d = VL == 7 ? uint32_t(brel[lo] + srel - (bbase[lo] - bbase[0]))
-                              : uint32_t(brel[lo] + Pg(P.pl, P.tp, int64_t(r) - 1) -
-                                         (abs0 + bbase[lo]));
-    if (VL == 5) {
-      lds_or16(img, d, make_uint4(kl | (vl << 16), vl >> 16, 0, 0));
-    } else if (VL == 6 && kl <= 64 && vl <= 64) {
-      const Lines5 K = load_lines5(P.key_arena + ko, kl);
-      const Lines5 Vl = load_lines5(P.val_arena + vo, vl);
-      uint32_t x = 0;
-#pragma unroll
-      for (int t = 0; t < 5; ++t) x ^= K.l[t].x ^ K.l[t].w ^ Vl.l[t].y ^ Vl.l[t].z;
-      lds_or16(img, d, make_uint4(kl | (vl << 16), vl >> 16, x == 0x9e3779b9u ? 1u : 0u, 0));
-    } else if (kl <= 64 && vl <= 64) {  // all source lines of the record in flight at once
-      const Lines5 K = load_lines5(P.key_arena + ko, kl);
-      const Lines5 Vl = load_lines5(P.val_arena + vo, vl);
-      lds_or16(img, d, make_uint4(kl | (vl << 16), vl >> 16, 0, 0));
-      lds_put5(img, d + 6, K, kl);
-      if (vl) lds_put5(img, d + 6 + kl, Vl, vl);
-    } else {
-      lds_or16(img, d, make_uint4(kl | (vl << 16), vl >> 16, 0, 0));
-      lds_copy_field(img, d + 6, P.key_arena + ko, kl);
-      if (vl) lds_copy_field(img, d + 6 + kl, P.val_arena + vo, vl);
-    }
+    const uint32_t b = region_block(sm.bfirst, rg.g, r);
+    const uint32_t d = uint32_t(sm.brel[b] + srel - (sm.bbase[b] - sm.bbase[0]));
+    lds_put_record(img, d, P.key_arena, ko, kl, P.val_arena, vo, vl);
   }
   __syncthreads();
-  uint4* dst = reinterpret_cast<uint4*>(P.seg + O0);
-  if constexpr (kOverlap) {
-    if (threadIdx.x >= 64) {
-      for (uint32_t q = threadIdx.x - 64; q < nq; q += NT - 64) dst[q] = img4[q];
-      return;
-    }
-  } else {
-  // Store the image; each 16 bytes lying in whole 32-byte stripes of its block
-  // are then replaced in place (same lane, so no barrier between) by their two
-  // XXH64 round inputs x * PRIME64_2, computed by all 256 lanes: the four
-  // hashing lanes per block are left with add, rotate, multiply per round.
-  // (non-temporal stores: the segment is written once and read by no kernel
-  // of this encode -- pack 4.53-4.55 -> 4.44-4.47 ms, profiles/r5/session/
-  // enc_pack_nt_ab.log; non-temporal arena loads as well: 4.82-4.84 ms)
-  for (uint32_t q = threadIdx.x; q < nq; q += NT) {
-    const uint4 v = img4[q];
+}
+
+// Store the image; each 16 bytes lying in whole 32-byte stripes of its block
+// are then replaced in place (same lane, so no barrier between) by their two
+// XXH64 round inputs x * PRIME64_2, computed by all 256 lanes: the four
+// hashing lanes per block are left with add, rotate, multiply per round.
+// (non-temporal stores: the segment is written once and read by no kernel
+// of this encode -- pack 4.53-4.55 -> 4.44-4.47 ms, profiles/r5/session/
+// enc_pack_nt_ab.log; non-temporal arena loads as well: 4.82-4.84 ms)
+__device__ __forceinline__ void pack_store(const PackParams& P, const LdsPackRegion& rg,
+                                           LdsPackSmem& sm) {
+  uint4* dst = reinterpret_cast<uint4*>(P.seg + rg.O0);
+  for (uint32_t q = threadIdx.x; q < rg.nq; q += kThreads) {
+    const uint4 v = sm.img4[q];
     store_nt16(&dst[q], v);
-    if (VL == 4) continue;
     const uint32_t p = q << 4;
-    uint32_t lo = 0, hi = g;  // block holding byte p
-    while (hi - lo > 1) {
-      const uint32_t m = (lo + hi) >> 1;
-      if (uint32_t(brel[m]) <= p)
-        lo = m;
-      else
-        hi = m;
-    }
+    const uint32_t b = region_block(sm.brel, rg.g, p);
+    const uint32_t boff = uint32_t(sm.brel[b]);
     // the block's first kFkStride bytes (its first record's header and key),
     // as stored, for the meta kernel -- which otherwise reads the block's first
     // line from the segment, one scattered line per block (blocks start
     // 16-byte aligned in the image: whole chunks; BlockSize >= 48 here)
-    if (P.fk && p < uint32_t(brel[lo]) + kFkStride && p + 16 <= uint32_t(brel[lo]) + blen[lo])
-      *reinterpret_cast<uint4*>(P.fk + (k0 + lo) * kFkStride + (p - uint32_t(brel[lo]))) = v;
-    if constexpr (kMeta) {  // FirstKey bytes of the block's meta entry (block_stat.go:31-33)
-      const uint32_t ks = uint32_t(brel[lo]) + 6, ke = ks + bfkl[lo];
-      const uint32_t a0 = max(p, ks), a1 = min(p + 16, ke);
-      uint8_t* m = P.meta + bmoff[lo] + 2 - ks;
-      for (uint32_t x = a0; x < a1; ++x) m[x] = uint8_t(dword_at(v, x - p));
-    }
-    if (p + 16 <= slim[lo]) {
+    if (P.fk && p < boff + kFkStride && p + 16 <= boff + sm.blen[b])
+      *reinterpret_cast<uint4*>(P.fk + (rg.k0 + b) * kFkStride + (p - boff)) = v;
+    if (p + 16 <= sm.slim[b]) {
       const uint64_t a = ((uint64_t(v.y) << 32) | v.x) * XP2;
       const uint64_t c = ((uint64_t(v.w) << 32) | v.z) * XP2;
-      img4[q] = make_uint4(uint32_t(a), uint32_t(a >> 32), uint32_t(c), uint32_t(c >> 32));
+      sm.img4[q] = make_uint4(uint32_t(a), uint32_t(a >> 32), uint32_t(c), uint32_t(c >> 32));
     }
   }
-  if (VL == 4) return;
   // only LDS has to be ordered here (a __syncthreads would also wait for the
   // image's global stores)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  }
-  // BlockStat.Hash = XXH64 of the padded block (segment_writer.go:185), from
-  // the image: four lanes per block own XXH64's four accumulators.
-  if (threadIdx.x < 4 * g) {
-    const uint32_t b = threadIdx.x >> 2, q = threadIdx.x & 3;
-    const uint32_t boff = uint32_t(brel[b]);
-    const uint64_t len = blen[b];
-    const uint64_t* w64 = reinterpret_cast<const uint64_t*>(img4) + (boff >> 3);
-    uint64_t acc = (q == 0) ? XP1 + XP2 : (q == 1) ? XP2 : (q == 2) ? 0 : 0 - XP1;
-    const uint32_t nstripe = uint32_t(len / 32);
-    uint32_t st = 0;
-    for (; st + 8 <= nstripe; st += 8) {  // 8 LDS reads ahead of the round chain
-      uint64_t x[8];
+}
+
+// BlockStat.Hash = XXH64 of the padded block (segment_writer.go:185), from
+// the image: four lanes per block own XXH64's four accumulators.
+__device__ __forceinline__ void pack_hash(const PackParams& P, const LdsPackRegion& rg,
+                                          const LdsPackSmem& sm) {
+  if (threadIdx.x >= 4 * rg.g) return;
+  const uint32_t b = threadIdx.x >> 2, q = threadIdx.x & 3;
+  const uint32_t boff = uint32_t(sm.brel[b]);
+  const uint64_t len = sm.blen[b];
+  const uint64_t* w64 = reinterpret_cast<const uint64_t*>(sm.img4) + (boff >> 3);
+  uint64_t acc = (q == 0) ? XP1 + XP2 : (q == 1) ? XP2 : (q == 2) ? 0 : 0 - XP1;
+  const uint32_t nstripe = uint32_t(len / 32);
+  uint32_t st = 0;
+  for (; st + 8 <= nstripe; st += 8) {  // 8 LDS reads ahead of the round chain
+    uint64_t x[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = w64[4 * (st + u) + q];
+    for (int u = 0; u < 8; ++u) x[u] = w64[4 * (st + u) + q];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) acc = kOverlap ? xround(acc, x[u]) : xround_pre(acc, x[u]);
-    }
-    for (; st < nstripe; ++st)
-      acc = kOverlap ? xround(acc, w64[4 * st + q]) : xround_pre(acc, w64[4 * st + q]);
-    const int lane = threadIdx.x & 63;
-    const uint64_t a1 = __shfl(acc, (lane & ~3) + 1, 64);
-    const uint64_t a2 = __shfl(acc, (lane & ~3) + 2, 64);
-    const uint64_t a3 = __shfl(acc, (lane & ~3) + 3, 64);
-    if (q == 0) {
-      uint64_t h;
-      if (len >= 32) {
-        h = rotl64(acc, 1) + rotl64(a1, 7) + rotl64(a2, 12) + rotl64(a3, 18);
-        h = (h ^ xround(0, acc)) * XP1 + XP4;
-        h = (h ^ xround(0, a1)) * XP1 + XP4;
-        h = (h ^ xround(0, a2)) * XP1 + XP4;
-        h = (h ^ xround(0, a3)) * XP1 + XP4;
-      } else {
-        h = XP5;
-      }
-      h += len;
-      const uint8_t* bytes = reinterpret_cast<const uint8_t*>(img4) + boff;
-      uint32_t t = nstripe * 32;
-      for (; t + 8 <= len; t += 8) {
-        h ^= xround(0, w64[t / 8]);
-        h = rotl64(h, 27) * XP1 + XP4;
-      }
-      if (t + 4 <= len) {
-        const uint32_t v = uint32_t(bytes[t]) | (uint32_t(bytes[t + 1]) << 8) |
-                           (uint32_t(bytes[t + 2]) << 16) | (uint32_t(bytes[t + 3]) << 24);
-        h ^= uint64_t(v) * XP1;
-        h = rotl64(h, 23) * XP2 + XP3;
-        t += 4;
-      }
-      for (; t < len; ++t) {
-        h ^= uint64_t(bytes[t]) * XP5;
-        h = rotl64(h, 11) * XP1;
-      }
-      h ^= h >> 33;
-      h *= XP2;
-      h ^= h >> 29;
-      h *= XP3;
-      h ^= h >> 32;
-      P.hash[k0 + b] = h;
-      if constexpr (kMeta) {  // the rest of the entry: u16 len(FirstKey), then 5 x u64 (:27-42)
-        uint8_t* m = P.meta + bmoff[b];
-        const uint32_t kl = bfkl[b];
-        put_le(m, kl, 2);
-        m += 2 + kl;
-        put_le(m, O0 + boff, 8);
-        put_le(m + 8, len, 8);
-        put_le(m + 16, borig[b], 8);
-        put_le(m + 24, bcsz[b], 8);
-        put_le(m + 32, h, 8);
-      }
-    }
+    for (int u = 0; u < 8; ++u) acc = xround_pre(acc, x[u]);
   }
+  for (; st < nstripe; ++st) acc = xround_pre(acc, w64[4 * st + q]);
+  const int lane = threadIdx.x & 63;
+  const uint64_t a1 = __shfl(acc, (lane & ~3) + 1, 64);
+  const uint64_t a2 = __shfl(acc, (lane & ~3) + 2, 64);
+  const uint64_t a3 = __shfl(acc, (lane & ~3) + 3, 64);
+  if (q != 0) return;
+  uint64_t h;
+  if (len >= 32) {
+    h = rotl64(acc, 1) + rotl64(a1, 7) + rotl64(a2, 12) + rotl64(a3, 18);
+    h = (h ^ xround(0, acc)) * XP1 + XP4;
+    h = (h ^ xround(0, a1)) * XP1 + XP4;
+    h = (h ^ xround(0, a2)) * XP1 + XP4;
+    h = (h ^ xround(0, a3)) * XP1 + XP4;
+  } else {
+    h = XP5;
+  }
+  h += len;
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(sm.img4) + boff;
+  uint32_t t = nstripe * 32;  // (the tail past the whole stripes holds the stored bytes)
+  for (; t + 8 <= len; t += 8) {
+    h ^= xround(0, w64[t / 8]);
+    h = rotl64(h, 27) * XP1 + XP4;
+  }
+  if (t + 4 <= len) {
+    const uint32_t v = uint32_t(bytes[t]) | (uint32_t(bytes[t + 1]) << 8) |
+                       (uint32_t(bytes[t + 2]) << 16) | (uint32_t(bytes[t + 3]) << 24);
+    h ^= uint64_t(v) * XP1;
+    h = rotl64(h, 23) * XP2 + XP3;
+    t += 4;
+  }
+  for (; t < len; ++t) {
+    h ^= uint64_t(bytes[t]) * XP5;
+    h = rotl64(h, 11) * XP1;
+  }
+  h ^= h >> 33;
+  h *= XP2;
+  h ^= h >> 29;
+  h *= XP3;
+  h ^= h >> 32;
+  P.hash[rg.k0 + b] = h;
+}
+
+// The product's pack kernel (70 registers, 7 waves per SIMD).  Its measured
+// alternatives -- other image sizes and thread counts, positions from the row
+// prefix, fused meta entries, hashing beside the stores -- are
+// okv_enc_pack_lds_arm_kernel in okv_encode_ablate_pack.inc.
+__global__ __launch_bounds__(kThreads) void okv_enc_pack_lds_kernel(PackParams P, uint64_t nb,
+                                                                    uint32_t G) {
+  __shared__ LdsPackSmem sm;
+  const LdsPackRegion rg = pack_open(P, nb, G, sm);
+  pack_fill(P, rg, sm);
+  pack_store(P, rg, sm);
+  pack_hash(P, rg, sm);
 }
 
 // E10 (general DataBlockSize, not a multiple of 16): one byte per lane.
@@ -2111,28 +2084,19 @@ uint64_t pack_region_blocks(const Plan& pl) {
                              uint64_t(kMaxChunks) * 16 / std::max<uint64_t>(pl.bmax, 1)});
 }
 
-// The product's pack launch (E10-E11): record-major LDS assembly + block hashes
-// for small records, chunk-major regions for large ones, a per-block kernel
-// or a byte kernel when the segment is not 16-byte aligned.  *hashed: the
-// launch also wrote the block hashes.
-int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
-             const Plan& pl, uint8_t* seg, const PackParams& pp, bool* hashed, bool* fk_done) {
-  // record-major LDS assembly pays off for small records (most chunks would
-  // mix fields); large records take the chunk-major kernels, which read the
-  // row prefix (E1-E2; a single-pass plan does not write it)
-  const bool aligned = o.block_size % 16 == 0 && (reinterpret_cast<uintptr_t>(seg) & 15) == 0;
-  const uint64_t GL = std::min<uint64_t>(kMaxRegion, kImage / std::max<uint64_t>(pl.bmax, 1));
+bool pack_aligned(const okv_encode_opts& o, const uint8_t* seg) {
+  return o.block_size % 16 == 0 && (reinterpret_cast<uintptr_t>(seg) & 15) == 0;
+}
+
+// The pack launch for large records (E10): chunk-major regions, a per-block
+// kernel for blocks larger than a region, or a byte kernel when the segment
+// is not 16-byte aligned.  The block hashes are left to okv_hash_kernel.
+int pack_large(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
+               const Plan& pl, uint8_t* seg, const PackParams& pp) {
+  const bool aligned = pack_aligned(o, seg);
   const uint64_t G = pack_region_blocks(pl);
   int rc;
-  if (aligned && GL >= 1 && pl.avg_rec <= 512) {
-    // small records: record-major LDS assembly, the block hashes and FirstKeys
-    hipLaunchKernelGGL((okv_enc_pack_lds_kernel<kImage, 7>), dim3(ceil_div(pl.nb, GL)),
-                       dim3(kThreads), 0, ctx->stream, pp, pl.nb, uint32_t(GL));
-    *hashed = true;
-    *fk_done = pp.fk != nullptr;
-    return OKV_OK;
-  }
-  // the other kernels read the row prefix: computed here (the tile cut writes
+  // these kernels read the row prefix: computed here (the tile cut writes
   // none), so the parameters take its buffers after the call
   if ((rc = enc_row_prefix(ctx, e, R, o.threshold_bytes))) return rc;
   PackParams q = pp;
@@ -2144,7 +2108,7 @@ int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
   if (!e->have_pl || !q.pl || !q.tp || e->pl.capacity() < R.n)
     return set_err(ctx, OKV_E_ARG, "enc_pack: row prefix missing for the chunk-major kernels");
   if (aligned && G >= 1) {  // large records: chunk-major regions
-    hipLaunchKernelGGL(okv_enc_pack_region_kernel<0>, dim3(ceil_div(pl.nb, G)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(okv_enc_pack_region_kernel, dim3(ceil_div(pl.nb, G)), dim3(kThreads), 0,
                        ctx->stream, q, pl.nb, uint32_t(G));
   } else if (aligned) {
     hipLaunchKernelGGL(okv_enc_pack_kernel, dim3(uint32_t(pl.nb)), dim3(kThreads), 0,
@@ -2154,6 +2118,22 @@ int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
     hipLaunchKernelGGL(okv_enc_pack_bytes_kernel, dim3(std::max<uint32_t>(g, 1)),
                        dim3(kThreads), 0, ctx->stream, q, pl.nb, pl.data_bytes);
   }
+  return OKV_OK;
+}
+
+// The product's pack launch (E10-E11).  Record-major LDS assembly pays off for
+// small records (most chunks would mix fields): one launch writes the blocks,
+// their hashes (*hashed) and their FirstKeys (*fk_done).  Large records take
+// pack_large.
+int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
+             const Plan& pl, uint8_t* seg, const PackParams& pp, bool* hashed, bool* fk_done) {
+  const uint64_t GL = std::min<uint64_t>(kMaxRegion, kImage / std::max<uint64_t>(pl.bmax, 1));
+  if (!(pack_aligned(o, seg) && GL >= 1 && pl.avg_rec <= 512))
+    return pack_large(ctx, e, R, o, pl, seg, pp);
+  hipLaunchKernelGGL(okv_enc_pack_lds_kernel, dim3(ceil_div(pl.nb, GL)), dim3(kThreads), 0,
+                     ctx->stream, pp, pl.nb, uint32_t(GL));
+  *hashed = true;
+  *fk_done = pp.fk != nullptr;
   return OKV_OK;
 }
 

@@ -412,6 +412,87 @@ def test_tile_cut_boundaries_and_general_path(enc, T):
         assert got.meta() == meta
 
 
+def _keyed(i, kl, rng):
+    """A kl-byte key that starts with the row number (as far as it fits)."""
+    return (b"%06d" % i + bytes(rng.getrandbits(8) for _ in range(kl)))[:kl]
+
+
+def _pack_edge_rows(name):
+    """(rows, threshold, block size, blocks) of one test_pack_image_edges case."""
+    rng = random.Random(name)
+    if name == "one_row":
+        return [(b"k", b"")], 3584, 4096, 1
+    if name == "many_rows":
+        # 2 340 records of 7 bytes fill a block to 16 380 bytes (T), padded to one
+        # 16 384-byte image: one block per region, ten 256-row passes of the scan
+        return [(bytes([33 + i % 90]), b"") for i in range(2 * 2340 + 1000)], 16380, 16384, 3
+    if name == "many_blocks":
+        # D = 16, T = 8: a record of 8 bytes or more closes its block, a 7-byte
+        # one waits for the next record: raw lengths 9..47, blocks of 16, 32 and
+        # 48 bytes, 64 blocks per region, the 129th alone in the third
+        rows = []
+        for b in range(128):
+            size = (9, 15, 16, 20, 31, 32, 40, 41)[b % 8]  # record bytes, one per block
+            if b % 5 == 4:
+                rows.append((bytes([65 + b % 26]), b""))  # a 7-byte record opens the block
+            kl = rng.randint(1, size - 6)
+            rows.append((_keyed(len(rows), kl, rng), bytes(rng.getrandbits(8)
+                                                           for _ in range(size - 6 - kl))))
+        rows.append((b"z", b""))  # the last block stays open for Close
+        return rows, 8, 16, 129
+    if name in ("fk_d48", "fk_d64"):
+        # first keys of 1..59 bytes (58 is the most the pack kernel keeps), blocks
+        # from 48 bytes (shorter than a kept line) up
+        rows = []
+        for i in range(400):
+            kl = 59 if i == 399 else rng.choice((1, 30, 57, 58, 59))  # (the last closes its block)
+            rows.append((_keyed(i, kl, rng), bytes(rng.getrandbits(8)
+                                                   for _ in range(rng.randint(0, 20)))))
+        rows.append((b"z", b""))  # the last block stays open for Close
+        return rows, 40, 48 if name == "fk_d48" else 64, None
+    if name == "copy_64_65":
+        # keys of 64 and 65 bytes with values of 0, 64, 65 and 200 bytes (the
+        # one-shot copy takes fields of <= 64 bytes) between random neighbours,
+        # which put them at every arena and image alignment
+        rows = []
+        for rep in range(6):
+            for kl in (64, 65):
+                for vl in (0, 64, 65, 200):
+                    for k, v in ((rng.randint(1, 70), rng.randint(0, 210)), (kl, vl)):
+                        rows.append((_keyed(len(rows), k, rng),
+                                     bytes(rng.getrandbits(8) for _ in range(v))))
+        return rows, 3584, 4096, None
+    if name in ("rec_512", "rec_513"):
+        # uniform records: 512 bytes is the largest mean the LDS kernel takes,
+        # 513 goes to the chunk-major region kernel
+        vl = (512 if name == "rec_512" else 513) - 6 - 16
+        return [(_keyed(i, 16, rng), bytes(rng.getrandbits(8) for _ in range(vl)))
+                for i in range(100)], 3584, 4096, 15
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize("name", ["one_row", "many_rows", "many_blocks", "fk_d48", "fk_d64",
+                                  "copy_64_65", "rec_512", "rec_513"])
+def test_pack_image_edges(enc, name):
+    """The smallest shapes at which each phase of okv_enc_pack_lds_kernel can go
+    wrong -- one row; > 2 000 rows per region (the scan's carry over ten
+    passes); 64 blocks of 16..48 bytes per region and a last region of one
+    block (no stripes, the hash's 8-byte tail, blocks shorter than a kept
+    FirstKey line); FirstKeys of 58 and 59 bytes at DataBlockSize 48 and 64;
+    fields of 64 and 65 bytes; mean records of 512 and 513 bytes, either side
+    of the route to the region kernel -- each whole segment (blocks, and in
+    its meta block their hashes and FirstKeys) byte-equal to the oracle
+    writer's."""
+    rows, T, D, nb = _pack_edge_rows(name)
+    rc, want, meta = oracle_segment(rows, T, D)
+    assert rc == 0
+    got = enc.encode(rows, T, D)
+    if nb is not None:
+        assert got.n_blocks == nb
+    assert got.seg.tobytes() == want
+    assert got.meta() == meta
+
+
 def _sized_rows(seed, n, vmax):
     """n rows of 8-byte keys and 0..vmax-byte values, built from one random buffer."""
     rng = np.random.default_rng(seed)

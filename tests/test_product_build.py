@@ -22,7 +22,9 @@ ABLATION_ONLY = [b"okv_value_sweep_kernel", b"okv_rows_kernel", b"okv_gather_sta
                  # round 4's measured-and-not-kept forms
                  b"okv_decode_stream_kernel", b"okv_enc_plan_kernel", b"fused_prefix_lookback",
                  # round 6's
-                 b"okv_group_kernel", b"okv_tile_kernel_skip"]
+                 b"okv_group_kernel", b"okv_tile_kernel_skip",
+                 # the encode pack kernels' measured arms
+                 b"okv_enc_pack_lds_arm_kernel", b"okv_enc_pack_region_arm_kernel"]
 KNOBS = [b"OKV_GATHER_THREADS", b"OKV_GATHER_GRID", b"OKV_DECODE_FUSED", b"OKV_GATHER_STAGED",
          b"OKV_VALUE_SWEEP", b"OKV_TILE", b"OKV_ZSTD_GENERAL", b"OKV_ZSTD_PROF",
          b"OKV_ENC_VARIANT", b"OKV_ENC_IMAGE", b"OKV_DECODE_PIECES", b"OKV_DECODE_STREAM",
@@ -77,7 +79,8 @@ def test_product_source_holds_only_product_kernels():
     enc = open(os.path.join(ROOT, "objectkv_amd", "csrc", "okv_encode.hip")).read()
     for name in ("okv_enc_plan_kernel", "enc_plan_fast"):
         assert not re.search(r"\b" + name + r"\s*\([^;]*\)\s*\{", enc), name
-    for inc_name in ("okv_encode_ablate.inc", "okv_encode_ablate_host.inc"):
+    for inc_name in ("okv_encode_ablate.inc", "okv_encode_ablate_host.inc",
+                     "okv_encode_ablate_pack.inc"):
         inc = enc.index(f'#include "{inc_name}"')
         assert enc.rfind("#ifdef OKV_ABLATE", 0, inc) > enc.rfind("#endif", 0, inc), inc_name
 
@@ -107,7 +110,8 @@ def test_product_reads_no_environment():
 def test_ablation_build_carries_the_alternatives():
     data = _bytes(ABLATE)
     for name in (b"okv_value_sweep_kernel", b"okv_gather_staged_kernel", b"okv_tile_kernel_w7",
-                 b"okv_decode_stream_kernel", b"okv_enc_plan_kernel"):
+                 b"okv_decode_stream_kernel", b"okv_enc_plan_kernel",
+                 b"okv_enc_pack_lds_arm_kernel", b"okv_enc_pack_region_arm_kernel"):
         assert name in data, name
     for knob in [b"OKV_VALUE_SWEEP", b"OKV_TILE", b"OKV_ZSTD_PROF"] + ZSTD_REPORTS:
         assert knob in data, knob
@@ -116,6 +120,29 @@ def test_ablation_build_carries_the_alternatives():
 def _strip_comments(src):
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return re.sub(r"//[^\n]*", "", src)
+
+
+def test_pack_kernels_are_the_product_form_only():
+    """The encode pack kernels are what the product launches, nothing else:
+    one non-template symbol each in the product library, no variant parameter
+    or knob in okv_encode.hip, okv_enc_pack_lds_kernel a short sequence of
+    phases; the decode copy helpers carry no variant parameter either."""
+    data = _bytes(PRODUCT)
+    for name, mangled in ((b"okv_enc_pack_lds_kernel",
+                           b"_ZN3okv23okv_enc_pack_lds_kernelENS_10PackParamsEmj"),
+                          (b"okv_enc_pack_region_kernel",
+                           b"_ZN3okv26okv_enc_pack_region_kernelENS_10PackParamsEmj")):
+        forms = set(re.findall(rb"_ZN3okv\d+" + name + rb"[A-Za-z0-9_]*", data))
+        assert forms == {mangled}, forms
+    csrc = os.path.join(ROOT, "objectkv_amd", "csrc")
+    enc = _strip_comments(open(os.path.join(csrc, "okv_encode.hip")).read())
+    for word in ("kMeta", "kOverlap", "OKV_ENC_VARIANT", "template <int V"):
+        assert not re.search(r"\b" + word + r"\b", enc), word
+    dec = _strip_comments(open(os.path.join(csrc, "okv_decode.hip")).read())
+    assert "template <int V" not in dec
+    m = re.search(r"\n[^\n;{}]*\bokv_enc_pack_lds_kernel\s*\([^)]*\)\s*\{.*?\n\}", enc, flags=re.S)
+    assert m and "__global__" in m.group(0)
+    assert m.group(0).strip("\n").count("\n") + 1 <= 25
 
 
 def test_zstd_stage_owns_its_scratch_and_diagnostics_are_out_of_line():

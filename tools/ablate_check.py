@@ -88,19 +88,21 @@ elif arm == "enc_arms":
     # OKV_ENC_VARIANT 1, 2, 4, 5, 6 -- are diagnostics that skip work):
     # every one byte-equal to the oracle writer over many LDS regions
     enc = okv.Encoder(0)
-    for knob, val in (("OKV_ENC_VARIANT", "8"), ("OKV_ENC_VARIANT", "9"),
-                      ("OKV_ENC_VARIANT", "3"), ("OKV_ENC_IMAGE", "8192"),
-                      ("OKV_ENC_IMAGE", "12288"), ("OKV_ENC_IMAGE", "32768"),
-                      ("OKV_ENC_META_FUSED", "1")):
-        os.environ[knob] = val
+    for knobs in ({"OKV_ENC_VARIANT": "8"}, {"OKV_ENC_VARIANT": "9"}, {"OKV_ENC_VARIANT": "3"},
+                  {"OKV_ENC_IMAGE": "8192"}, {"OKV_ENC_IMAGE": "12288"},
+                  {"OKV_ENC_IMAGE": "32768"}, {"OKV_ENC_META_FUSED": "1"},
+                  {"OKV_ENC_IMAGE": "65536"},
+                  {"OKV_ENC_IMAGE": "32768", "OKV_ENC_VARIANT": "10"}):
+        os.environ.update(knobs)
         for T, vmax in ((3584, 120), (3584, 60), (9000, 60)):
             rng = random.Random(T + vmax)
             rows = TE._random_rows(rng, 30000, 8, vmax)
             rc, want, meta = TE.oracle_segment(rows, T, 4096)
             got = enc.encode(rows, T, 4096, strict_go=rc == 0)
             if rc == 0:
-                assert got.seg.tobytes() == want, (knob, val, T, vmax)
-        del os.environ[knob]
-        print(f"  {knob}={val}: parity ok", flush=True)
+                assert got.seg.tobytes() == want, (knobs, T, vmax)
+        for knob in knobs:
+            del os.environ[knob]
+        print("  " + " ".join(f"{k}={v}" for k, v in knobs.items()) + ": parity ok", flush=True)
     enc.close()
 print(f"ablation arm {arm}: parity ok")
