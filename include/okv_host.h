@@ -91,6 +91,9 @@ void okv_meta_free(okv_meta *m);
  * OKV_R_PANIC for a filter with m == 0 (Go's integer division panic). */
 int okv_meta_has_bloom(const okv_meta *m);
 int okv_meta_bloom_test(const okv_meta *m, const uint8_t *key, size_t klen);
+/* The filter's bytes as the meta block carries them (BloomFilter.WriteTo's output:
+ * the input of okv_bloom_read_from), valid until okv_meta_free; NULL without a filter. */
+const uint8_t *okv_meta_bloom_bytes(const okv_meta *m, uint64_t *len);
 
 /* ---- SegmentReader / RowIter over the GPU decode -------------------------- */
 /* A row as Go's KVPair (segment_reader.go:285-288): NULL pointer = nil slice.
@@ -122,6 +125,19 @@ int okv_reader_num_blocks(okv_reader *r, uint64_t *n); /* btree entries (unique 
  * *rows points to n rows (valid until free). */
 int okv_reader_read_block(okv_reader *r, uint64_t i, const okv_row **rows, uint64_t *n);
 int okv_reader_get_row(okv_reader *r, const uint8_t *key, size_t klen, okv_row *out); /* :362 */
+/* GetRow for n keys in one GPU call (okv_get_rows, okv_sst.h): rcs[i] and rows[i] are
+ * exactly what okv_reader_get_row gives for keys[i]; the rows stay valid until the next
+ * read call.  The first batched call uploads the storage, the block index and the bloom
+ * filter once (kept until okv_reader_close: bytes_staged grows by the storage length
+ * once, calls by one per batched call).  Keys on blocks the batched kernel does not take
+ * (BlockSize > 64 KiB), keys longer than 65535 bytes, every key when the filter is one the
+ * device probe refuses (m == 0 with k > 0, k > 4096), every key of a zstd segment (for which
+ * nothing is uploaded) and every key of a reader without a context go through
+ * okv_reader_get_row.  Returns OKV_OK; the metadata error; or OKV_R_GPU when the upload or the
+ * batched call itself fails (okv_last_error; nothing stays on the device after a failed
+ * upload).  A non-zero return is also in every rcs[i]. */
+int okv_reader_get_rows(okv_reader *r, const uint8_t *const *keys, const size_t *klens,
+                        uint64_t n, okv_row *rows, int *rcs);
 /* GetRange [start, end) (:410-475); an empty start is UnboundStart, end == {0xff} UnboundEnd.
  * Go ranges a map over the candidate blocks; this returns them in ascending FirstKey order. */
 int okv_reader_get_range(okv_reader *r, const uint8_t *start, size_t slen, const uint8_t *end,

@@ -39,7 +39,9 @@ extern "C" {
                              6: okv_point_get (GetRow's block step, one row back);
                                 still 6 with the device bloom filter (okv_bloom_*,
                                 OKV_F_BLOOM_DEVICE): purely additive -- new symbols and one
-                                new flag bit, no struct layout or behaviour change */
+                                new flag bit, no struct layout or behaviour change;
+                                still 6 with the batched GetRow (okv_index_*, okv_get_*,
+                                OKV_PATH_GET): new symbols only */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -394,6 +396,72 @@ int okv_bloom_write_to(okv_ctx *ctx, const okv_bloom *f, uint8_t *dst, uint64_t 
 uint32_t okv_bloom_last_path(const okv_bloom *f);
 
 /* ======================================================================== *
+ * Batched GetRow: SegmentReader.GetRow (segment_reader.go:362-404) for many keys
+ * against one segment in device memory, in one call.  Per key, in Go's order:
+ * the bloom probe (:371-378; a rejected key touches no block, even a corrupt
+ * one), DescendLessOrEqual over the block index for the floor block (:381-389),
+ * ReadBlockWithStat of that block in full (:392; a block whose walk fails fails
+ * the key even when an equal key sits before the bad record), then the first row
+ * with bytes.Equal(row.Key, key) (:395-403; nil equals empty).  Keys are grouped
+ * by floor block on the device, so a block is read once per call however many
+ * keys land on it.  DESIGN.md 20.
+ *
+ * okv_index is SegmentMetadata.BlockIndex on the device: google/btree built by
+ * ReplaceOrInsert in meta-block order, so of entries with an equal FirstKey the
+ * last one stays (Q9).  n_tree counts the entries that stayed, n_file those given.
+ * ======================================================================== */
+typedef struct okv_index okv_index;
+/* host pointers, meta-block order: entry i has descs[i] and the first key
+ * fk_arena[fk_off[i] .. +fk_len[i]]; n_entries == 0 is legal (every key: no block) */
+int okv_index_new(okv_ctx *ctx, const okv_block_desc *descs, const uint8_t *fk_arena,
+                  const uint64_t *fk_off, const uint16_t *fk_len, uint64_t n_entries,
+                  okv_index **out);
+void okv_index_free(okv_index *ix);
+int okv_index_info(const okv_index *ix, uint64_t *n_tree, uint64_t *n_file);
+
+#define OKV_GET_FOUND 0
+#define OKV_GET_BLOOM_NEGATIVE 1 /* ErrNoRows, "did not find row in bloom filter" (:371-378) */
+#define OKV_GET_NO_BLOCK 2       /* ErrNoRows, no index entry <= key (:387-389) */
+#define OKV_GET_NOT_IN_BLOCK 3   /* ErrNoRows, "did not find row in block" (:403) */
+#define OKV_GET_BLOCK_ERROR 4    /* blk_status[i] = OKV_BLK_EOF / _SHORT / _PANIC */
+#define OKV_GET_FALLBACK 5       /* not a block this path takes (zstd, BlockSize > 64 KiB):
+                                    use okv_decode_blocks */
+
+typedef struct okv_get_out {
+  int32_t *state;      /* [n] OKV_GET_* */
+  int32_t *blk_status; /* [n] OKV_BLK_* of the floor block (OKV_BLK_OK when none was read) */
+  uint32_t *entry;     /* [n] file index of the floor block, UINT32_MAX when none */
+  uint64_t *val_off;   /* [n] FOUND: byte offset of the value in seg (else 0) */
+  uint32_t *val_len;   /* [n] FOUND: its length, 0 <=> nil (else 0) */
+  uint64_t *val_pos;   /* [n] or NULL: offset of the value in val_arena, 16-byte aligned;
+                          keys that are not FOUND take no room */
+  uint8_t *val_arena;  /* or NULL (index only); each value is zero-padded to 16 bytes;
+                          a device arena must be 16-byte aligned */
+  uint64_t val_cap;
+  /* filled on return (also with OKV_E_CAPACITY, then val_arena is not written): */
+  uint64_t n_found, n_fallback, val_bytes, blocks_searched;
+} okv_get_out;
+
+/*
+ * seg is device memory (16-byte aligned); the kernels read inside round16(seg_bytes).
+ * keys: of okv_rows only key_arena, key_off, key_len, n_rows and key_arena_bytes are
+ * read; fewer than 2^32 keys.  bloom may be NULL (no filter: no probe).  The index and
+ * the filter belong to ctx (another context: OKV_E_ARG).  A filter with m == 0 and
+ * k > 0, or k > 4096, is OKV_E_ARG (okv_bloom_test_rows' divergences).
+ * flags: without OKV_F_DEVICE_PTRS the key arrays and every output are host memory
+ * (staged; the call synchronises); with it, optionally OKV_F_ASYNC, everything stays
+ * in stream order (totals then by okv_get_totals after okv_sync).  n_rows == 0
+ * succeeds and launches nothing.  Returns OKV_OK, OKV_E_CAPACITY (val_bytes > val_cap:
+ * totals and the per-key arrays are set, val_arena is not written), or an error.
+ */
+int okv_get_rows(okv_ctx *ctx, const uint8_t *seg, uint64_t seg_bytes, const okv_index *ix,
+                 const okv_bloom *bloom, const okv_rows *keys, int compression,
+                 okv_get_out *out, uint32_t flags);
+/* After an OKV_F_ASYNC okv_get_rows and okv_sync(): the totals of the context's last call
+ * (OKV_E_CAPACITY as the synchronous call would have returned it). */
+int okv_get_totals(okv_ctx *ctx, okv_get_out *out);
+
+/* ======================================================================== *
  * Merge: snapshot_reader.Reader.GetRange's k-way merge
  * (/root/reference/snapshot_reader/snapshot_reader.go:214-372) on the device,
  * and the same newest-wins merge as a compaction feed.
@@ -506,6 +574,8 @@ int okv_profile_read(okv_ctx *ctx, double *ms, uint64_t *calls);
                                   slower than passes 1-3 */
 #define OKV_PATH_POINT 2048u /* okv_point_kernel: a host-mode call of a few small uncompressed
                                 blocks (GetRow, GetRange) in one launch over pinned memory */
+#define OKV_PATH_GET 8192u /* okv_get_rows: okv_get_locate_kernel, the grouping and
+                             okv_get_search_kernel */
 uint32_t okv_last_path(const okv_ctx *ctx);
 
 /* Device / pinned-host memory helpers for callers without another allocator. */

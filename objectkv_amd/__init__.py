@@ -9,8 +9,10 @@ from .sst import (Decoded, Decoder, Encoded, Encoder, GpuSegmentWriter, Metadata
                   OkvError, SegmentWriter, bytes_to_metadata, fetch_metadata, pack_rows,
                   synth_segment, xxh64)
 from .bloom import DeviceBloom  # noqa: F401
+from .get import DeviceIndex, get_rows  # noqa: F401
 
-__all__ = ["build", "lib", "Decoder", "Decoded", "DeviceBloom", "Encoder", "Encoded",
+__all__ = ["build", "lib", "Decoder", "Decoded", "DeviceBloom", "DeviceIndex", "get_rows",
+           "Encoder", "Encoded",
            "GpuSegmentWriter",
            "Metadata", "OkvError", "SegmentWriter", "pack_rows",
            "bytes_to_metadata", "fetch_metadata", "synth_segment", "xxh64"]

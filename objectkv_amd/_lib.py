@@ -36,6 +36,10 @@ PATH_FUSED, PATH_SMALL, PATH_TILE, PATH_SWEEP = 1, 2, 4, 8
 PATH_STAGED, PATH_GATHER, PATH_BIG, PATH_ZSTD = 16, 32, 64, 128
 PATH_ZSTD_REGROW, PATH_ENC_ONEPASS, PATH_STREAM = 256, 512, 1024
 PATH_POINT, PATH_GROUP = 2048, 4096
+PATH_GET = 8192
+# okv_get_out.state (include/okv_sst.h OKV_GET_*)
+GET_FOUND, GET_BLOOM_NEGATIVE, GET_NO_BLOCK, GET_NOT_IN_BLOCK = 0, 1, 2, 3
+GET_BLOCK_ERROR, GET_FALLBACK = 4, 5
 # SegmentWriter sentinels (okv_sst.h OKV_W_*)
 W_KEY_TOO_LARGE, W_VALUE_TOO_LARGE, W_CLOSED, W_INVALID_KEY = -101, -102, -103, -104
 W_NIL_WRITER, W_UNSUPPORTED, W_NO_ROWS = -105, -106, -107
@@ -57,14 +61,17 @@ SYMBOLS = [
     "okv_bloom_estimate", "okv_bloom_new", "okv_bloom_read_from", "okv_bloom_free",
     "okv_bloom_info", "okv_bloom_clear", "okv_bloom_add_rows", "okv_bloom_test_rows",
     "okv_bloom_write_to", "okv_bloom_last_path",
+    "okv_index_new", "okv_index_free", "okv_index_info", "okv_get_rows", "okv_get_totals",
     "okv_writer_new", "okv_writer_write_row", "okv_writer_close", "okv_writer_data",
     "okv_writer_meta", "okv_writer_num_blocks", "okv_writer_block", "okv_writer_free",
     "okv_writer_set_bloom",
     "okv_meta_fetch", "okv_meta_parse", "okv_meta_num_blocks", "okv_meta_compression",
     "okv_meta_descs", "okv_meta_first_key", "okv_meta_last_key", "okv_meta_block",
-    "okv_meta_free", "okv_meta_has_bloom", "okv_meta_bloom_test", "okv_synth_segment",
+    "okv_meta_free", "okv_meta_has_bloom", "okv_meta_bloom_test", "okv_meta_bloom_bytes",
+    "okv_synth_segment",
     "okv_reader_open", "okv_reader_fetch_metadata", "okv_reader_load_metadata",
     "okv_reader_num_blocks", "okv_reader_read_block", "okv_reader_get_row",
+    "okv_reader_get_rows",
     "okv_reader_get_range", "okv_reader_close", "okv_reader_free", "okv_reader_row_iter",
     "okv_iter_next", "okv_iter_seek", "okv_iter_free", "okv_reader_io_stats",
 ]
@@ -122,6 +129,15 @@ class EncodeOut(C.Structure):
                 ("n_blocks", C.c_uint64), ("data_bytes", C.c_uint64),
                 ("meta_bytes", C.c_uint64), ("file_bytes", C.c_uint64),
                 ("meta_hash", C.c_uint64), ("bad_row", C.c_uint64)]
+
+
+class GetOut(C.Structure):
+    """okv_get_out (include/okv_sst.h)."""
+    _fields_ = [("state", C.c_void_p), ("blk_status", C.c_void_p), ("entry", C.c_void_p),
+                ("val_off", C.c_void_p), ("val_len", C.c_void_p), ("val_pos", C.c_void_p),
+                ("val_arena", C.c_void_p), ("val_cap", C.c_uint64), ("n_found", C.c_uint64),
+                ("n_fallback", C.c_uint64), ("val_bytes", C.c_uint64),
+                ("blocks_searched", C.c_uint64)]
 
 
 class MergeSrc(C.Structure):
@@ -219,6 +235,11 @@ def lib():
         "okv_bloom_test_rows": (i32, [p, p, C.POINTER(Rows), p, u32]),
         "okv_bloom_write_to": (i32, [p, p, p, u64, u32]),
         "okv_bloom_last_path": (C.c_uint32, [p]),
+        "okv_index_new": (i32, [p, p, p, p, p, u64, C.POINTER(p)]),
+        "okv_index_free": (None, [p]),
+        "okv_index_info": (i32, [p, C.POINTER(u64), C.POINTER(u64)]),
+        "okv_get_rows": (i32, [p, p, u64, p, p, C.POINTER(Rows), i32, C.POINTER(GetOut), u32]),
+        "okv_get_totals": (i32, [p, C.POINTER(GetOut)]),
         "okv_writer_new": (p, [u64, u64, i32, i32]),
         "okv_writer_write_row": (i32, [p, p, C.c_size_t, p, C.c_size_t]),
         "okv_writer_close": (i32, [p, i32, C.POINTER(u64), C.POINTER(u64)]),
@@ -233,6 +254,7 @@ def lib():
         "okv_meta_parse": (i32, [p, u64, C.POINTER(p)]),
         "okv_meta_has_bloom": (i32, [p]),
         "okv_meta_bloom_test": (i32, [p, p, C.c_size_t]),
+        "okv_meta_bloom_bytes": (p, [p, C.POINTER(u64)]),
         "okv_meta_num_blocks": (u64, [p]),
         "okv_meta_compression": (i32, [p]),
         "okv_meta_descs": (p, [p]),
@@ -248,6 +270,8 @@ def lib():
         "okv_reader_num_blocks": (i32, [p, C.POINTER(u64)]),
         "okv_reader_read_block": (i32, [p, u64, C.POINTER(C.POINTER(Row)), C.POINTER(u64)]),
         "okv_reader_get_row": (i32, [p, p, C.c_size_t, C.POINTER(Row)]),
+        "okv_reader_get_rows": (i32, [p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), u64,
+                                      C.POINTER(Row), C.POINTER(i32)]),
         "okv_reader_get_range": (i32, [p, p, C.c_size_t, p, C.c_size_t,
                                        C.POINTER(C.POINTER(Row)), C.POINTER(u64)]),
         "okv_reader_close": (i32, [p]),

@@ -33,6 +33,23 @@ def pack_keys(keys):
     return dict(key_arena=r["key_arena"], key_off=r["key_off"], key_len=r["key_len"])
 
 
+def key_rows(rows, n_rows, key_arena_bytes):
+    """The key arrays of rows -- the pack_rows() dict, a list of keys or (key, value) pairs,
+    or a dict of device tensors -- as an okv_rows -> (okv_rows, device?, the arrays kept alive)"""
+    if not isinstance(rows, dict):
+        rows = list(rows)
+        rows = pack_rows(rows) if rows and isinstance(rows[0], tuple) else pack_keys(rows)
+    host = isinstance(rows["key_len"], np.ndarray)
+    n = int(rows["key_len"].size if host else rows["key_len"].numel()) \
+        if n_rows is None else int(n_rows)
+    if key_arena_bytes is None:
+        ka = rows.get("key_arena")
+        key_arena_bytes = 0 if ka is None else int(ka.size if host else ka.numel())
+    R = _lib.Rows(_ptr(rows.get("key_arena")), _ptr(rows["key_off"]), _ptr(rows["key_len"]),
+                  None, None, None, n, int(key_arena_bytes), 0)
+    return R, not host, rows
+
+
 class DeviceBloom:
     """One okv_bloom on the context of an existing Decoder / Encoder."""
 
@@ -76,28 +93,12 @@ class DeviceBloom:
         return int(lib().okv_bloom_last_path(self._h))
 
     # -- rows ----------------------------------------------------------------------
-    @staticmethod
-    def _rows(rows, n_rows, key_arena_bytes):
-        """-> (okv_rows, device?, the arrays kept alive)"""
-        if not isinstance(rows, dict):
-            rows = list(rows)
-            rows = pack_rows(rows) if rows and isinstance(rows[0], tuple) else pack_keys(rows)
-        host = isinstance(rows["key_len"], np.ndarray)
-        n = int(rows["key_len"].size if host else rows["key_len"].numel()) \
-            if n_rows is None else int(n_rows)
-        if key_arena_bytes is None:
-            ka = rows.get("key_arena")
-            key_arena_bytes = 0 if ka is None else int(ka.size if host else ka.numel())
-        R = _lib.Rows(_ptr(rows.get("key_arena")), _ptr(rows["key_off"]), _ptr(rows["key_len"]),
-                      None, None, None, n, int(key_arena_bytes), 0)
-        return R, not host, rows
-
     def add_rows(self, rows, n_rows=None, key_arena_bytes=None, form: int = 0, sync=True):
         """Add(key) for every row.  rows: the pack_rows() dict, a list of keys or
         (key, value) pairs (host mode), or a dict of device tensors key_arena,
         key_off, key_len.  form: BLOOM_FORCE_LDS / BLOOM_FORCE_GLOBAL; sync=False
         only enqueues (device tensors)."""
-        R, dev, keep = self._rows(rows, n_rows, key_arena_bytes)
+        R, dev, keep = key_rows(rows, n_rows, key_arena_bytes)
         flags = form | ((F_DEVICE_PTRS | (0 if sync else F_ASYNC)) if dev else 0)
         self._owner._check(lib().okv_bloom_add_rows(self._owner._ctx, self._h, C.byref(R), flags),
                            "okv_bloom_add_rows")
@@ -106,7 +107,7 @@ class DeviceBloom:
     def test_rows(self, rows, n_rows=None, key_arena_bytes=None, out=None, sync=True):
         """Test(key) for every row -> uint8 per key (1 maybe, 0 absent): a numpy
         array (host rows) or `out`, a device uint8 tensor (device rows)."""
-        R, dev, keep = self._rows(rows, n_rows, key_arena_bytes)
+        R, dev, keep = key_rows(rows, n_rows, key_arena_bytes)
         if dev:
             if out is None:
                 raise ValueError("test_rows on device rows needs out=")

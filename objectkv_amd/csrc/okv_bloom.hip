@@ -197,6 +197,11 @@ int own(okv_ctx* ctx, const okv_bloom* f) {
 }
 
 }  // namespace
+
+BloomView bloom_view(const okv_bloom* f) {
+  return BloomView{f->ctx, f->bits.data(), f->m, f->k, f->length};
+}
+
 }  // namespace okv
 
 using namespace okv;

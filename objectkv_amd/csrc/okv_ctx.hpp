@@ -1,11 +1,12 @@
 // okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip), encode
-// (okv_encode.hip), zstd (okv_zstd.hip) and merge (okv_merge.hip) translation units.
+// (okv_encode.hip), zstd (okv_zstd.hip), merge (okv_merge.hip) and batched GetRow
+// (okv_get.hip) translation units.
 // Internal header.
 // Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
 // its capacity and frees itself with its owner; kernels get raw pointers from data().  The
 // owners are okv_ctx (decode), AblateState (the decode ablation arms) and, each defined in its
 // own file behind a forward declaration here and released by okv_close: EncScratch,
-// zst::Scratch and mrg::Scratch.
+// zst::Scratch, mrg::Scratch and get::Scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #define OKV_BUF_HIP
@@ -26,9 +27,24 @@ namespace mrg {
 struct Scratch;  // okv_merge.hip
 }
 void merge_release(okv_ctx* ctx);
+namespace get {
+struct Scratch;  // okv_get.hip
+}
+void get_release(okv_ctx* ctx);
+// okv_bloom.hip: what another translation unit's kernel needs to probe a device filter.
+struct BloomView {
+  okv_ctx* ctx;
+  const uint64_t* words;  // device, wordsNeeded(length) native words
+  uint64_t m, k, length;
+};
+BloomView bloom_view(const okv_bloom* f);
 // okv_decode.hip: enqueue XXH64 of each block's BlockSize bytes (device pointers).
 void launch_hash(hipStream_t stream, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
                  uint32_t nblk, uint64_t* out);
+// okv_encode.hip: enqueue the one-workgroup exclusive scan of n u64 values (okv_enc_scan_kernel):
+// out[i] = sum of in[j], j < i; *total (may be null) = the sum.  in and out are distinct.
+void launch_scan_u64(hipStream_t stream, const uint64_t* in, uint64_t n, uint64_t* out,
+                     unsigned long long* total);
 // okv_zstd.hip: the zstd stage.  Every block of the batch (device pointers) is decompressed into
 // the stage's own scratch; passes 1-3 then walk `bytes` by `descs` (offset into bytes,
 // BlockSize = decompressed length), with `status` as each block's outcome so far.  The
@@ -144,6 +160,7 @@ struct okv_ctx {
   okv::EncScratch* enc = nullptr;  // encode scratch (okv_encode.hip)
   okv::mrg::Scratch* merge = nullptr;  // merge scratch (okv_merge.hip)
   okv::zst::Scratch* zstd = nullptr;   // zstd stage scratch (okv_zstd.hip)
+  okv::get::Scratch* get = nullptr;    // batched GetRow scratch (okv_get.hip)
 };
 
 namespace okv {

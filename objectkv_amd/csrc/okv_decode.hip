@@ -1302,53 +1302,9 @@ __device__ __forceinline__ void walk_staged(const Src& lsrc, uint32_t L, uint64_
                                             uint32_t* rec, uint32_t lane, int32_t& st,
                                             uint64_t& rows, uint64_t& kb, uint64_t& vb,
                                             uint64_t& p) {
-  const uint32_t o32 = __builtin_amdgcn_readfirstlane(
-      uint32_t(min<uint64_t>(go_walk_bound(original_size), 0xffffffffull)));  // (:340)
-  uint32_t pp = 0, nr = 0;
-  kb = vb = 0;
-  while (pp < o32) {  // :340
-    uint32_t kl, vl;
-    lsrc.header(min(pp, L), kl, vl);  // (one address: a broadcast)
-    kl = __builtin_amdgcn_readfirstlane(kl);
-    vl = __builtin_amdgcn_readfirstlane(vl);
-    const uint32_t room = L - pp - 6;
-    // u16/u32 reads (:342-345), key/value reads (:346-349)
-    if (!((L - pp >= 6) & (kl <= room) & (vl <= room - kl))) {
-      st = OKV_BLK_PANIC;
-      break;
-    }
-    const uint32_t rl = 6 + kl + vl;
-    const uint32_t q = pp + lane * rl;  // (< 64 * 64 KiB)
-    uint32_t kj, vj;
-    lsrc.header(min(q, L), kj, vj);
-    const uint32_t rj = L - q - 6;
-    const bool okj = (q <= L) & (L - q >= 6) & (kj <= rj) & (vj <= rj - kj);
-    // (the run is of equal headers, not only equal lengths: the counts add
-    // m key and value lengths)
-    const bool brk = lane >= 1 && (q >= o32 || !okj || kj != kl || vj != vl);
-    const uint64_t bm = __ballot(brk);
-    const uint32_t m = bm ? uint32_t(__builtin_ctzll(bm)) : 64u;  // (>= 1)
-    if (lane < m && nr + lane < uint32_t(kRCap)) rec[nr + lane] = q;
-    nr += m;
-    kb += uint64_t(m) * kl;
-    vb += uint64_t(m) * vl;
-    pp += m * rl;  // the breaking lane's position: a true record start
-    if (m == 64 || pp >= o32) continue;
-    const uint32_t okm = __builtin_amdgcn_readlane(uint32_t(okj), m);
-    const uint32_t km = __builtin_amdgcn_readlane(kj, m), vm = __builtin_amdgcn_readlane(vj, m);
-    if (!okm) {
-      st = OKV_BLK_PANIC;
-      break;
-    }
-    if (lane == 0 && nr < uint32_t(kRCap)) rec[nr] = pp;
-    ++nr;
-    kb += km;
-    vb += vm;
-    pp += 6 + km + vm;
-  }
-  rows = nr;
-  p = pp;
-  if (st != OKV_BLK_OK) rows = kb = vb = 0;
+  walk_staged_to(lsrc, L, original_size,
+                 [rec](uint32_t row, uint32_t pos) { if (row < uint32_t(kRCap)) rec[row] = pos; },
+                 lane, st, rows, kb, vb, p);
 }
 // The same walk in HBM by lane 0 (a block too large for the stage); the
 // results are broadcast to the wave.
@@ -3018,6 +2974,7 @@ void okv_close(okv_ctx* ctx) {
   okv::enc_release(ctx);
   okv::zstd_release(ctx);
   okv::merge_release(ctx);
+  okv::get_release(ctx);
   const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;
   delete ctx;  // every scratch buffer releases itself
   if (owned) (void)hipStreamDestroy(owned);

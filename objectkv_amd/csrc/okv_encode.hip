@@ -150,16 +150,6 @@ __device__ __forceinline__ uint64_t Pg(const uint64_t* __restrict__ pl,
   return i < 0 ? 0 : v;
 }
 
-// v from the lane the DPP control names (id where there is none), 64 bits as
-// two v_mov_dpp: a reduction or scan step without an LDS round trip.
-template <int kCtrl, int kRowMask = 0xf>
-__device__ __forceinline__ uint64_t dpp64(uint64_t v, uint64_t id) {
-  const uint32_t lo = __builtin_amdgcn_update_dpp(uint32_t(id), uint32_t(v), kCtrl, kRowMask, 0xf,
-                                                  false);
-  const uint32_t hi = __builtin_amdgcn_update_dpp(uint32_t(id >> 32), uint32_t(v >> 32), kCtrl,
-                                                  kRowMask, 0xf, false);
-  return uint64_t(lo) | (uint64_t(hi) << 32);
-}
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
   return uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(v)), l))) |
          (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(v >> 32)), l))) << 32);
@@ -182,35 +172,7 @@ __device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
   return std::max(std::max(readlane64(v, 15), readlane64(v, 31)),
                   std::max(readlane64(v, 47), readlane64(v, 63)));
 }
-// Wave64 inclusive scan of a 64-bit value by DPP (wave_scan_dpp's steps).
-__device__ __forceinline__ uint64_t wave_scan_dpp64(uint64_t x) {
-  x += dpp64<0x111>(x, 0);
-  x += dpp64<0x112>(x, 0);
-  x += dpp64<0x114>(x, 0);
-  x += dpp64<0x118>(x, 0);
-  x += dpp64<0x142, 0xa>(x, 0);  // row_bcast:15
-  x += dpp64<0x143, 0xc>(x, 0);  // row_bcast:31
-  return x;
-}
-
-// Workgroup exclusive scan of one u64 per thread (kThreads threads); also
-// returns the workgroup total.  `sm` holds kThreads/64 + 1 entries.
-__device__ __forceinline__ uint64_t wg_excl_scan(uint64_t v, uint64_t* sm, uint64_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t inc = wave_scan_dpp64(v);  // (all lanes active)
-  if (lane == 63) sm[wave] = inc;
-  __syncthreads();
-  uint64_t before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const uint64_t t = sm[w];
-    before += (w < wave) ? t : 0;
-    tot += t;
-  }
-  __syncthreads();
-  total = tot;
-  return before + inc - v;
-}
+// (dpp64, wave_scan_dpp64 and wg_excl_scan: okv_kernels.hpp, shared with okv_get.hip)
 
 // rotl64(x, 31) as two independent alignbit ops (the shift/or form is two deep)
 __device__ __forceinline__ uint64_t rotl31(uint64_t x) {
@@ -1829,6 +1791,13 @@ __global__ __launch_bounds__(kThreads) void okv_synth_fixed_kernel(
   key_len[i] = uint16_t(kl);
   val_off[i] = i * vl;
   val_len[i] = vl;
+}
+
+// okv_enc_scan_kernel for other translation units (okv_ctx.hpp): out[i] = sum of in[j],
+// j < i, for i < n, and *total (may be null) = the sum; in and out are distinct arrays.
+void launch_scan_u64(hipStream_t stream, const uint64_t* in, uint64_t n, uint64_t* out,
+                     unsigned long long* total) {
+  hipLaunchKernelGGL(okv_enc_scan_kernel, dim3(1), dim3(1024), 0, stream, in, n, out, total);
 }
 
 }  // namespace okv

@@ -1,0 +1,667 @@
+// okv_get.hip -- SegmentReader.GetRow (segment_reader.go:362-404) for a batch of keys
+// against one segment resident in device memory: the bloom probe, the floor search over
+// the block index, ReadBlockWithStat of each touched block once, and the row search,
+// one row back per key.  DESIGN.md 20.
+//
+//   okv_get_locate_kernel   one lane per key: Test(key) (okv_bloom_hash.hpp), then
+//                           DescendLessOrEqual over the index image (okv_index.hpp's
+//                           floor_upper); a key that lands on a block this path takes
+//                           adds 1 to that block's count
+//   scan + okv_get_scatter_kernel
+//                           the counts scanned exclusively, the keys scattered into
+//                           per-block lists, the touched blocks compacted into a work list
+//   okv_get_search_kernel   one workgroup per touched block: the block staged into LDS
+//                           by LDS DMA, the header walk with Go's checks (walk_staged_to),
+//                           then the block's keys spread over the waves, lanes over rows
+//   scan + okv_get_values_kernel
+//                           round16(val_len) of the found keys scanned in key order, the
+//                           values copied out with 16-byte stores
+//
+// No kernel waits for another workgroup, and every loop is bounded by an argument of
+// the call: the binary search by 64 steps, the probe by k <= 4096, a walk by
+// BlockSize / 6 records, a compare by the key length (u16), the lists by the key count.
+#include "okv_ctx.hpp"
+
+#include <cstring>
+#include <memory>
+
+#include "okv_bloom_hash.hpp"
+#include "okv_index.hpp"
+
+struct okv_index {
+  okv_ctx* ctx = nullptr;
+  uint64_t nt = 0, nf = 0;     // tree entries, entries given
+  uint64_t max_block = 0;      // largest BlockSize in the tree
+  uint32_t n_cu = 0;
+  okv::DevBuf<okv::Desc> descs;        // [nt] tree order
+  okv::DevBuf<uint32_t> file_index;    // [nt]
+  okv::DevBuf<uint8_t> arena;          // first keys
+  okv::DevBuf<uint64_t> off;           // [nt]
+  okv::DevBuf<uint16_t> len;           // [nt]
+  okv::DevBuf<uint64_t> prefix;        // [nt]
+};
+
+namespace okv {
+namespace get {
+
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kSmallCap = 8192;       // the search kernel's small stage (4 KiB blocks)
+constexpr uint32_t kSearchThreads = 1024;  // 16 waves share a staged block's keys
+constexpr uint32_t kScanPer = 8;           // elements per thread of a scan tile
+constexpr uint32_t kScanTile = kThreads * kScanPer;
+constexpr uint64_t kMaxK = 4096;           // as okv_bloom.hip
+
+struct GetTotals {
+  uint64_t n_found, n_fallback, val_bytes, blocks;
+};
+
+struct Scratch {
+  DevBuf<uint32_t> cnt;     // [nt] keys per block (back to zero after the scatter)
+  DevBuf<uint64_t> gscan;   // [nt + 1] low word: keys before the block; high: touched blocks
+  DevBuf<uint32_t> work;    // [nt] touched blocks (tree positions)
+  DevBuf<uint32_t> tpos;    // [n] the key's block (tree position) or kNone
+  DevBuf<uint32_t> list;    // [n] keys grouped by block
+  DevBuf<uint64_t> vscan;   // [n + 1] exclusive scan of round16(val_len) of found keys
+  DevBuf<uint64_t> tsum_in; // scan tile sums
+  DevBuf<uint64_t> tsum;    // [tiles + 1] their exclusive scan, then the total
+  DevBuf<GetTotals> d_tot;
+  PinBuf<GetTotals> h_tot;
+  DevBuf<uint8_t> stage;    // host mode: key arrays and per-key outputs
+  DevBuf<uint8_t> d_val;    // host mode: the value arena
+  bool last_arena = false;  // the last call's arena and capacity (okv_get_totals)
+  uint64_t last_cap = 0;
+};
+
+struct Params {
+  const uint8_t* seg;
+  uint64_t seg_bytes;
+  int comp;
+  const uint8_t* ka;  // keys
+  const uint64_t* ko;
+  const uint16_t* kl;
+  uint32_t n;
+  index::View ix;  // index image
+  const Desc* descs;
+  const uint32_t* file_index;
+  const uint64_t* words;  // filter (k == 0: no probe)
+  bloom::Modulus mod;
+  uint32_t k;
+  uint64_t length;
+  int32_t* state;  // outputs
+  int32_t* blk_status;
+  uint32_t* entry;
+  uint64_t* val_off;
+  uint32_t* val_len;
+  uint8_t* val_arena;
+  uint64_t val_cap;
+  uint32_t* cnt;  // scratch
+  uint64_t* gscan;
+  uint32_t* work;
+  uint32_t* tpos;
+  uint32_t* list;
+  uint64_t* vscan;
+  GetTotals* tot;
+};
+
+namespace {
+
+// ---- locate ------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void okv_get_locate_kernel(Params P) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < P.n;
+       i += uint64_t(gridDim.x) * kThreads) {
+    const uint8_t* key = P.ka + P.ko[i];
+    const uint32_t kl = P.kl[i];
+    int32_t state = OKV_GET_NOT_IN_BLOCK, bst = OKV_BLK_OK;
+    uint32_t entry = kNone, t = kNone;
+    bool maybe = true;
+    if (P.k) {  // Test (:371-378): a location >= length reads as unset (bitset.Test)
+      uint64_t h[4];
+      bloom::base_hashes(key, kl, h);
+      for (uint32_t j = 0; j < P.k; ++j) {
+        const uint64_t loc = bloom::location(h, j, P.mod);
+        if (loc >= P.length || !((P.words[loc >> 6] >> (loc & 63)) & 1)) {
+          maybe = false;
+          break;
+        }
+      }
+    }
+    if (!maybe) {
+      state = OKV_GET_BLOOM_NEGATIVE;
+    } else {
+      const uint64_t up = index::floor_upper(P.ix, key, kl, index::prefix8(key, kl));
+      if (up == 0) {
+        state = OKV_GET_NO_BLOCK;  // :387-389
+      } else {
+        const uint32_t tt = uint32_t(up - 1);
+        const Desc d = P.descs[tt];
+        entry = P.file_index[tt];
+        bst = go_read_status(d, P.seg_bytes);  // :303-316, before any read
+        if (bst != OKV_BLK_OK) {
+          state = OKV_GET_BLOCK_ERROR;
+        } else if (P.comp == OKV_COMP_ZSTD || d.block_size > uint64_t(kStage)) {
+          state = OKV_GET_FALLBACK;
+        } else {
+          t = tt;
+          atomicAdd(&P.cnt[tt], 1u);
+        }
+      }
+    }
+    P.state[i] = state;
+    P.blk_status[i] = bst;
+    P.entry[i] = entry;
+    P.val_off[i] = 0;
+    P.val_len[i] = 0;
+    P.tpos[i] = t;
+  }
+}
+
+// ---- exclusive scan of a u64 per element: tile sums (wg_excl_scan, okv_kernels.hpp), their
+// scan by the encode's one-workgroup kernel (launch_scan_u64), the tiles again.  Three
+// launches; no workgroup waits for another. -------------------------------------------
+struct CntLoad {  // keys on the block | (block touched) << 32
+  const uint32_t* cnt;
+  __device__ uint64_t operator()(uint64_t i) const {
+    const uint32_t c = cnt[i];
+    return uint64_t(c) | (uint64_t(c != 0) << 32);
+  }
+};
+struct ValLoad {  // arena room of the key's value
+  const int32_t* state;
+  const uint32_t* val_len;
+  __device__ uint64_t operator()(uint64_t i) const {
+    return state[i] == OKV_GET_FOUND ? round16(val_len[i]) : 0;
+  }
+};
+
+template <class Load>
+__global__ __launch_bounds__(kThreads) void okv_get_scan_sums_kernel(Load ld, uint64_t n,
+                                                                     uint64_t* __restrict__ tsum) {
+  __shared__ uint64_t sm[kThreads / 64 + 1];
+  const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
+  uint64_t s = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < kScanPer; ++j)
+    if (base + j < n) s += ld(base + j);
+  uint64_t total;
+  (void)wg_excl_scan(s, sm, total);
+  if (threadIdx.x == 0) tsum[blockIdx.x] = total;
+}
+
+// out[i] = sum of ld(j), j < i; out[n] = the total; out2 (may be null): out[0 .. n) again
+template <class Load>
+__global__ __launch_bounds__(kThreads) void okv_get_scan_write_kernel(
+    Load ld, uint64_t n, const uint64_t* __restrict__ tsum, uint64_t* __restrict__ out,
+    uint64_t* __restrict__ out2) {
+  __shared__ uint64_t sm[kThreads / 64 + 1];
+  const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
+  uint64_t v[kScanPer], s = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < kScanPer; ++j) {
+    v[j] = base + j < n ? ld(base + j) : 0;
+    s += v[j];
+  }
+  uint64_t total;
+  uint64_t x = wg_excl_scan(s, sm, total) + tsum[blockIdx.x];
+#pragma unroll
+  for (uint32_t j = 0; j < kScanPer; ++j) {
+    if (base + j < n) {
+      out[base + j] = x;
+      if (out2) out2[base + j] = x;
+    }
+    x += v[j];
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = tsum[gridDim.x];
+}
+
+// ---- grouping: keys into per-block lists, touched blocks into the work list ----
+__global__ __launch_bounds__(kThreads) void okv_get_scatter_kernel(Params P) {
+  const uint64_t stride = uint64_t(gridDim.x) * kThreads;
+  const uint64_t first = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  for (uint64_t i = first; i < P.n; i += stride) {
+    const uint32_t t = P.tpos[i];
+    if (t == kNone) continue;
+    // (the count is taken down as the list fills: zero again for the next call)
+    const uint32_t slot = uint32_t(P.gscan[t]) + atomicSub(&P.cnt[t], 1u) - 1u;
+    P.list[slot] = uint32_t(i);
+  }
+  for (uint64_t t = first; t < P.ix.nt; t += stride) {
+    const uint64_t a = P.gscan[t], b = P.gscan[t + 1];
+    if (uint32_t(a) != uint32_t(b)) P.work[uint32_t(a >> 32)] = uint32_t(t);
+  }
+  if (first == 0) P.tot->blocks = P.gscan[P.ix.nt] >> 32;
+}
+
+// ---- search --------------------------------------------------------------------
+template <uint32_t kCap>
+struct __align__(16) SearchSmem {
+  uint4 stage[(kCap + kStagePad) / 16];  // [16 B guard][block image][guard]
+  uint16_t rec[kCap / 6 + 2];            // every record's position (< 64 KiB)
+};
+
+struct StageSrc {  // block byte x at LDS byte bias + x
+  const uint32_t* sw;
+  uint32_t bias;
+  __device__ __forceinline__ void header(uint32_t pos, uint32_t& kl, uint32_t& vl) const {
+    header_lds(sw, bias + pos, kl, vl);
+  }
+};
+
+// Key bytes [j, j + 4) (j < kl) from the aligned dwords that contain a key byte; bytes
+// past the key are unspecified.
+__device__ __forceinline__ uint32_t key_dword(const uint8_t* key, uint32_t kl, uint32_t j) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(key + j);
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3));
+  const uint32_t sh = uint32_t(a & 3);
+  const uint32_t w0 = w[0];
+  const uint32_t w1 =
+      (sh && reinterpret_cast<const uint8_t*>(w + 1) < key + kl) ? w[1] : 0u;
+  return funnel(w1, w0, sh);
+}
+
+template <uint32_t kCap>
+__global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P) {
+  __shared__ SearchSmem<kCap> sm;
+  __shared__ int32_t s_st;
+  __shared__ uint32_t s_rows;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sm.stage);
+  const uint32_t touched = uint32_t(P.gscan[P.ix.nt] >> 32);
+  for (uint32_t w = blockIdx.x; w < touched; w += gridDim.x) {
+    const uint32_t t = P.work[w];
+    const Desc d = P.descs[t];
+    const uint32_t k0 = uint32_t(P.gscan[t]), k1 = uint32_t(P.gscan[t + 1]);
+    if (d.block_size > kCap) continue;  // (the launch sized kCap for the whole index)
+    // the block passed go_read_status in the locate kernel: its BlockSize bytes are
+    // in the segment.  Q7 (:331-333): the LZ4 flag decodes an empty buffer
+    const uint32_t L = P.comp == OKV_COMP_LZ4 ? 0u : uint32_t(d.block_size);
+    const uint32_t shift = uint32_t(d.offset & 15);
+    if (L) {  // stage [offset - shift, offset + L) in 16-byte pieces, all in flight
+      const uint32_t nch = (shift + L + 15) >> 4;
+      const uint8_t* g = P.seg + (d.offset - shift);
+      for (uint32_t c0 = wave * 64; c0 < nch; c0 += kSearchThreads) {
+        if (c0 + lane < nch)  // (an inactive lane writes no LDS)
+          __builtin_amdgcn_global_load_lds(g + 16ull * (c0 + lane), OKV_LDS_PTR(sm.stage + 1 + c0),
+                                           16, 0, 0);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    const uint32_t bias = 16u + shift;
+    if (tid < 64) {  // ReadBlockWithStat's record loop (:338-352) in full, by wave 0
+      int32_t st = OKV_BLK_OK;
+      uint64_t rows = 0, kb = 0, vb = 0, pend = 0;
+      uint16_t* rec = sm.rec;
+      walk_staged_to(StageSrc{sw, bias}, L, d.original_size,
+                     [rec](uint32_t row, uint32_t pos) { rec[row] = uint16_t(pos); }, lane, st,
+                     rows, kb, vb, pend);
+      if (lane == 0) {
+        s_st = st;
+        s_rows = uint32_t(rows);
+      }
+    }
+    __syncthreads();
+    const int32_t st = s_st;
+    const uint32_t rows = s_rows;
+    // the block's keys over the waves; per key, lanes over the rows in block order
+    for (uint32_t j = k0 + wave; j < k1; j += kSearchThreads / 64) {
+      const uint32_t i = P.list[j];
+      if (st != OKV_BLK_OK) {  // a failed block fails its keys, wherever the bad record is
+        if (lane == 0) {
+          P.state[i] = OKV_GET_BLOCK_ERROR;
+          P.blk_status[i] = st;
+        }
+        continue;
+      }
+      const uint8_t* key = P.ka + P.ko[i];
+      const uint32_t kl = P.kl[i];
+      uint32_t hit = kNone;
+      for (uint32_t r0 = 0; r0 < rows; r0 += 64) {
+        const uint32_t r = r0 + lane;
+        bool eq = false;
+        if (r < rows) {
+          const uint32_t at = bias + sm.rec[r];
+          uint32_t rkl, rvl;
+          header_lds(sw, at, rkl, rvl);
+          eq = rkl == kl;  // bytes.Equal (:398): the lengths, then the bytes
+          for (uint32_t b = 0; b < kl && eq; b += 4) {
+            const uint32_t bi = at + 6 + b, sh = bi & 3;
+            const uint32_t a = funnel(sw[(bi >> 2) + 1], sw[bi >> 2], sh);
+            const uint32_t nb = min(4u, kl - b);
+            const uint32_t m = nb == 4 ? ~0u : (1u << (8 * nb)) - 1u;
+            eq = ((a ^ key_dword(key, kl, b)) & m) == 0;
+          }
+        }
+        const uint64_t bm = __ballot(eq);
+        if (bm) {  // the lowest matching row of the earliest round: the first in block order
+          hit = r0 + uint32_t(__builtin_ctzll(bm));
+          break;
+        }
+      }
+      if (lane == 0 && hit != kNone) {
+        const uint32_t pos = sm.rec[hit];
+        uint32_t rkl, rvl;
+        header_lds(sw, bias + pos, rkl, rvl);
+        P.state[i] = OKV_GET_FOUND;
+        P.val_off[i] = d.offset + pos + 6 + rkl;
+        P.val_len[i] = rvl;
+      }
+    }
+    __syncthreads();  // the stage and the positions are reused by the next block
+  }
+}
+
+// ---- values ----------------------------------------------------------------------
+// The totals of the call: found and fallback keys, and the scan's value bytes.
+__global__ __launch_bounds__(kThreads) void okv_get_count_kernel(Params P) {
+  uint32_t f = 0, fb = 0;
+  for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < P.n;
+       i += uint64_t(gridDim.x) * kThreads) {
+    const int32_t s = P.state[i];
+    f += s == OKV_GET_FOUND;
+    fb += s == OKV_GET_FALLBACK;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    f += __shfl_xor(f, d, 64);
+    fb += __shfl_xor(fb, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (f) atomicAdd(reinterpret_cast<unsigned long long*>(&P.tot->n_found), f);
+    if (fb) atomicAdd(reinterpret_cast<unsigned long long*>(&P.tot->n_fallback), fb);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) P.tot->val_bytes = P.vscan[P.n];
+}
+
+// One wave per found key: its value from the segment into val_arena at the scanned
+// position, 16 bytes a lane, the pad bytes zero.  Nothing is written when the values do
+// not fit val_cap.
+__global__ __launch_bounds__(kThreads) void okv_get_values_kernel(Params P) {
+  if (P.vscan[P.n] > P.val_cap) return;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t waves = uint64_t(gridDim.x) * (kThreads / 64);
+  for (uint64_t i = uint64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); i < P.n;
+       i += waves) {
+    if (P.state[i] != OKV_GET_FOUND) continue;
+    const uint32_t vl = P.val_len[i];
+    const uint64_t off = P.val_off[i];
+    uint4* dst = reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]);
+    for (uint32_t c = lane; c < (vl + 15) / 16; c += 64) {
+      const uint4 v = window16(P.seg, P.seg_bytes, int64_t(off + 16ull * c));
+      const int32_t nb = int32_t(min(16u, vl - 16 * c));
+      dst[c] = merge_bytes(make_uint4(0, 0, 0, 0), v, 0, nb);
+    }
+  }
+}
+
+// ---- host ------------------------------------------------------------------------
+uint32_t ceil_div(uint64_t a, uint64_t b) { return uint32_t((a + b - 1) / b); }
+
+Scratch* scratch(okv_ctx* ctx) {
+  if (!ctx->get) ctx->get = new Scratch();
+  return ctx->get;
+}
+
+template <class Load>
+int scan(okv_ctx* ctx, Scratch* s, Load ld, uint64_t n, uint64_t* out, uint64_t* out2) {
+  const uint32_t ntiles = ceil_div(n, kScanTile);  // (n > 0)
+  if (int rc = reserve(ctx, s->tsum, size_t(ntiles) + 1)) return rc;
+  if (int rc = reserve(ctx, s->tsum_in, size_t(ntiles))) return rc;
+  hipLaunchKernelGGL(okv_get_scan_sums_kernel<Load>, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
+                     ld, n, s->tsum_in.data());
+  launch_scan_u64(ctx->stream, s->tsum_in.data(), ntiles, s->tsum.data(),
+                  reinterpret_cast<unsigned long long*>(s->tsum.data() + ntiles));
+  hipLaunchKernelGGL(okv_get_scan_write_kernel<Load>, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
+                     ld, n, s->tsum.data(), out, out2);
+  OKV_HIP(hipGetLastError());
+  return OKV_OK;
+}
+
+// Everything up to the totals, enqueued: locate, grouping, search, the value scan
+// (val_pos: where the caller wants the positions, or null) and the counts.
+int run(okv_ctx* ctx, Scratch* s, const okv_index* ix, Params& P, uint64_t* val_pos) {
+  const uint64_t n = P.n, nt = ix->nt;
+  if (int rc = reserve(ctx, s->cnt, size_t(nt))) return rc;
+  if (int rc = reserve(ctx, s->gscan, size_t(nt) + 1)) return rc;
+  if (int rc = reserve(ctx, s->work, size_t(nt))) return rc;
+  if (int rc = reserve(ctx, s->tpos, size_t(n))) return rc;
+  if (int rc = reserve(ctx, s->list, size_t(n))) return rc;
+  if (int rc = reserve(ctx, s->vscan, size_t(n) + 1)) return rc;
+  if (int rc = reserve(ctx, s->d_tot, 1)) return rc;
+  if (int rc = reserve(ctx, s->h_tot, 1)) return rc;
+  P.cnt = s->cnt.data(), P.gscan = s->gscan.data(), P.work = s->work.data();
+  P.tpos = s->tpos.data(), P.list = s->list.data(), P.vscan = s->vscan.data();
+  P.tot = s->d_tot.data();
+  OKV_HIP(hipMemsetAsync(P.tot, 0, sizeof(GetTotals), ctx->stream));
+  if (nt) OKV_HIP(hipMemsetAsync(P.cnt, 0, nt * 4, ctx->stream));
+  const uint32_t cap = ix->n_cu * 8;
+  const uint32_t gk = std::max(1u, std::min(ceil_div(n, kThreads), cap));
+  hipLaunchKernelGGL(okv_get_locate_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
+  OKV_HIP(hipGetLastError());
+  if (nt) {
+    if (int rc = scan(ctx, s, CntLoad{P.cnt}, nt, P.gscan, nullptr)) return rc;
+    const uint32_t gs = std::max(1u, std::min(ceil_div(std::max(n, nt), kThreads), cap));
+    hipLaunchKernelGGL(okv_get_scatter_kernel, dim3(gs), dim3(kThreads), 0, ctx->stream, P);
+    const uint64_t most = std::min(n, nt);  // touched blocks at most
+    if (ix->max_block <= kSmallCap) {
+      const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(ix->n_cu) * 8));
+      hipLaunchKernelGGL(okv_get_search_kernel<kSmallCap>, dim3(g), dim3(kSearchThreads), 0,
+                         ctx->stream, P);
+    } else {
+      const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(ix->n_cu) * 2));
+      hipLaunchKernelGGL(okv_get_search_kernel<uint32_t(kStage)>, dim3(g), dim3(kSearchThreads), 0,
+                         ctx->stream, P);
+    }
+    OKV_HIP(hipGetLastError());
+  }
+  if (int rc = scan(ctx, s, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos)) return rc;
+  hipLaunchKernelGGL(okv_get_count_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
+  OKV_HIP(hipGetLastError());
+  return OKV_OK;
+}
+
+int launch_values(okv_ctx* ctx, const okv_index* ix, const Params& P) {
+  const uint32_t g = std::max(1u, std::min(ceil_div(P.n, kThreads / 64), ix->n_cu * 8));
+  hipLaunchKernelGGL(okv_get_values_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, P);
+  OKV_HIP(hipGetLastError());
+  return OKV_OK;
+}
+
+int read_totals(okv_ctx* ctx, Scratch* s, okv_get_out* out) {
+  OKV_HIP(hipMemcpyAsync(s->h_tot.data(), s->d_tot.data(), sizeof(GetTotals),
+                         hipMemcpyDeviceToHost, ctx->stream));
+  OKV_HIP(hipStreamSynchronize(ctx->stream));
+  out->n_found = s->h_tot->n_found;
+  out->n_fallback = s->h_tot->n_fallback;
+  out->val_bytes = s->h_tot->val_bytes;
+  out->blocks_searched = s->h_tot->blocks;
+  return OKV_OK;
+}
+
+}  // namespace
+}  // namespace get
+
+void get_release(okv_ctx* ctx) {
+  delete ctx->get;  // the buffers release themselves
+  ctx->get = nullptr;
+}
+
+}  // namespace okv
+
+using namespace okv;
+using namespace okv::get;
+
+extern "C" {
+
+int okv_index_new(okv_ctx* ctx, const okv_block_desc* descs, const uint8_t* fk_arena,
+                  const uint64_t* fk_off, const uint16_t* fk_len, uint64_t n, okv_index** out) {
+  if (!ctx || !out) return OKV_E_ARG;
+  *out = nullptr;
+  if (n && (!descs || !fk_off || !fk_len)) return set_err(ctx, OKV_E_ARG, "index: entries");
+  if (n >= kNone) return set_err(ctx, OKV_E_ARG, "index: 2^32 - 1 entries or more");
+  for (uint64_t i = 0; i < n; ++i)
+    if (fk_len[i] && !fk_arena) return set_err(ctx, OKV_E_ARG, "index: fk_arena");
+  OKV_HIP(hipSetDevice(ctx->device));
+  const index::Image im = index::build_image(descs, fk_arena, fk_off, fk_len, n);
+  std::unique_ptr<okv_index> ix(new okv_index());
+  ix->ctx = ctx;
+  ix->nt = im.descs.size(), ix->nf = n;
+  for (const okv_block_desc& d : im.descs) ix->max_block = std::max(ix->max_block, d.block_size);
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) !=
+          hipSuccess || ncu <= 0)
+    ncu = 256;
+  ix->n_cu = uint32_t(ncu);
+  const size_t nt = size_t(ix->nt);
+  if (reserve(ctx, ix->descs, nt) || reserve(ctx, ix->file_index, nt) ||
+      reserve(ctx, ix->arena, im.arena.size()) || reserve(ctx, ix->off, nt) ||
+      reserve(ctx, ix->len, nt) || reserve(ctx, ix->prefix, nt))
+    return OKV_E_HIP;
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice;
+  if (nt) {
+    OKV_HIP(hipMemcpyAsync(ix->descs.data(), im.descs.data(), nt * sizeof(Desc), h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(ix->file_index.data(), im.file_index.data(), nt * 4, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(ix->off.data(), im.off.data(), nt * 8, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(ix->len.data(), im.len.data(), nt * 2, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(ix->prefix.data(), im.prefix.data(), nt * 8, h2d, ctx->stream));
+  }
+  if (!im.arena.empty())
+    OKV_HIP(hipMemcpyAsync(ix->arena.data(), im.arena.data(), im.arena.size(), h2d, ctx->stream));
+  OKV_HIP(hipStreamSynchronize(ctx->stream));  // (the image leaves scope)
+  *out = ix.release();
+  return OKV_OK;
+}
+
+void okv_index_free(okv_index* ix) { delete ix; }  // (the buffers release themselves)
+
+int okv_index_info(const okv_index* ix, uint64_t* n_tree, uint64_t* n_file) {
+  if (!ix) return OKV_E_ARG;
+  if (n_tree) *n_tree = ix->nt;
+  if (n_file) *n_file = ix->nf;
+  return OKV_OK;
+}
+
+int okv_get_rows(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv_index* ix,
+                 const okv_bloom* bloom, const okv_rows* keys, int compression, okv_get_out* out,
+                 uint32_t flags) {
+  if (!ctx) return OKV_E_ARG;
+  if (!ix || !keys || !out) return set_err(ctx, OKV_E_ARG, "get: index, keys or out");
+  if (ix->ctx != ctx) return set_err(ctx, OKV_E_ARG, "get: the index belongs to another context");
+  BloomView bv{nullptr, nullptr, 0, 0, 0};
+  if (bloom) {
+    bv = bloom_view(bloom);
+    if (bv.ctx != ctx) return set_err(ctx, OKV_E_ARG, "get: the filter belongs to another context");
+    if (bv.k > kMaxK) return set_err(ctx, OKV_E_ARG, "get: bloom k > 4096");
+    if (bv.k && bv.m == 0) return set_err(ctx, OKV_E_ARG, "get: bloom m == 0");
+  }
+  if (compression != OKV_COMP_NONE && compression != OKV_COMP_ZSTD && compression != OKV_COMP_LZ4)
+    return set_err(ctx, OKV_E_ARG, "get: compression");
+  const uint64_t n = keys->n_rows;
+  if (n >= kNone) return set_err(ctx, OKV_E_ARG, "get: 2^32 - 1 keys or more");
+  ctx->last_path = 0;
+  out->n_found = out->n_fallback = out->val_bytes = out->blocks_searched = 0;
+  Scratch* s = scratch(ctx);
+  s->last_arena = out->val_arena != nullptr;
+  s->last_cap = out->val_cap;
+  if (n == 0) {
+    if (s->d_tot.data()) {  // (okv_get_totals reads this call's totals: none)
+      OKV_HIP(hipSetDevice(ctx->device));
+      OKV_HIP(hipMemsetAsync(s->d_tot.data(), 0, sizeof(GetTotals), ctx->stream));
+    }
+    return OKV_OK;
+  }
+  if (!keys->key_off || !keys->key_len || (!keys->key_arena && keys->key_arena_bytes))
+    return set_err(ctx, OKV_E_ARG, "get: keys");
+  if (!out->state || !out->blk_status || !out->entry || !out->val_off || !out->val_len)
+    return set_err(ctx, OKV_E_ARG, "get: a NULL output array");
+  if (!seg && seg_bytes) return set_err(ctx, OKV_E_ARG, "get: seg");
+  if (reinterpret_cast<uintptr_t>(seg) & 15)
+    return set_err(ctx, OKV_E_ARG, "get: seg is not 16-byte aligned");
+  const bool dev = flags & OKV_F_DEVICE_PTRS;
+  if (dev && out->val_arena && (reinterpret_cast<uintptr_t>(out->val_arena) & 15))
+    return set_err(ctx, OKV_E_ARG, "get: val_arena is not 16-byte aligned");
+  OKV_HIP(hipSetDevice(ctx->device));
+
+  Params P;
+  memset(&P, 0, sizeof(P));
+  P.seg = seg, P.seg_bytes = seg_bytes, P.comp = compression;
+  P.n = uint32_t(n);
+  P.ix = index::View{ix->prefix.data(), ix->arena.data(), ix->off.data(), ix->len.data(), ix->nt};
+  P.descs = ix->descs.data(), P.file_index = ix->file_index.data();
+  if (bloom && bv.k) {
+    P.words = bv.words, P.mod = bloom::modulus(bv.m), P.k = uint32_t(bv.k), P.length = bv.length;
+  }
+  P.val_cap = out->val_cap;
+  ctx->last_path = OKV_PATH_GET;
+
+  if (dev) {
+    P.ka = keys->key_arena, P.ko = keys->key_off, P.kl = keys->key_len;
+    P.state = out->state, P.blk_status = out->blk_status, P.entry = out->entry;
+    P.val_off = out->val_off, P.val_len = out->val_len, P.val_arena = out->val_arena;
+    if (int rc = run(ctx, s, ix, P, out->val_pos)) return rc;
+    if (out->val_arena)
+      if (int rc = launch_values(ctx, ix, P)) return rc;
+    if (flags & OKV_F_ASYNC) return OKV_OK;
+    if (int rc = read_totals(ctx, s, out)) return rc;
+    if (out->val_arena && out->val_bytes > out->val_cap)
+      return set_err(ctx, OKV_E_CAPACITY, "get: val_cap too small");
+    return OKV_OK;
+  }
+
+  // host mode: the key arrays in, the per-key arrays out, through one staging buffer
+  for (uint64_t i = 0; i < n; ++i)
+    if (keys->key_off[i] > keys->key_arena_bytes ||
+        keys->key_len[i] > keys->key_arena_bytes - keys->key_off[i])
+      return set_err(ctx, OKV_E_ARG, "get: a key lies outside key_arena_bytes");
+  const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t oko = al(keys->key_arena_bytes), okl = oko + al(n * 8), ost = okl + al(n * 2),
+               obs = ost + al(n * 4), oen = obs + al(n * 4), ovo = oen + al(n * 4),
+               ovl = ovo + al(n * 8), ovp = ovl + al(n * 4), end = ovp + al(n * 8);
+  if (int rc = reserve(ctx, s->stage, end)) return rc;
+  uint8_t* b = s->stage.data();
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+  if (keys->key_arena_bytes)
+    OKV_HIP(hipMemcpyAsync(b, keys->key_arena, keys->key_arena_bytes, h2d, ctx->stream));
+  OKV_HIP(hipMemcpyAsync(b + oko, keys->key_off, n * 8, h2d, ctx->stream));
+  OKV_HIP(hipMemcpyAsync(b + okl, keys->key_len, n * 2, h2d, ctx->stream));
+  P.ka = b;
+  P.ko = reinterpret_cast<const uint64_t*>(b + oko);
+  P.kl = reinterpret_cast<const uint16_t*>(b + okl);
+  P.state = reinterpret_cast<int32_t*>(b + ost);
+  P.blk_status = reinterpret_cast<int32_t*>(b + obs);
+  P.entry = reinterpret_cast<uint32_t*>(b + oen);
+  P.val_off = reinterpret_cast<uint64_t*>(b + ovo);
+  P.val_len = reinterpret_cast<uint32_t*>(b + ovl);
+  if (int rc = run(ctx, s, ix, P, reinterpret_cast<uint64_t*>(b + ovp))) return rc;
+  OKV_HIP(hipMemcpyAsync(out->state, b + ost, n * 4, d2h, ctx->stream));
+  OKV_HIP(hipMemcpyAsync(out->blk_status, b + obs, n * 4, d2h, ctx->stream));
+  OKV_HIP(hipMemcpyAsync(out->entry, b + oen, n * 4, d2h, ctx->stream));
+  OKV_HIP(hipMemcpyAsync(out->val_off, b + ovo, n * 8, d2h, ctx->stream));
+  OKV_HIP(hipMemcpyAsync(out->val_len, b + ovl, n * 4, d2h, ctx->stream));
+  if (out->val_pos) OKV_HIP(hipMemcpyAsync(out->val_pos, b + ovp, n * 8, d2h, ctx->stream));
+  if (int rc = read_totals(ctx, s, out)) return rc;  // (synchronises)
+  if (!out->val_arena) return OKV_OK;
+  if (out->val_bytes > out->val_cap) return set_err(ctx, OKV_E_CAPACITY, "get: val_cap too small");
+  if (out->val_bytes == 0) return OKV_OK;
+  if (int rc = reserve(ctx, s->d_val, size_t(out->val_bytes))) return rc;
+  P.val_arena = s->d_val.data();
+  P.val_cap = out->val_bytes;
+  if (int rc = launch_values(ctx, ix, P)) return rc;
+  OKV_HIP(hipMemcpyAsync(out->val_arena, P.val_arena, out->val_bytes, d2h, ctx->stream));
+  OKV_HIP(hipStreamSynchronize(ctx->stream));
+  return OKV_OK;
+}
+
+int okv_get_totals(okv_ctx* ctx, okv_get_out* out) {
+  if (!ctx || !out) return OKV_E_ARG;
+  Scratch* s = ctx->get;
+  out->n_found = out->n_fallback = out->val_bytes = out->blocks_searched = 0;
+  if (!s || !s->d_tot.data()) return OKV_OK;  // no call has launched anything
+  OKV_HIP(hipSetDevice(ctx->device));
+  if (int rc = reserve(ctx, s->h_tot, 1)) return rc;
+  if (int rc = read_totals(ctx, s, out)) return rc;
+  if (s->last_arena && out->val_bytes > s->last_cap)
+    return set_err(ctx, OKV_E_CAPACITY, "get: val_cap too small");
+  return OKV_OK;
+}
+
+}  // extern "C"

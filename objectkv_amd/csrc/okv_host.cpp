@@ -447,6 +447,11 @@ void okv_meta_free(okv_meta* m) { delete m; }
 
 int okv_meta_has_bloom(const okv_meta* m) { return m && m->has_bloom ? 1 : 0; }
 
+const uint8_t* okv_meta_bloom_bytes(const okv_meta* m, uint64_t* len) {
+  if (len) *len = m && m->has_bloom ? m->bloom_len : 0;
+  return m && m->has_bloom ? m->bytes.data() + m->bloom_off : nullptr;
+}
+
 // BloomFilter.Test (bloom v2.0.3): baseHashes = murmur3 Sum128 of key, then of
 // key ++ [1] (the hasher keeps its state); bit i of k is
 // (h[i % 2] + i * h[2 + ((i + i % 2) % 4) / 2]) % m, tested by bitset.Test (a

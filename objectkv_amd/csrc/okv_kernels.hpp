@@ -277,6 +277,110 @@ __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t x, int lane) {
   return x;
 }
 
+// v from the lane the DPP control names (id where there is none), 64 bits as
+// two v_mov_dpp: a reduction or scan step without an LDS round trip.
+template <int kCtrl, int kRowMask = 0xf>
+__device__ __forceinline__ uint64_t dpp64(uint64_t v, uint64_t id) {
+  const uint32_t lo = __builtin_amdgcn_update_dpp(uint32_t(id), uint32_t(v), kCtrl, kRowMask, 0xf,
+                                                  false);
+  const uint32_t hi = __builtin_amdgcn_update_dpp(uint32_t(id >> 32), uint32_t(v >> 32), kCtrl,
+                                                  kRowMask, 0xf, false);
+  return uint64_t(lo) | (uint64_t(hi) << 32);
+}
+// Wave64 inclusive scan of a 64-bit value by DPP (wave_scan_dpp's steps).
+__device__ __forceinline__ uint64_t wave_scan_dpp64(uint64_t x) {
+  x += dpp64<0x111>(x, 0);
+  x += dpp64<0x112>(x, 0);
+  x += dpp64<0x114>(x, 0);
+  x += dpp64<0x118>(x, 0);
+  x += dpp64<0x142, 0xa>(x, 0);  // row_bcast:15
+  x += dpp64<0x143, 0xc>(x, 0);  // row_bcast:31
+  return x;
+}
+
+// Workgroup exclusive scan of one u64 per thread (kThreads threads); also
+// returns the workgroup total.  `sm` holds kThreads/64 + 1 entries.
+__device__ __forceinline__ uint64_t wg_excl_scan(uint64_t v, uint64_t* sm, uint64_t& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t inc = wave_scan_dpp64(v);  // (all lanes active)
+  if (lane == 63) sm[wave] = inc;
+  __syncthreads();
+  uint64_t before = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) {
+    const uint64_t t = sm[w];
+    before += (w < wave) ? t : 0;
+    tot += t;
+  }
+  __syncthreads();
+  total = tot;
+  return before + inc - v;
+}
+
+// A staged block's header walk (Go's checks in its order, segment_reader.go:338-352)
+// from its LDS image, by one whole wave on a wave-uniform position, run-length
+// speculated: from a record at p of length rl, lane j reads the header at p + j rl -- a
+// record start if every record before it had the same header; the first lane that
+// breaks the run (past OriginalSize, a failed check, another header) is itself a true
+// record start.  A round of two dependent LDS reads confirms 2 to 64 records.
+// lsrc.header(pos, kl, vl) reads the header at block byte pos <= L (L = the staged
+// length, <= 64 KiB); sink(row, pos) takes every record's position, in any order,
+// from the lane that found it.  A failed block has no rows (rows = kb = vb = 0) and p
+// at the failing record.  The loop runs at most L / 6 + 1 rounds.
+template <class Src, class Sink>
+__device__ __forceinline__ void walk_staged_to(const Src& lsrc, uint32_t L, uint64_t original_size,
+                                               Sink sink, uint32_t lane, int32_t& st,
+                                               uint64_t& rows, uint64_t& kb, uint64_t& vb,
+                                               uint64_t& p) {
+  const uint32_t o32 = __builtin_amdgcn_readfirstlane(
+      uint32_t(min<uint64_t>(go_walk_bound(original_size), 0xffffffffull)));  // (:340)
+  uint32_t pp = 0, nr = 0;
+  kb = vb = 0;
+  while (pp < o32) {  // :340
+    uint32_t kl, vl;
+    lsrc.header(min(pp, L), kl, vl);  // (one address: a broadcast)
+    kl = __builtin_amdgcn_readfirstlane(kl);
+    vl = __builtin_amdgcn_readfirstlane(vl);
+    const uint32_t room = L - pp - 6;
+    // u16/u32 reads (:342-345), key/value reads (:346-349)
+    if (!((L - pp >= 6) & (kl <= room) & (vl <= room - kl))) {
+      st = OKV_BLK_PANIC;
+      break;
+    }
+    const uint32_t rl = 6 + kl + vl;
+    const uint32_t q = pp + lane * rl;  // (< 64 * 64 KiB)
+    uint32_t kj, vj;
+    lsrc.header(min(q, L), kj, vj);
+    const uint32_t rj = L - q - 6;
+    const bool okj = (q <= L) & (L - q >= 6) & (kj <= rj) & (vj <= rj - kj);
+    // (the run is of equal headers, not only equal lengths: the counts add
+    // m key and value lengths)
+    const bool brk = lane >= 1 && (q >= o32 || !okj || kj != kl || vj != vl);
+    const uint64_t bm = __ballot(brk);
+    const uint32_t m = bm ? uint32_t(__builtin_ctzll(bm)) : 64u;  // (>= 1)
+    if (lane < m) sink(nr + lane, q);
+    nr += m;
+    kb += uint64_t(m) * kl;
+    vb += uint64_t(m) * vl;
+    pp += m * rl;  // the breaking lane's position: a true record start
+    if (m == 64 || pp >= o32) continue;
+    const uint32_t okm = __builtin_amdgcn_readlane(uint32_t(okj), m);
+    const uint32_t km = __builtin_amdgcn_readlane(kj, m), vm = __builtin_amdgcn_readlane(vj, m);
+    if (!okm) {
+      st = OKV_BLK_PANIC;
+      break;
+    }
+    if (lane == 0) sink(nr, pp);
+    ++nr;
+    kb += km;
+    vb += vm;
+    pp += 6 + km + vm;
+  }
+  rows = nr;
+  p = pp;
+  if (st != OKV_BLK_OK) rows = kb = vb = 0;
+}
+
 // XXH64 (cespare/xxhash v2.2.0 == canonical XXH64, seed 0) building blocks.
 __device__ constexpr uint64_t XP1 = 11400714785074694791ULL, XP2 = 14029467366897019727ULL,
                               XP3 = 1609587929392839161ULL, XP4 = 9650029242287828579ULL,

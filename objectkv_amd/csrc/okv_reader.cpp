@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "okv_host.h"
+#include "okv_index.hpp"
 #include "okv_sst.h"
 
 namespace {
@@ -113,7 +114,27 @@ struct okv_reader {
   std::vector<okv_row> range_out;
   std::vector<uint8_t> point_key, point_val;  // GetRow's row from okv_point_get
   okv_reader_io io{};  // GPU calls, blocks decoded, bytes staged
+  // the batched GetRow (okv_reader_get_rows): the storage, the block index and the
+  // filter resident on the device from the first batched call until Close
+  bool dev_ready = false;
+  bool dev_bloom_refused = false;  // a filter the device probe does not take
+  uint8_t* d_seg = nullptr;
+  okv_index* d_index = nullptr;
+  okv_bloom* d_bloom = nullptr;
+  std::vector<uint8_t> rows_bytes;  // the keys (and fallback rows) of the last batch
+  ~okv_reader();
 };
+
+namespace {
+void drop_device(okv_reader* r) {
+  if (r->d_bloom) okv_bloom_free(r->d_bloom);
+  if (r->d_index) okv_index_free(r->d_index);
+  if (r->d_seg) okv_device_free(nullptr, r->d_seg);  // (no context: it may be closed by now)
+  r->d_bloom = nullptr, r->d_index = nullptr, r->d_seg = nullptr;
+  r->dev_ready = r->dev_bloom_refused = false;
+}
+}  // namespace
+okv_reader::~okv_reader() { drop_device(this); }
 
 struct okv_iter {
   okv_reader* s;
@@ -127,28 +148,20 @@ struct okv_iter {
 
 namespace {
 
-// ---- btree helpers (google/btree v1.1.2 semantics over a sorted vector) ----
-size_t lower(const okv_reader* r, const uint8_t* k, size_t kl) {  // first item >= k
-  size_t lo = 0, hi = r->tree.size();
-  while (lo < hi) {
-    const size_t m = (lo + hi) / 2;
-    if (bcmp(r->tree[m].first_key.data(), r->tree[m].first_key.size(), k, kl) < 0)
-      lo = m + 1;
-    else
-      hi = m;
+// ---- btree helpers (google/btree v1.1.2 semantics over a sorted vector; the
+// searches and the ReplaceOrInsert order are okv_index.hpp's) ----
+struct TreeKey {
+  const okv_reader* r;
+  void operator()(size_t t, const uint8_t** p, size_t* n) const {
+    *p = r->tree[t].first_key.data();
+    *n = r->tree[t].first_key.size();
   }
-  return lo;
+};
+size_t lower(const okv_reader* r, const uint8_t* k, size_t kl) {  // first item >= k
+  return okv::index::lower(r->tree.size(), TreeKey{r}, k, kl);
 }
 size_t upper(const okv_reader* r, const uint8_t* k, size_t kl) {  // first item > k
-  size_t lo = 0, hi = r->tree.size();
-  while (lo < hi) {
-    const size_t m = (lo + hi) / 2;
-    if (bcmp(r->tree[m].first_key.data(), r->tree[m].first_key.size(), k, kl) <= 0)
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo;
+  return okv::index::upper(r->tree.size(), TreeKey{r}, k, kl);
 }
 
 int load_meta(okv_reader* r, okv_meta* m) {
@@ -169,13 +182,14 @@ int load_meta(okv_reader* r, okv_meta* m) {
     e.first_key.assign(fk, fk + fl);
     e.file_index = i;
     r->file_entries.push_back(e);
-    // ReplaceOrInsert (segment_reader.go:234): an equal FirstKey replaces (Q9)
-    const size_t pos = lower(r, e.first_key.data(), e.first_key.size());
-    if (pos < r->tree.size() && bcmp(r->tree[pos].first_key, e.first_key) == 0)
-      r->tree[pos] = e;
-    else
-      r->tree.insert(r->tree.begin() + pos, e);
   }
+  // ReplaceOrInsert (segment_reader.go:234): an equal FirstKey replaces (Q9)
+  const auto file_key = [r](size_t i, const uint8_t** fk, size_t* fl) {
+    *fk = r->file_entries[i].first_key.data();
+    *fl = r->file_entries[i].first_key.size();
+  };
+  for (uint64_t e : okv::index::tree_order(nb, file_key)) r->tree.push_back(r->file_entries[e]);
+  drop_device(r);  // the batched GetRow's device copies belong to the old metadata
   r->meta.reset(m);  // kept for GetRow's bloom probe
   r->have_meta = true;
   r->window.reset();
@@ -471,6 +485,157 @@ int okv_reader_get_row(okv_reader* r, const uint8_t* key, size_t klen, okv_row* 
   return OKV_R_NO_ROWS;
 }
 
+namespace {
+
+// The storage, the block index and the filter onto the device (once per metadata).  A
+// failure keeps nothing on the device and counts no staged byte; the next call tries again.
+int upload_device(okv_reader* r);
+int ensure_device(okv_reader* r) {
+  if (r->dev_ready) return OKV_OK;
+  drop_device(r);
+  const int rc = upload_device(r);
+  if (rc)
+    drop_device(r);
+  else
+    r->io.bytes_staged += r->data.size();
+  return rc;
+}
+int upload_device(okv_reader* r) {
+  const uint64_t n = r->data.size();
+  r->d_seg = static_cast<uint8_t*>(okv_device_alloc(r->ctx, size_t(n ? n : 1)));
+  if (!r->d_seg) return OKV_R_GPU;
+  if (n && okv_memcpy(r->ctx, r->d_seg, r->data.data(), size_t(n), 0)) return OKV_R_GPU;
+  std::vector<okv_block_desc> descs;
+  std::vector<uint8_t> arena;
+  std::vector<uint64_t> off;
+  std::vector<uint16_t> len;
+  for (const Entry& e : r->file_entries) {
+    descs.push_back(e.d);
+    off.push_back(arena.size());
+    len.push_back(uint16_t(e.first_key.size()));
+    arena.insert(arena.end(), e.first_key.begin(), e.first_key.end());
+  }
+  if (okv_index_new(r->ctx, descs.data(), arena.data(), off.data(), len.data(), descs.size(),
+                    &r->d_index))
+    return OKV_R_GPU;
+  if (okv_meta_has_bloom(r->meta.get())) {
+    uint64_t bl = 0;
+    const uint8_t* bb = okv_meta_bloom_bytes(r->meta.get(), &bl);
+    if (okv_bloom_read_from(r->ctx, bb, bl, &r->d_bloom)) return OKV_R_GPU;
+    uint64_t m = 0, k = 0;
+    okv_bloom_info(r->d_bloom, &m, &k, nullptr, nullptr);
+    r->dev_bloom_refused = k > 4096 || (k && m == 0);  // okv_get_rows: OKV_E_ARG
+  }
+  r->dev_ready = true;
+  return OKV_OK;
+}
+
+}  // namespace
+
+int okv_reader_get_rows(okv_reader* r, const uint8_t* const* keys, const size_t* klens, uint64_t n,
+                        okv_row* rows, int* rcs) {
+  if (!r || (n && (!keys || !klens || !rows || !rcs))) return OKV_E_ARG;
+  int rc = ensure_meta(r);
+  if (rc) {
+    for (uint64_t i = 0; i < n; ++i) rcs[i] = rc;
+    return rc;
+  }
+  for (uint64_t i = 0; i < n; ++i) rows[i] = okv_row{nullptr, 0, nullptr, 0};
+  // the single-key path: without a context, for keys the okv_rows layout cannot hold
+  // and for FALLBACK blocks; its row lives until the next read call, so the bytes move
+  // into the batch's storage (offsets first: the storage grows)
+  struct Held {
+    bool on = false;
+    size_t k = 0, v = 0;
+  };
+  std::vector<Held> held(static_cast<size_t>(n));
+  r->rows_bytes.clear();
+  const auto single = [&](uint64_t i) {
+    okv_row row;
+    rcs[i] = okv_reader_get_row(r, keys[i], klens[i], &row);
+    if (rcs[i]) return;
+    held[size_t(i)].on = true;
+    held[size_t(i)].k = r->rows_bytes.size();
+    r->rows_bytes.insert(r->rows_bytes.end(), row.key, row.key + row.key_len);
+    held[size_t(i)].v = r->rows_bytes.size();
+    r->rows_bytes.insert(r->rows_bytes.end(), row.val, row.val + row.val_len);
+    rows[i].key_len = row.key_len, rows[i].val_len = row.val_len;
+  };
+  // a failure of the device path is the call's failure (OKV_R_GPU for every key), as a
+  // failed decode is okv_reader_get_row's: no quiet change of path
+  const auto gpu_failed = [&]() {
+    for (uint64_t i = 0; i < n; ++i) rcs[i] = OKV_R_GPU;
+    return OKV_R_GPU;
+  };
+  std::vector<uint64_t> batch;  // the keys the device takes
+  // (a zstd segment's keys would all come back FALLBACK: nothing is uploaded for it)
+  if (r->ctx && n && r->compression != OKV_COMP_ZSTD) {
+    if (ensure_device(r)) return gpu_failed();
+    if (!r->dev_bloom_refused)
+      for (uint64_t i = 0; i < n; ++i)
+        if (klens[i] <= 65535) batch.push_back(i);
+  }
+  std::vector<bool> taken(static_cast<size_t>(n), false);
+  if (!batch.empty()) {
+    std::vector<uint8_t> ka;
+    std::vector<uint64_t> ko;
+    std::vector<uint16_t> kl;
+    for (uint64_t i : batch) {
+      ko.push_back(ka.size());
+      kl.push_back(uint16_t(klens[i]));
+      ka.insert(ka.end(), keys[i], keys[i] + klens[i]);
+    }
+    const size_t nb = batch.size();
+    std::vector<int32_t> state(nb), bst(nb);
+    std::vector<uint32_t> entry(nb), vlen(nb);
+    std::vector<uint64_t> voff(nb);
+    okv_rows kr;
+    std::memset(&kr, 0, sizeof(kr));
+    kr.key_arena = ka.data(), kr.key_off = ko.data(), kr.key_len = kl.data();
+    kr.n_rows = nb, kr.key_arena_bytes = ka.size();
+    okv_get_out o;
+    std::memset(&o, 0, sizeof(o));
+    o.state = state.data(), o.blk_status = bst.data(), o.entry = entry.data();
+    o.val_off = voff.data(), o.val_len = vlen.data();
+    // index only: the values are read from the reader's own copy of the storage
+    if (okv_get_rows(r->ctx, r->d_seg, r->data.size(), r->d_index, r->d_bloom, &kr,
+                     r->compression, &o, 0) != OKV_OK)
+      return gpu_failed();
+    {
+      r->io.calls++;
+      r->io.blocks += o.blocks_searched;
+      for (size_t j = 0; j < nb; ++j) {
+        const uint64_t i = batch[j];
+        if (state[j] == OKV_GET_FALLBACK) continue;
+        taken[size_t(i)] = true;
+        switch (state[j]) {
+          case OKV_GET_FOUND:
+            rcs[i] = OKV_OK;
+            held[size_t(i)].on = true;  // bytes.Equal: the row's key is the query's bytes
+            held[size_t(i)].k = r->rows_bytes.size();
+            r->rows_bytes.insert(r->rows_bytes.end(), keys[i], keys[i] + klens[i]);
+            rows[i].key_len = klens[i];
+            rows[i].val_len = vlen[j];
+            rows[i].val = vlen[j] ? r->data.data() + voff[j] : nullptr;  // nil (Q4)
+            break;
+          case OKV_GET_BLOCK_ERROR: rcs[i] = block_rc(bst[j]); break;
+          default: rcs[i] = OKV_R_NO_ROWS; break;  // bloom, no block, not in the block
+        }
+      }
+    }
+  }
+  for (uint64_t i = 0; i < n; ++i)
+    if (!taken[size_t(i)]) single(i);
+  for (uint64_t i = 0; i < n; ++i) {  // the storage is final: pointers
+    const Held& h = held[size_t(i)];
+    if (!h.on) continue;
+    rows[i].key = rows[i].key_len ? r->rows_bytes.data() + h.k : nullptr;  // nil (Q4)
+    if (!taken[size_t(i)])
+      rows[i].val = rows[i].val_len ? r->rows_bytes.data() + h.v : nullptr;
+  }
+  return OKV_OK;
+}
+
 int okv_reader_get_range(okv_reader* r, const uint8_t* start, size_t slen, const uint8_t* end,
                          size_t elen, const okv_row** rows_out, uint64_t* n) {
   int rc = ensure_meta(r);  // GetRange :410-475
@@ -531,6 +696,7 @@ int okv_reader_get_range(okv_reader* r, const uint8_t* start, size_t slen, const
 int okv_reader_close(okv_reader* r) {  // Close :481-487
   if (r->closed) return OKV_R_ALREADY_CLOSED;
   r->closed = true;
+  drop_device(r);
   return OKV_OK;
 }
 

@@ -120,6 +120,23 @@ class SegmentReader:
         _check(lib().okv_reader_get_row(self._h, kb, kl, C.byref(out)))
         return _pair(out)
 
+    def GetRows(self, keys):
+        """GetRow for every key in one GPU call (okv_reader_get_rows): per key the
+        KVPair GetRow returns, or the GoError / GoPanic it raises (returned, not
+        raised)."""
+        ks = [bytes(k or b"") for k in keys]
+        n = len(ks)
+        arr = (C.c_char_p * max(n, 1))(*ks)
+        lens = (C.c_size_t * max(n, 1))(*[len(k) for k in ks])
+        rows = (Row * max(n, 1))()
+        rcs = (C.c_int * max(n, 1))()
+        _check(lib().okv_reader_get_rows(self._h, arr, lens, n, rows, rcs))
+        out = []
+        for i in range(n):
+            rc = rcs[i]
+            out.append(_pair(rows[i]) if rc == 0 else GoPanic(rc) if rc in _PANIC else GoError(rc))
+        return out
+
     def GetRange(self, start, end):
         sb, sl = _buf(start)
         eb, el = _buf(end)
