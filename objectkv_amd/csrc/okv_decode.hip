@@ -1127,18 +1127,6 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(kT <= 16384
 // stage take the global-window gather (same workgroup, same row table code).
 constexpr uint32_t kSmallStage = 5 * 1024;  // staged bytes per block (DMA pieces of 1 KiB)
 
-// Byte source: a block's LDS stage; block byte x at stage byte bias + x.
-struct StageWin {
-  const uint4* s4;
-  uint32_t bias;
-  __device__ __forceinline__ uint4 at(int64_t rel) const {
-    return load16_lds_b128(s4, uint32_t(int64_t(bias) + rel));
-  }
-  __device__ __forceinline__ void header(uint32_t pos, uint32_t& kl, uint32_t& vl) const {
-    header_lds(reinterpret_cast<const uint32_t*>(s4), bias + pos, kl, vl);
-  }
-};
-
 __global__ __launch_bounds__(64) void okv_gather_small_kernel(CopyParams P) {
   __shared__ GatherSmem sm;
   __shared__ uint4 stage[kSmallStage / 16 + 4];
@@ -1155,16 +1143,8 @@ __global__ __launch_bounds__(64) void okv_gather_small_kernel(CopyParams P) {
       // windows that begin before a row, and 32 bytes of slack at the end
       const uint32_t need = 16 + shift + uint32_t(m.c.pend) + 32;
       if (need <= kSmallStage && !P.index_only) {
-        const int64_t D = int64_t(m.off) - int64_t(shift) - 16;
-        const int64_t lim = int64_t(round16(P.seg_bytes));
-        const uint32_t np = (need + 1023) >> 10;
-        for (uint32_t p = 0; p < np; ++p) {
-          int64_t a = D + (int64_t(p) << 10) + int64_t(lane << 4);
-          if (a < 0 || a + 16 > lim) a = int64_t(m.off) & ~int64_t(15);  // bytes never used
-          __builtin_amdgcn_global_load_lds(P.seg + a, OKV_LDS_PTR(stage + p * 64), 16, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const StageWin src{stage, 16 + shift};
+        const Staged src{stage, stage_block_wave(stage, P.seg, P.seg_bytes, m.off,
+                                                 uint32_t(m.c.pend), lane)};
         build_row_table(src, sm, rows, rec);
         write_row_index(P, sm, m, rows);
         gather_region<false>(src, sm, rows, P.key_arena, m.B.kb0, 0, 1);
@@ -1185,7 +1165,7 @@ __global__ __launch_bounds__(64) void okv_gather_small_kernel(CopyParams P) {
 // Single-pass decode for small batches of small blocks (<= kFusedMaxBlocks
 // blocks averaging <= 16 KiB): passes 1-3 in ONE launch.  One wave per block,
 // the block index from blockIdx.x: it DMAs the whole block into LDS, walks its
-// record headers there as the Go loop does (walk_staged; statuses as in
+// record headers there as the Go loop does (walk_staged_to; statuses as in
 // okv_count_kernel) and publishes the block's counts with the call's epoch
 // tag in one packed 8-byte look-back word (fused_pack; counts that do not fit
 // go through F.agg[b]).  Its exclusive prefix is the sum of the words of all
@@ -1286,28 +1266,10 @@ __device__ __forceinline__ bool fused_pack(const Prefix& v, uint32_t& w) {
   return true;
 }
 
-// A small block's header walk (okv_count_kernel's checks in Go's order,
-// segment_reader.go:338-352) from its LDS stage, by the whole wave on a
-// wave-uniform position, run-length speculated (okv_point_kernel's walk):
-// from a record at p of length rl, lane j reads the header at p + j rl -- a
-// record start if every record before it had the same header; the first lane
-// that breaks the run (past OriginalSize, a failed check, another header) is
-// itself a true record start.  A round of two dependent LDS reads confirms 2
-// to 64 records (C2's fixed 86-byte records: all 42 in one round); lane 0
-// alone paid one dependent header decode per record.  Record positions of
-// rows < kRCap go to rec[].  A failed block has no rows (rows = kb = vb = 0)
-// and p at the failing record.
-template <class Src>
-__device__ __forceinline__ void walk_staged(const Src& lsrc, uint32_t L, uint64_t original_size,
-                                            uint32_t* rec, uint32_t lane, int32_t& st,
-                                            uint64_t& rows, uint64_t& kb, uint64_t& vb,
-                                            uint64_t& p) {
-  walk_staged_to(lsrc, L, original_size,
-                 [rec](uint32_t row, uint32_t pos) { if (row < uint32_t(kRCap)) rec[row] = pos; },
-                 lane, st, rows, kb, vb, p);
-}
-// The same walk in HBM by lane 0 (a block too large for the stage); the
-// results are broadcast to the wave.
+// A small block's header walk from its LDS stage is walk_staged_to (okv_kernels.hpp;
+// C2's fixed 86-byte records: all 42 in one round), record positions of rows < kRCap
+// going to rec[] (RecSink).  The same walk in HBM by lane 0 (a block too large for the
+// stage); the results are broadcast to the wave.
 __device__ __forceinline__ void walk_global(const uint8_t* seg, uint64_t off, uint64_t len,
                                             uint64_t original_size, uint32_t* rec, uint32_t lane,
                                             int32_t& st, uint64_t& rows, uint64_t& kb,
@@ -1357,34 +1319,19 @@ __device__ __forceinline__ void fused_pass(const CopyParams& P, const FusedParam
   if (b == 0 && lane == 0) *F.big_zero = 0;
   // ---- pass 1 for this block (okv_count_kernel's rules) ----
   const Desc d = P.descs[b];
-  const uint64_t len = (P.comp == OKV_COMP_LZ4) ? 0 : d.block_size;  // Q7 (:331-333)
+  uint64_t len;
+  int32_t st = entry_status(d, P.seg_bytes, P.comp, F.pre, b, len);
   const uint32_t shift = uint32_t(d.offset & 15);
-  int32_t st = OKV_BLK_OK;
-  {
-    const int32_t pre = F.pre ? F.pre[b] : int32_t(OKV_BLK_OK);
-    if (pre != OKV_BLK_OK) st = pre;  // outcome of the zstd stage
-    else if ((st = go_read_status(d, P.seg_bytes)) != OKV_BLK_OK) {}  // :303-316
-    else if (P.comp == OKV_COMP_ZSTD) st = OKV_BLK_UNSUPPORTED;
-  }
-  const uint32_t need = 16 + shift + uint32_t(len < kSmallStage ? len : kSmallStage) + 32;
   const bool staged = st == OKV_BLK_OK && len + 16 + shift + 32 <= kSmallStage;
-  if (staged && len) {  // the whole block (BlockSize bytes) into the stage
-    const int64_t D = int64_t(d.offset) - int64_t(shift) - 16;
-    const int64_t lim = int64_t(round16(P.seg_bytes));
-    const uint32_t np = (need + 1023) >> 10;
-    for (uint32_t p = 0; p < np; ++p) {
-      int64_t a = D + (int64_t(p) << 10) + int64_t(lane << 4);
-      if (a < 0 || a + 16 > lim) a = int64_t(d.offset) & ~int64_t(15);  // bytes never used
-      __builtin_amdgcn_global_load_lds(P.seg + a, OKV_LDS_PTR(stage + p * 64), 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  if (staged && len)  // the whole block (BlockSize bytes) into the stage
+    stage_block_wave<kSmallStage>(stage, P.seg, P.seg_bytes, d.offset, uint32_t(len), lane);
   __syncthreads();
   OKV_FUSED_STAMP(1);
-  const StageWin lsrc{stage, 16 + shift};
+  const Staged lsrc{stage, 16 + shift};
   uint64_t rows = 0, kb = 0, vb = 0, p = 0;
   if (st == OKV_BLK_OK && staged)
-    walk_staged(lsrc, uint32_t(len), d.original_size, sm.rec, lane, st, rows, kb, vb, p);
+    walk_staged_to(lsrc, uint32_t(len), d.original_size, RecSink{sm.rec, kRCap}, lane, st, rows,
+                   kb, vb, p);
   else if (st == OKV_BLK_OK)  // not stageable: lane 0 walks the headers in HBM
     walk_global(P.seg, d.offset, len, d.original_size, sm.rec, lane, st, rows, kb, vb, p);
   __syncthreads();  // the walk's record positions (sm.rec) are read by every lane below
@@ -1555,18 +1502,6 @@ struct __align__(16) CopySmem {
     FastRows f;
     FindRows k;
   };
-};
-
-// Byte source: the LDS image of the block (byte index = 16 + shift + pos).
-struct LdsSrc {
-  const uint32_t* sw;
-  uint32_t bias;
-  __device__ __forceinline__ void header(uint64_t pos, uint32_t& kl, uint32_t& vl) const {
-    header_lds(sw, bias + uint32_t(pos), kl, vl);
-  }
-  __device__ __forceinline__ uint4 load16(int64_t pos) const {
-    return load16_lds(sw, uint32_t(int64_t(bias) + pos));
-  }
 };
 
 // Byte source: the block in HBM (blocks too large to stage).
@@ -1778,7 +1713,7 @@ __global__ __launch_bounds__(kThreads) void okv_copy_kernel(CopyParams P) {
         materialise_fast(P, sm, 16u + shift, int(c.rows), c.kbytes, c.vbytes, B.row0, B.kb0,
                             B.vb0);
       } else {
-        LdsSrc src{reinterpret_cast<const uint32_t*>(sm.stage), 16u + shift};
+        const Staged src{sm.stage, 16u + shift};
         materialise(src, P, sm, c.rows, c.kbytes, c.vbytes, B.row0, B.kb0, B.vb0, c.pend);
       }
     } else {
@@ -1796,11 +1731,12 @@ __global__ __launch_bounds__(kThreads) void okv_copy_kernel(CopyParams P) {
 // straight from the context's pinned slab and writing every output into it,
 // so the call is one launch and one synchronisation (no H2D / D2H copies,
 // no plan, no totals read-back).  Per block: the block's
-// bytes into LDS (one trip over PCIe), the header walk in LDS by lane 0 with
-// okv_count_kernel's checks in Go's order (:338-352), recording the row table
+// bytes into LDS (one trip over PCIe), the header walk in LDS by wave 0
+// (walk_staged_to: Go's checks in its order, :338-352), recording the row table
 // as it goes, then the SoA rows and both arena regions from LDS (emit_fast;
 // blocks of more than kFastRows rows re-walk in batches, materialise).  The
 // host admits only batches whose OK blocks stage (BlockSize <= kStage).
+// The kernel is its phases: point_block, then point_find or point_rows.
 // ---------------------------------------------------------------------------
 #ifdef OKV_ABLATE
 // (ablation build: wall-clock stamps of the point kernel's phases for the
@@ -1834,252 +1770,177 @@ __device__ __forceinline__ void point_done(const PointFind& F) {
 }
 constexpr uint32_t kFindKey = 8192;  // (held in the row table's prefix arrays)
 
+// What every thread knows of a point call's block once it is staged and walked, and the
+// words wave 0 hands it over in.
+struct PointBlock {
+  Staged src;
+  int32_t st;
+  uint64_t rows, kb, vb, pend;
+};
+struct PointWalk {
+  uint64_t rows, kb, vb, pend;
+  int32_t st;
+};
+
+// Block b into LDS (every 16-byte piece in flight at once -- a load/store loop paid one
+// PCIe round trip per iteration, ~16 for a 64 KiB block), then its header walk by wave 0
+// (lane 0 alone, one dependent header decode per record: 120 ns a record, 80 us of a
+// 64 KiB block's GetRow), the positions of rows < kFastRows into the row table, and the
+// block's outputs at the running prefix `at`.
+__device__ __forceinline__ PointBlock point_block(const CopyParams& P, uint32_t b,
+                                                  const Prefix& at, CopySmem& sm, PointWalk& w) {
+  const uint32_t tid = threadIdx.x;
+  OKV_POINT_STAMP(0);
+  const Desc d = P.descs[b];
+  uint64_t len;
+  const int32_t st0 = entry_status(d, P.seg_bytes, P.comp, nullptr, b, len);
+  const uint32_t L = st0 == OKV_BLK_OK ? uint32_t(len) : 0u;  // <= kStage (point_eligible)
+  const Staged src{sm.stage, stage_block_wg<kThreads>(sm.stage, P.seg, d.offset, L)};
+  __syncthreads();
+  OKV_POINT_STAMP(1);
+  if (tid < 64) {
+    int32_t st = st0;
+    uint64_t rows = 0, kb = 0, vb = 0, pend = 0;
+    if (st == OKV_BLK_OK)
+      walk_staged_to(src, L, d.original_size, RecSink{sm.f.rec, kFastRows}, tid, st, rows, kb, vb,
+                     pend);
+    if (tid == 0) {
+      w = PointWalk{rows, kb, vb, pend, st};
+      P.row_start[b] = at.rows;
+      P.key_base[b] = at.kb;
+      P.val_base[b] = at.vb;
+      P.blk_status[b] = st;
+    }
+  }
+  __syncthreads();
+  OKV_POINT_STAMP(2);
+  return PointBlock{src, w.st, w.rows, w.kb, w.vb, w.pend};
+}
+
+// okv_point_get's answer from its walked block: the first row whose key equals the
+// probe (in LDS, over the prefix arrays: unused by the search) -- one lane per row
+// compares, the lowest index wins -- and only that row's bytes go back.
+__device__ __forceinline__ void point_find(const CopyParams& P, Totals* tot, const PointFind& F,
+                                           const CopySmem& sm, const PointBlock& k) {
+  __shared__ uint32_t s_hit;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) s_hit = ~0u;
+  __syncthreads();
+  const bool ok = k.st == OKV_BLK_OK, listed = k.rows <= uint64_t(kFastRows);
+  if (ok && listed) {
+    const uint32_t* tk = sm.k.key;
+    for (uint32_t i = tid; i < uint32_t(k.rows); i += kThreads)
+      if (key_equal(k.src, sm.f.rec[i], F.klen, [tk](uint32_t j) { return tk[j >> 2]; }))
+        atomicMin(&s_hit, i);
+  }
+  __syncthreads();
+  OKV_POINT_STAMP(3);
+  const uint32_t hit = s_hit;
+  uint32_t kl = 0, vl = 0;
+  if (hit != ~0u) {
+    const uint32_t r0 = sm.f.rec[hit];
+    k.src.header(r0, kl, vl);
+    uint4* ka = reinterpret_cast<uint4*>(P.key_arena);
+    uint4* va = reinterpret_cast<uint4*>(P.val_arena);
+    for (uint32_t c = tid; c < (kl + 15) / 16; c += kThreads) ka[c] = k.src.load16(r0 + 6 + 16 * c);
+    for (uint32_t c = tid; c < (vl + 15) / 16; c += kThreads)
+      va[c] = k.src.load16(r0 + 6 + kl + 16 * c);
+  }
+  if (tid == 0) {
+    *F.found = !ok ? 0 : !listed ? -1 : hit != ~0u ? 1 : 0;
+    P.key_len[0] = uint16_t(kl);
+    P.val_len[0] = vl;
+    *tot = Totals{hit != ~0u ? 1u : 0u, kl, vl, uint64_t(!ok)};
+  }
+  OKV_POINT_STAMP(4);
+}
+
+// A walked block's rows out.  Up to kFastRows rows: the recorded rows' key and value
+// lengths (4 rows a lane), their exclusive prefixes by two workgroup scans (DPP in the
+// wave, the waves' sums through s_wsum), then the SoA rows and both arena regions from
+// LDS (emit_fast).  More rows than the table holds: the batched row tables
+// (materialise), with the walk's byte totals.
+__device__ __forceinline__ void point_rows(const CopyParams& P, CopySmem& sm,
+                                           uint32_t (*s_wsum)[kThreads / 64],
+                                           const PointBlock& k, const Prefix& at) {
+  const uint32_t tid = threadIdx.x;
+  if (k.rows > uint64_t(kFastRows)) {
+    materialise(k.src, P, sm, k.rows, k.kb, k.vb, at.rows, at.kb, at.vb, k.pend);
+    return;
+  }
+  constexpr int kPer = kFastRows / kThreads;
+  const uint32_t rows = uint32_t(k.rows);
+  uint32_t kls[kPer], vls[kPer], ks = 0, vs = 0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t i = tid * kPer + j;
+    kls[j] = vls[j] = 0;
+    if (i < rows) k.src.header(sm.f.rec[i], kls[j], vls[j]);
+    ks += kls[j];
+    vs += vls[j];
+  }
+  const uint32_t ki = wave_scan_dpp(ks), vi = wave_scan_dpp(vs), wave = tid >> 6;
+  if ((tid & 63) == 63) {
+    s_wsum[0][wave] = ki;
+    s_wsum[1][wave] = vi;
+  }
+  __syncthreads();
+  uint32_t kx = ki - ks, vx = vi - vs;
+#pragma unroll
+  for (uint32_t w = 0; w < kThreads / 64; ++w) {
+    kx += w < wave ? s_wsum[0][w] : 0u;
+    vx += w < wave ? s_wsum[1][w] : 0u;
+  }
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t i = tid * kPer + j;
+    if (i < rows) {
+      sm.f.kpre[i] = kx;
+      sm.f.vpre[i] = vx;
+    }
+    kx += kls[j];
+    vx += vls[j];
+  }
+  // (32-bit totals, <= 64 KiB: emit_fast's bytes-per-row divisions stay 32-bit)
+  const uint32_t kb = uint32_t(k.kb), vb = uint32_t(k.vb);
+  if (tid == 0) {
+    sm.f.rec[rows] = uint32_t(k.pend);
+    sm.f.kpre[rows] = kb;
+    sm.f.vpre[rows] = vb;
+  }
+  __syncthreads();
+  OKV_POINT_STAMP(3);
+  emit_fast(P, sm, k.src.bias, int(rows), kb, vb, at.rows, at.kb, at.vb);
+}
+
 template <bool kFind>
 __global__ __launch_bounds__(kThreads) void okv_point_kernel(CopyParams P, Totals* tot,
                                                              PointFind F) {
   __shared__ CopySmem sm;
-  __shared__ uint64_t s_walk[4];  // rows, key bytes, value bytes, walk end
-  __shared__ uint32_t s_wsum[2][kThreads / 64];
-  __shared__ int32_t s_st, s_pst;
-  __shared__ uint32_t s_pw[2];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sm.stage);
-  uint64_t row0 = 0, kb0 = 0, vb0 = 0, bad = 0;  // exclusive prefixes (uniform)
-  if constexpr (kFind) {  // the key into LDS (the prefix arrays: unused by the search)
+  __shared__ PointWalk s_w;
+  Prefix at{0, 0, 0, 0};  // rows, padded key and value bytes, failed blocks so far (uniform)
+  if constexpr (kFind) {  // one block; the key into LDS before the block's barriers
     static_assert(sizeof(sm.k.key) >= kFindKey, "the key fits its LDS array");
     const uint32_t* k4 = reinterpret_cast<const uint32_t*>(F.key);
-    for (uint32_t i = tid; i < (F.klen + 3) / 4; i += kThreads) sm.k.key[i] = k4[i];
-  }
-  for (uint32_t b = 0; b < P.nblk; ++b) {
-    OKV_POINT_STAMP(0);
-    const Desc d = P.descs[b];
-    const int32_t st0 = go_read_status(d, P.seg_bytes);  // :303-316
-    const uint64_t len = P.comp == OKV_COMP_LZ4 ? 0 : d.block_size;  // Q7 (:331-333)
-    const uint32_t shift = uint32_t(d.offset & 15);
-    if (st0 == OKV_BLK_OK && len) {  // stage [offset - shift, offset + len): one trip
-      // (LDS DMA: every 16-byte piece in flight at once -- a load/store loop
-      // paid one PCIe round trip per iteration, ~16 for a 64 KiB block)
-      const uint32_t nch = uint32_t((shift + len + 15) >> 4);
-      const uint8_t* g = P.seg + (d.offset - shift);
-      const uint32_t lane = tid & 63, wave = tid >> 6;
-      for (uint32_t c0 = wave * 64; c0 < nch; c0 += kThreads) {
-        if (c0 + lane < nch)  // (an inactive lane writes no LDS)
-          __builtin_amdgcn_global_load_lds(g + 16ull * (c0 + lane), OKV_LDS_PTR(sm.stage + 1 + c0),
-                                           16, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    OKV_POINT_STAMP(1);
-    const uint32_t bias = 16u + shift;
-    // The header walk (Go's checks in its order) by wave 0 on a wave-uniform
-    // position, run-length speculated: from a record at p of length len, lane
-    // j reads the header at p + j * len -- a record start if every record
-    // before it was len long.  The first lane that breaks the run (past
-    // OriginalSize, a failed check, another length) ends the round; its
-    // position is a true record start, so a round confirms at least two
-    // records (the one at p and the next) and up to 64 when lengths repeat,
-    // for two dependent LDS reads.  (Lane 0 alone, one dependent header
-    // decode per record: 120 ns a record, 80 us of a 64 KiB block's GetRow.)
-    const uint32_t L = st0 == OKV_BLK_OK ? uint32_t(len) : 0u;  // <= kStage
-    const uint64_t orig = go_walk_bound(d.original_size);       // int(OriginalSize) (:340)
-    if (tid < 64) {
-      const uint32_t lane = tid;
-      const uint32_t o32 =
-          __builtin_amdgcn_readfirstlane(uint32_t(min<uint64_t>(orig, 0xffffffffull)));
-      uint32_t p = 0, rows = 0;
-      int32_t pst = st0;
-      if (st0 == OKV_BLK_OK) {
-        while (p < o32) {  // :340
-          uint32_t kl, vl;
-          header_lds(sw, bias + min(p, L), kl, vl);  // (one address: a broadcast)
-          kl = __builtin_amdgcn_readfirstlane(kl);
-          vl = __builtin_amdgcn_readfirstlane(vl);
-          const uint32_t room = L - p - 6;
-          // u16/u32 reads (:342-345), key/value reads (:346-349)
-          if (!((L - p >= 6) & (kl <= room) & (vl <= room - kl))) {
-            pst = OKV_BLK_PANIC;
-            break;
-          }
-          const uint32_t rl = 6 + kl + vl;
-          const uint32_t q = p + lane * rl;  // (< 64 * 64 KiB)
-          uint32_t kj, vj;
-          header_lds(sw, bias + min(q, L), kj, vj);
-          const uint32_t rj = L - q - 6;
-          const bool okj = (q <= L) & (L - q >= 6) & (kj <= rj) & (vj <= rj - kj);
-          const bool brk = lane >= 1 && (q >= o32 || !okj || 6 + kj + vj != rl);
-          const uint64_t bm = __ballot(brk);
-          const uint32_t m = bm ? uint32_t(__builtin_ctzll(bm)) : 64u;  // (>= 1)
-          if (lane < m) sm.f.rec[min(rows + lane, uint32_t(kFastRows))] = q;
-          rows += m;
-          p += m * rl;  // the breaking lane's position: a true record start
-          if (m == 64 || p >= o32) continue;
-          const uint32_t okm = __builtin_amdgcn_readlane(uint32_t(okj), m);
-          const uint32_t lm = __builtin_amdgcn_readlane(6 + kj + vj, m);
-          if (!okm) {
-            pst = OKV_BLK_PANIC;
-            break;
-          }
-          if (lane == 0) sm.f.rec[min(rows, uint32_t(kFastRows))] = p;
-          ++rows;
-          p += lm;
-        }
-      }
-      if (tid == 0) {
-        s_pw[0] = p;
-        s_pw[1] = rows;
-        s_pst = pst;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int32_t st = s_pst;
-      uint32_t rows = s_pw[1], p = s_pw[0];
-      // a walk that reached the block end short of OriginalSize: the header read (:342-345)
-      if (st == OKV_BLK_OK && p < orig) st = OKV_BLK_PANIC;
-      if (st != OKV_BLK_OK) rows = p = 0;  // a failed block has no rows
-      s_walk[0] = rows;
-      s_walk[3] = p;
-      s_st = st;
-      P.row_start[b] = row0;
-      P.key_base[b] = kb0;
-      P.val_base[b] = vb0;
-      P.blk_status[b] = st;
-    }
-    __syncthreads();
-    OKV_POINT_STAMP(2);
-    const uint64_t rows = s_walk[0], pend = s_walk[3];
-    const int32_t st = s_st;
-    uint64_t kb = 0, vb = 0;
-    if constexpr (kFind) {
-      // the first row whose key equals F.key: one lane per row compares in
-      // LDS, the lowest index wins; only that row's bytes go back
-      __shared__ uint32_t s_hit;
-      if (tid == 0) s_hit = ~0u;
-      __syncthreads();
-      const bool listed = rows <= uint64_t(kFastRows);
-      if (st == OKV_BLK_OK && listed) {
-        const uint32_t* tk = sm.k.key;
-        for (uint32_t i = tid; i < uint32_t(rows); i += kThreads) {
-          uint32_t kl, vl;
-          header_lds(sw, bias + sm.f.rec[i], kl, vl);
-          if (kl != F.klen) continue;
-          const uint32_t kp = bias + sm.f.rec[i] + 6;
-          bool eq = true;
-          for (uint32_t j = 0; j < kl && eq; j += 4) {
-            const uint32_t bi = kp + j, sh = bi & 3;
-            const uint32_t a = funnel(sw[(bi >> 2) + 1], sw[bi >> 2], sh);
-            const uint32_t n = min(4u, kl - j);
-            const uint32_t m = n == 4 ? ~0u : (1u << (8 * n)) - 1u;
-            eq = ((a ^ tk[j >> 2]) & m) == 0;
-          }
-          if (eq) atomicMin(&s_hit, i);
-        }
-      }
-      __syncthreads();
-      OKV_POINT_STAMP(3);
-      const uint32_t hit = s_hit;
-      uint32_t kl = 0, vl = 0;
-      if (hit != ~0u) {
-        const uint32_t r0 = bias + sm.f.rec[hit];
-        header_lds(sw, r0, kl, vl);
-        uint4* ka = reinterpret_cast<uint4*>(P.key_arena);
-        uint4* va = reinterpret_cast<uint4*>(P.val_arena);
-        for (uint32_t c = tid; c < (kl + 15) / 16; c += kThreads) ka[c] = load16_lds(sw, r0 + 6 + 16 * c);
-        for (uint32_t c = tid; c < (vl + 15) / 16; c += kThreads)
-          va[c] = load16_lds(sw, r0 + 6 + kl + 16 * c);
-      }
-      if (tid == 0) {
-        *F.found = st != OKV_BLK_OK ? 0 : !listed ? -1 : hit != ~0u ? 1 : 0;
-        P.key_len[0] = uint16_t(kl);
-        P.val_len[0] = vl;
-        *tot = Totals{hit != ~0u ? 1u : 0u, kl, vl, uint64_t(st != OKV_BLK_OK)};
-      }
+    for (uint32_t i = threadIdx.x; i < (F.klen + 3) / 4; i += kThreads) sm.k.key[i] = k4[i];
+    point_find(P, tot, F, sm, point_block(P, 0, at, sm, s_w));
+  } else {
+    __shared__ uint32_t s_wsum[2][kThreads / 64];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t b = 0; b < P.nblk; ++b) {
+      const PointBlock k = point_block(P, b, at, sm, s_w);
+      if (k.st == OKV_BLK_OK && k.rows) point_rows(P, sm, s_wsum, k, at);
+      at.rows += k.rows;
+      at.kb += round16(k.kb);
+      at.vb += round16(k.vb);
+      at.bad += k.st != OKV_BLK_OK;
+      __syncthreads();  // the stage and the row table are reused by the next block
       OKV_POINT_STAMP(4);
-      point_done(F);
-      return;  // (one block)
     }
-    if (st == OKV_BLK_OK && rows) {
-      if (rows <= uint64_t(kFastRows)) {
-        // key / value lengths of the recorded rows, exclusive prefixes (4 rows a lane)
-        constexpr int kPer = kFastRows / kThreads;
-        uint32_t kls[kPer], vls[kPer], ks = 0, vs = 0;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-          const uint32_t i = tid * kPer + j;
-          kls[j] = vls[j] = 0;
-          if (i < rows) header_lds(sw, bias + sm.f.rec[i], kls[j], vls[j]);
-          ks += kls[j];
-          vs += vls[j];
-        }
-        const uint32_t ki = wave_scan_dpp(ks), vi = wave_scan_dpp(vs);
-        const uint32_t wave = tid >> 6;
-        if ((tid & 63) == 63) {
-          s_wsum[0][wave] = ki;
-          s_wsum[1][wave] = vi;
-        }
-        __syncthreads();
-        uint32_t kx = ki - ks, vx = vi - vs;
-        uint32_t ktot = 0, vtot = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kThreads / 64; ++w) {
-          kx += w < wave ? s_wsum[0][w] : 0u;
-          vx += w < wave ? s_wsum[1][w] : 0u;
-          ktot += s_wsum[0][w];
-          vtot += s_wsum[1][w];
-        }
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-          const uint32_t i = tid * kPer + j;
-          if (i < rows) {
-            sm.f.kpre[i] = kx;
-            sm.f.vpre[i] = vx;
-          }
-          kx += kls[j];
-          vx += vls[j];
-        }
-        if (tid == 0) {
-          sm.f.rec[rows] = uint32_t(pend);
-          sm.f.kpre[rows] = ktot;
-          sm.f.vpre[rows] = vtot;
-        }
-        kb = ktot;
-        vb = vtot;
-        __syncthreads();
-        OKV_POINT_STAMP(3);
-        emit_fast(P, sm, bias, int(rows), kb, vb, row0, kb0, vb0);
-      } else {
-        // more rows than the row table holds: the byte totals by a second
-        // walk (the block passed its checks), then the batched row tables
-        if (tid == 0) {
-          uint64_t k = 0, v = 0;
-          for (uint32_t q = 0; q < uint32_t(pend);) {
-            uint32_t kl, vl;
-            header_lds(sw, bias + q, kl, vl);
-            k += kl;
-            v += vl;
-            q += 6 + kl + vl;
-          }
-          s_walk[1] = k;
-          s_walk[2] = v;
-        }
-        __syncthreads();
-        kb = s_walk[1];
-        vb = s_walk[2];
-        LdsSrc src{sw, bias};
-        materialise(src, P, sm, rows, kb, vb, row0, kb0, vb0, pend);
-      }
+    if (tid == 0) {
+      P.row_start[P.nblk] = at.rows;
+      *tot = Totals{at.rows, at.kb, at.vb, at.bad};
     }
-    row0 += rows;
-    kb0 += round16(kb);
-    vb0 += round16(vb);
-    bad += st != OKV_BLK_OK;
-    __syncthreads();  // the stage and the row table are reused by the next block
-    OKV_POINT_STAMP(4);
-  }
-  if (tid == 0) {
-    P.row_start[P.nblk] = row0;
-    *tot = Totals{row0, kb0, vb0, bad};
   }
   point_done(F);
 }

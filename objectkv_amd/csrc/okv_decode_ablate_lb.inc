@@ -227,7 +227,7 @@ okv_block_kernel(CopyParams P, FusedParams F) {
   if (staged && rows <= uint64_t(kFastRows)) {
     emit_fast(P, sm, bias, int(rows), kb, vb, B.row0, B.kb0, B.vb0);
   } else if (staged) {
-    LdsSrc src{reinterpret_cast<const uint32_t*>(sm.stage), bias};
+    const Staged src{sm.stage, bias};
     materialise(src, P, sm, rows, kb, vb, B.row0, B.kb0, B.vb0, pend);
   } else {
     GlobalSrc src{P.seg, P.seg_bytes, off};
@@ -241,7 +241,7 @@ okv_block_kernel(CopyParams P, FusedParams F) {
 // compaction feed's 386 K x 4 KiB segments): each block's bytes are read from
 // HBM once.  One 256-thread workgroup per group of kGroup consecutive blocks:
 //   1. every wave DMAs its four blocks into their LDS slots (64 KiB of the
-//      group in flight at once) and walks their headers there (walk_staged,
+//      group in flight at once) and walks their headers there (walk_staged_to,
 //      Go's checks in Go's order);
 //   2. the group's counts go out as an aggregate, and wave 0 sums its
 //      predecessors' by a decoupled look-back over 64 groups per round
@@ -301,12 +301,8 @@ __global__ __launch_bounds__(kThreads) void okv_group_kernel(CopyParams P, Group
     if (lb >= nb) break;
     const uint32_t b = b0 + lb;
     const Desc d = P.descs[b];
-    int32_t st = OKV_BLK_OK;
-    const int32_t pre = G.pre ? G.pre[b] : int32_t(OKV_BLK_OK);
-    if (pre != OKV_BLK_OK) st = pre;  // outcome of the zstd stage
-    else if ((st = go_read_status(d, P.seg_bytes)) != OKV_BLK_OK) {}  // :303-316
-    else if (P.comp == OKV_COMP_ZSTD) st = OKV_BLK_UNSUPPORTED;
-    const uint64_t len = (P.comp == OKV_COMP_LZ4) ? 0 : d.block_size;  // Q7 (:331-333)
+    uint64_t len;
+    const int32_t st = entry_status(d, P.seg_bytes, P.comp, G.pre, b, len);
     const uint32_t shift = uint32_t(d.offset & 15);
     const bool staged = st == OKV_BLK_OK && len + 16 + shift + 32 <= kGroupSlot;
     if (lane == 0) {
@@ -337,8 +333,9 @@ __global__ __launch_bounds__(kThreads) void okv_group_kernel(CopyParams P, Group
     uint64_t rows = 0, kb = 0, vb = 0, p = 0;
     const uint64_t len = (P.comp == OKV_COMP_LZ4) ? 0 : d.block_size;
     if (st == OKV_BLK_OK && sm.staged[lb]) {
-      const StageWin lsrc{&sm.stage[lb][0], 16 + uint32_t(d.offset & 15)};
-      walk_staged(lsrc, uint32_t(len), d.original_size, sm.rec[lb], lane, st, rows, kb, vb, p);
+      const Staged lsrc{&sm.stage[lb][0], 16 + uint32_t(d.offset & 15)};
+      walk_staged_to(lsrc, uint32_t(len), d.original_size, RecSink{sm.rec[lb], kRCap}, lane, st,
+                     rows, kb, vb, p);
     } else if (st == OKV_BLK_OK) {
       walk_global(P.seg, d.offset, len, d.original_size, sm.rec[lb], lane, st, rows, kb, vb, p);
     }
@@ -446,7 +443,7 @@ __global__ __launch_bounds__(kThreads) void okv_group_kernel(CopyParams P, Group
       P.val_off[gr] = m.B.vb0 + gs.vpre[lane];
     };
     if (sm.staged[lb]) {
-      const StageWin src{&sm.stage[lb][0], 16 + uint32_t(m.off & 15)};
+      const Staged src{&sm.stage[lb][0], 16 + uint32_t(m.off & 15)};
       build_row_table(src, gs, nr, rec);
       row_index();
       gather_region<false>(src, gs, nr, P.key_arena, m.B.kb0, 0, 1);

@@ -238,33 +238,12 @@ struct __align__(16) SearchSmem {
   uint16_t rec[kCap / 6 + 2];            // every record's position (< 64 KiB)
 };
 
-struct StageSrc {  // block byte x at LDS byte bias + x
-  const uint32_t* sw;
-  uint32_t bias;
-  __device__ __forceinline__ void header(uint32_t pos, uint32_t& kl, uint32_t& vl) const {
-    header_lds(sw, bias + pos, kl, vl);
-  }
-};
-
-// Key bytes [j, j + 4) (j < kl) from the aligned dwords that contain a key byte; bytes
-// past the key are unspecified.
-__device__ __forceinline__ uint32_t key_dword(const uint8_t* key, uint32_t kl, uint32_t j) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(key + j);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3));
-  const uint32_t sh = uint32_t(a & 3);
-  const uint32_t w0 = w[0];
-  const uint32_t w1 =
-      (sh && reinterpret_cast<const uint8_t*>(w + 1) < key + kl) ? w[1] : 0u;
-  return funnel(w1, w0, sh);
-}
-
 template <uint32_t kCap>
 __global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P) {
   __shared__ SearchSmem<kCap> sm;
   __shared__ int32_t s_st;
   __shared__ uint32_t s_rows;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sm.stage);
   const uint32_t touched = uint32_t(P.gscan[P.ix.nt] >> 32);
   for (uint32_t w = blockIdx.x; w < touched; w += gridDim.x) {
     const uint32_t t = P.work[w];
@@ -274,24 +253,13 @@ __global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P
     // the block passed go_read_status in the locate kernel: its BlockSize bytes are
     // in the segment.  Q7 (:331-333): the LZ4 flag decodes an empty buffer
     const uint32_t L = P.comp == OKV_COMP_LZ4 ? 0u : uint32_t(d.block_size);
-    const uint32_t shift = uint32_t(d.offset & 15);
-    if (L) {  // stage [offset - shift, offset + L) in 16-byte pieces, all in flight
-      const uint32_t nch = (shift + L + 15) >> 4;
-      const uint8_t* g = P.seg + (d.offset - shift);
-      for (uint32_t c0 = wave * 64; c0 < nch; c0 += kSearchThreads) {
-        if (c0 + lane < nch)  // (an inactive lane writes no LDS)
-          __builtin_amdgcn_global_load_lds(g + 16ull * (c0 + lane), OKV_LDS_PTR(sm.stage + 1 + c0),
-                                           16, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    const Staged src{sm.stage, stage_block_wg<kSearchThreads>(sm.stage, P.seg, d.offset, L)};
     __syncthreads();
-    const uint32_t bias = 16u + shift;
     if (tid < 64) {  // ReadBlockWithStat's record loop (:338-352) in full, by wave 0
       int32_t st = OKV_BLK_OK;
       uint64_t rows = 0, kb = 0, vb = 0, pend = 0;
       uint16_t* rec = sm.rec;
-      walk_staged_to(StageSrc{sw, bias}, L, d.original_size,
+      walk_staged_to(src, L, d.original_size,
                      [rec](uint32_t row, uint32_t pos) { rec[row] = uint16_t(pos); }, lane, st,
                      rows, kb, vb, pend);
       if (lane == 0) {
@@ -317,20 +285,9 @@ __global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P
       uint32_t hit = kNone;
       for (uint32_t r0 = 0; r0 < rows; r0 += 64) {
         const uint32_t r = r0 + lane;
-        bool eq = false;
-        if (r < rows) {
-          const uint32_t at = bias + sm.rec[r];
-          uint32_t rkl, rvl;
-          header_lds(sw, at, rkl, rvl);
-          eq = rkl == kl;  // bytes.Equal (:398): the lengths, then the bytes
-          for (uint32_t b = 0; b < kl && eq; b += 4) {
-            const uint32_t bi = at + 6 + b, sh = bi & 3;
-            const uint32_t a = funnel(sw[(bi >> 2) + 1], sw[bi >> 2], sh);
-            const uint32_t nb = min(4u, kl - b);
-            const uint32_t m = nb == 4 ? ~0u : (1u << (8 * nb)) - 1u;
-            eq = ((a ^ key_dword(key, kl, b)) & m) == 0;
-          }
-        }
+        const bool eq = r < rows && key_equal(src, sm.rec[r], kl, [key, kl](uint32_t b) {
+                          return key_dword(key, kl, b);
+                        });
         const uint64_t bm = __ballot(eq);
         if (bm) {  // the lowest matching row of the earliest round: the first in block order
           hit = r0 + uint32_t(__builtin_ctzll(bm));
@@ -340,7 +297,7 @@ __global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P
       if (lane == 0 && hit != kNone) {
         const uint32_t pos = sm.rec[hit];
         uint32_t rkl, rvl;
-        header_lds(sw, bias + pos, rkl, rvl);
+        src.header(pos, rkl, rvl);
         P.state[i] = OKV_GET_FOUND;
         P.val_off[i] = d.offset + pos + 6 + rkl;
         P.val_len[i] = rvl;

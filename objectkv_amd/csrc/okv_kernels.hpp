@@ -317,6 +317,114 @@ __device__ __forceinline__ uint64_t wg_excl_scan(uint64_t v, uint64_t* sm, uint6
   return before + inc - v;
 }
 
+// A block's status before its walk, in every kernel's order: the zstd stage's outcome
+// (pre, or null), the raw read (:303-316), then zstd bytes nobody decompressed.  len is
+// the walk's buffer: BlockSize bytes, or none under the LZ4 flag (Q7, :331-333).
+__device__ __forceinline__ int32_t entry_status(const Desc& d, uint64_t seg_bytes, int comp,
+                                                const int32_t* pre, uint32_t b, uint64_t& len) {
+  len = comp == OKV_COMP_LZ4 ? 0 : d.block_size;
+  int32_t st = pre ? pre[b] : int32_t(OKV_BLK_OK);
+  if (st == OKV_BLK_OK) st = go_read_status(d, seg_bytes);
+  if (st == OKV_BLK_OK && comp == OKV_COMP_ZSTD) st = OKV_BLK_UNSUPPORTED;
+  return st;
+}
+
+// ---------------------------------------------------------------------------
+// A block staged in LDS: block byte x lives at stage byte bias + x, with
+// bias = 16 + (offset & 15) -- the block's 16-byte lines land on the stage's, after one
+// guard line for windows that begin before a row.
+// ---------------------------------------------------------------------------
+struct Staged {  // the byte source of every kernel that works from a staged block
+  const uint4* s4;
+  uint32_t bias;
+  __device__ __forceinline__ const uint32_t* sw() const {
+    return reinterpret_cast<const uint32_t*>(s4);
+  }
+  __device__ __forceinline__ void header(uint32_t pos, uint32_t& kl, uint32_t& vl) const {
+    header_lds(sw(), bias + pos, kl, vl);
+  }
+  // 16 bytes at block byte rel (may be < 0): the b128 form (gather_*) ...
+  __device__ __forceinline__ uint4 at(int64_t rel) const {
+    return load16_lds_b128(s4, uint32_t(int64_t(bias) + rel));
+  }
+  // ... and the dword form (materialise / copy_region, the point get's row)
+  __device__ __forceinline__ uint4 load16(int64_t pos) const {
+    return load16_lds(sw(), uint32_t(int64_t(bias) + pos));
+  }
+};
+
+// Both staging forms issue the block's LDS DMA, wait for it (the caller's barrier makes
+// it visible to the other waves) and return bias.
+// Workgroup form (kNT threads): [offset - shift, offset + len) from stage line 1, every
+// 16-byte piece in flight at once.  The stage holds len + kStagePad bytes.
+template <uint32_t kNT>
+__device__ __forceinline__ uint32_t stage_block_wg(uint4* stage, const uint8_t* seg,
+                                                   uint64_t offset, uint32_t len) {
+  const uint32_t shift = uint32_t(offset & 15);
+  if (len) {
+    const uint32_t nch = (shift + len + 15) >> 4;
+    const uint8_t* g = seg + (offset - shift);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t c0 = wave * 64; c0 < nch; c0 += kNT) {
+      if (c0 + lane < nch)  // (an inactive lane writes no LDS)
+        __builtin_amdgcn_global_load_lds(g + 16ull * (c0 + lane), OKV_LDS_PTR(stage + 1 + c0), 16,
+                                         0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  return 16 + shift;
+}
+// One-wave form: [offset - shift - 16, offset + len + 32) from stage line 0 in 1 KiB
+// pieces -- the lead-in and 32 bytes of slack are real segment bytes where there are
+// any.  The caller has checked that they fit its stage; kMaxLen, where given, only
+// tells the compiler so (a short piece loop, not one unrolled by eight).
+template <uint32_t kMaxLen = 0xffffffffu>
+__device__ __forceinline__ uint32_t stage_block_wave(uint4* stage, const uint8_t* seg,
+                                                     uint64_t seg_bytes, uint64_t offset,
+                                                     uint32_t len, uint32_t lane) {
+  const uint32_t shift = uint32_t(offset & 15);
+  const int64_t D = int64_t(offset) - int64_t(shift) - 16;
+  const int64_t lim = int64_t(round16(seg_bytes));
+  const uint32_t np = (16 + shift + min(len, kMaxLen) + 32 + 1023) >> 10;
+  for (uint32_t p = 0; p < np; ++p) {
+    int64_t a = D + (int64_t(p) << 10) + int64_t(lane << 4);
+    if (a < 0 || a + 16 > lim) a = int64_t(offset) & ~int64_t(15);  // bytes never used
+    __builtin_amdgcn_global_load_lds(seg + a, OKV_LDS_PTR(stage + p * 64), 16, 0, 0);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  return 16 + shift;
+}
+
+// bytes.Equal (:398) of the staged record at block byte pos with a probe key of kl
+// bytes: the lengths, then the bytes, four at a time.  probe(j) gives probe bytes
+// [j, j + 4), j a multiple of 4; bytes past kl are masked.
+template <class Probe>
+__device__ __forceinline__ bool key_equal(const Staged& s, uint32_t pos, uint32_t kl,
+                                          Probe probe) {
+  uint32_t rkl, rvl;
+  s.header(pos, rkl, rvl);
+  bool eq = rkl == kl;
+  const uint32_t* sw = s.sw();
+  for (uint32_t j = 0; j < kl && eq; j += 4) {
+    const uint32_t bi = s.bias + pos + 6 + j, sh = bi & 3;
+    const uint32_t a = funnel(sw[(bi >> 2) + 1], sw[bi >> 2], sh);
+    const uint32_t n = min(4u, kl - j);
+    const uint32_t m = n == 4 ? ~0u : (1u << (8 * n)) - 1u;
+    eq = ((a ^ probe(j)) & m) == 0;
+  }
+  return eq;
+}
+// Bytes [j, j + 4) (j < kl) of a key in global memory, from the aligned dwords that
+// contain a key byte; bytes past the key are unspecified.
+__device__ __forceinline__ uint32_t key_dword(const uint8_t* key, uint32_t kl, uint32_t j) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(key + j);
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3));
+  const uint32_t sh = uint32_t(a & 3);
+  const uint32_t w0 = w[0];
+  const uint32_t w1 = (sh && reinterpret_cast<const uint8_t*>(w + 1) < key + kl) ? w[1] : 0u;
+  return funnel(w1, w0, sh);
+}
+
 // A staged block's header walk (Go's checks in its order, segment_reader.go:338-352)
 // from its LDS image, by one whole wave on a wave-uniform position, run-length
 // speculated: from a record at p of length rl, lane j reads the header at p + j rl -- a
@@ -327,6 +435,13 @@ __device__ __forceinline__ uint64_t wg_excl_scan(uint64_t v, uint64_t* sm, uint6
 // length, <= 64 KiB); sink(row, pos) takes every record's position, in any order,
 // from the lane that found it.  A failed block has no rows (rows = kb = vb = 0) and p
 // at the failing record.  The loop runs at most L / 6 + 1 rounds.
+struct RecSink {  // the usual sink: positions of rows < cap into a row table
+  uint32_t* rec;
+  uint32_t cap;
+  __device__ __forceinline__ void operator()(uint32_t row, uint32_t pos) const {
+    if (row < cap) rec[row] = pos;
+  }
+};
 template <class Src, class Sink>
 __device__ __forceinline__ void walk_staged_to(const Src& lsrc, uint32_t L, uint64_t original_size,
                                                Sink sink, uint32_t lane, int32_t& st,

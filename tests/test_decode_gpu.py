@@ -11,6 +11,7 @@ import pytest
 import objectkv_amd as okv
 from objectkv_amd import _lib
 from oracle import coracle as CO
+from tests import staged_cases as SC
 from tests.conftest import descs_of, rowval, unpack
 
 pytestmark = pytest.mark.gpu
@@ -405,6 +406,27 @@ def test_mixed_blocks_all_paths(decoder, nofused_decoder, nopoint_decoder, path)
     for index_only in (False, True):
         got, seg2 = decode_path(path, decoder, nofused_decoder, seg, d, index_only=index_only, nopoint=nopoint_decoder)
         _assert_same_as_oracle(got, seg2, d, 0, index_only)
+
+
+@pytest.mark.parametrize("path", PATHS)
+def test_staged_cases_all_paths(decoder, nofused_decoder, nopoint_decoder, path):
+    """The walk and staging cases of tests/staged_cases.py (run lengths around a wave,
+    equal lengths under other headers, bad records inside a run, OriginalSize against
+    the run, the row table's edge, offsets & 15 of 0 / 1 / 15 from the segment's first
+    byte to its last, the one-wave stage filled to the byte and one byte past it, a
+    64 KiB block whose stage ends in a partial piece), full and index-only, through
+    every shipping path vs the oracle."""
+    for name in SC.WALK + SC.STAGING:
+        seg, d, _keys = SC.cases()[name]
+        for index_only in (False, True):
+            got, seg2 = decode_path(path, decoder, nofused_decoder, seg, d, index_only=index_only,
+                                    nopoint=nopoint_decoder)
+            _assert_same_as_oracle(got, seg2, d, 0, index_only)
+            if name == "small_stage_edge" and not index_only:  # the one-wave stage's kernels ran
+                if path == "fused":
+                    assert nopoint_decoder.last_path() & _lib.PATH_FUSED
+                if path == "nofused":
+                    assert nofused_decoder.last_path() & _lib.PATH_SMALL
 
 
 @pytest.mark.parametrize("nblk", [255, 256, 257, 513])

@@ -19,6 +19,7 @@ from oracle import bloom_ref as B
 from oracle import coracle as CO
 from oracle import pyoracle as P
 from tests import index_cases as IC
+from tests import staged_cases as SC
 from tests.conftest import descs_of, unpack
 from tests.test_point_gpu import _bloom_segment, _expect_get
 
@@ -247,6 +248,64 @@ def test_many_rows(decoder):
     res = _check_block(decoder, dseg, seg, d2, 0, [b"", b"\x00", b"x"])
     assert [int(s) for s in res.state] == [FOUND, NOT_IN_BLOCK, NOT_IN_BLOCK]
     assert int(res.val_off[0]) == len(body1) + 6 and res.value(0) is None
+
+
+def _one_block_reader(seg, d):
+    """The oracle's reader over seg with d as its only block (FirstKey empty)."""
+    st = P.BlockStat(FirstKey=b"", Offset=int(d[0]), BlockSize=int(d[1]), OriginalSize=int(d[2]))
+    md = P.SegmentMetadata()
+    md.entries.append(st)
+    md.BlockIndex.replace_or_insert(st)
+    orr = P.SegmentReader(seg, len(seg))
+    orr.LoadCachedMetadata(md)
+    return orr
+
+
+@pytest.mark.parametrize("name", SC.WALK + SC.STAGING + SC.KEYS)
+def test_staged_cases(decoder, name):
+    """tests/staged_cases.py through okv_get_rows, each block as the floor of every probe
+    key: == the oracle's GetRow (_oracle_state) and its ReadBlockWithStat + row loop --
+    runs of 1 to 129 equal records, a bad record inside a run failing every key of its
+    block, OriginalSize against the run, 1 023 to 1 025 rows, offsets & 15 of 0 / 1 / 15,
+    8 192- and 8 193-byte blocks (the two kCap forms), a 64 KiB block at offset & 15 ==
+    15, probe keys of 0 to 8 192 bytes, all but the last byte, prefixes, duplicates."""
+    seg, d, keys = SC.cases()[name]
+    dseg = _dev(seg)
+    for row in d:
+        res = _check_block(decoder, dseg, seg, row, 0, keys)
+        _same_as_oracle(res, keys, _one_block_reader(seg, row))
+        if name == "bad_in_run":
+            assert all((int(s), int(b)) == (BLOCK_ERROR, _lib.BLK_PANIC)
+                       for s, b in zip(res.state, res.blk_status))
+    if name == "keys":
+        assert res.n_found >= 8 and res.value(keys.index(b"dup")) == b"first"
+
+
+def test_probe_keys_at_every_arena_alignment(decoder):
+    """The probe keys packed back to back so that they start at arena offsets & 3 of 0,
+    1, 2 and 3, the last one ending on the arena's last byte (no pad after it): the same
+    outcomes as key by key."""
+    seg, d, keys = SC.cases()["keys"]
+    ks = [k for k in keys if 0 < len(k) <= 256]
+    hit5 = [k for k in ks if len(k) == 5][0]
+    ks.append(b"dup")
+    while sum(len(k) for k in ks) & 3 != 3:
+        ks.append(b"x")
+    ks.append(hit5)  # starts at offset & 3 == 3, ends the arena
+    pk = pack_keys(ks)
+    total = int(pk["key_off"][-1]) + len(ks[-1])
+    pk["key_arena"] = np.ascontiguousarray(pk["key_arena"][:total])
+    assert {int(o) & 3 for o, k in zip(pk["key_off"], ks) if len(k) >= 4} == {0, 1, 2, 3}
+    assert int(pk["key_off"][-1]) & 3 and len(ks[-1]) == 5
+    dseg = _dev(seg)
+    ix = okv.DeviceIndex(decoder, d, [b""])
+    res = G.get_rows(decoder, dseg[0], dseg[1], ix, pk)
+    one = _get(decoder, dseg, ix, ks)
+    ix.close()
+    _same_as_oracle(res, ks, _one_block_reader(seg, d[0]))
+    assert int(res.state[-1]) == FOUND
+    for f in ("state", "blk_status", "val_off", "val_len"):
+        assert list(getattr(res, f)) == list(getattr(one, f)), f
 
 
 def test_bloom_default_filter(decoder):

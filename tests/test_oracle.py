@@ -214,6 +214,75 @@ def test_random_blocks_restatements_agree():
         _cmp_soa(bytes(seg), descs, rng.choice([0, 0, 2]))
 
 
+def test_staged_cases_oracles_agree_and_cases_are_what_they_claim():
+    """tests/staged_cases.py (the inputs of the staged-block GPU tests): the C and the
+    Python oracle agree on every case, and the cases have the properties they are named
+    for -- run lengths, row counts at the row table's edge, the bad record's lane,
+    OriginalSize against the run, offsets and the two stages filled to the byte."""
+    from tests import staged_cases as SC
+    cs = SC.cases()
+    assert set(cs) == set(SC.WALK + SC.STAGING + SC.KEYS)
+    assert sum(len(seg) for seg, _d, _k in cs.values()) < 512 << 10
+    ref = {}
+    for name, (seg, d, keys) in cs.items():
+        assert len(seg) <= 512 << 10 and d.shape[0] <= 16  # a point-path call
+        assert all(int(x[1]) <= SC.STAGE for x in d) and keys
+        _cmp_soa(seg, d, P.COMP_NONE)
+        ref[name] = P.decode_soa(seg, [tuple(int(x) for x in r) for r in d], P.COMP_NONE)
+    rows = lambda n: np.diff(ref[n]["row_start"]).tolist()  # noqa: E731
+    ok = lambda n: set(ref[n]["status"]) == {P.BLK_OK}  # noqa: E731
+
+    assert ok("runs") and rows("runs") == [n + 1 for n in SC.RUNS]
+    for (seg, d, _k), n in ((cs["runs"], n) for n in SC.RUNS):
+        b = SC.RUNS.index(n)
+        body = seg[int(d[b][0]):int(d[b][0] + d[b][1])]
+        assert body[:11 * n] == body[:11] * n and body[11 * n:11 * n + 6] != body[:6]
+        assert len(body) == 11 * n + 6 + 5 + 9  # ... the different record, the block's end
+    r = ref["same_length_other_header"]
+    lens = list(zip(r["key_len"], r["val_len"]))
+    assert ok("same_length_other_header") and {k + v for k, v in lens} == {8}
+    assert lens[:4] == [(3, 5), (5, 3), (4, 4), (0, 8)] and lens[-3:] == [(3, 5)] * 3
+    assert ref["bad_in_run"]["status"] == [P.BLK_PANIC] * 9 and sum(rows("bad_in_run")) == 0
+    seg, d, _k = cs["bad_in_run"]
+    for b, lane in enumerate(l for l in SC.BAD_LANES for _ in range(3)):
+        body = seg[int(d[b][0]):int(d[b][0] + d[b][1])]
+        assert body[:11 * lane] == body[:11] * lane and len(body) - 11 * lane in (11, 5)
+    r = ref["original_size"]
+    assert r["status"] == [0, 0, 0, 0, 0, P.BLK_PANIC]
+    assert rows("original_size") == [10, 4, 0, 0, 0, 0]
+    assert ok("fast_rows_edge")
+    assert rows("fast_rows_edge") == [SC.FAST_ROWS - 1, SC.FAST_ROWS, SC.FAST_ROWS + 1]
+    assert min(ref["fast_rows_edge"]["key_len"]) > 0 and min(ref["fast_rows_edge"]["val_len"]) > 0
+    assert len(set(zip(ref["fast_rows_edge"]["key_len"], ref["fast_rows_edge"]["val_len"]))) > 20
+
+    seg, d, _k = cs["offsets"]
+    assert ok("offsets") and [int(x[0]) & 15 for x in d] == [0, 1, 15, 1] and int(d[0][0]) == 0
+    assert int(d[-1][0] + d[-1][1]) == len(seg) and len(seg) % 16 != 0
+    seg, d, _k = cs["small_stage_edge"]
+    need = [SC.small_need(int(x[0]), int(x[1])) for x in d]
+    assert ok("small_stage_edge") and all(n <= SC.RCAP for n in rows("small_stage_edge"))
+    assert need == [SC.SMALL_STAGE, SC.SMALL_STAGE + 1] * 2
+    assert [int(x[0]) & 15 for x in d] == [0, 0, 15, 15]
+    seg, d, _k = cs["stage_last_piece"]
+    assert ok("stage_last_piece") and int(d[0][1]) == SC.STAGE and int(d[0][0]) & 15 == 15
+    assert ok("get_caps") and [int(x[1]) for x in cs["get_caps"][1]] == [8192, 8193]
+    assert SC.GET_CAPS[0] == 8192
+
+    seg, d, keys = cs["keys"]
+    r = ref["keys"]
+    assert ok("keys") and {0, 1, 3, 4, 5, 255, 256, SC.FIND_KEY} <= {len(k) for k in keys}
+    ka = r["key_arena"]
+    have = [ka[o:o + n] for o, n in zip(r["key_off"], r["key_len"])]
+    assert have.count(b"dup") == 3 and b"" in have and b"absent" not in have
+    for kl in (1, 3, 4, 5, 255, 256, SC.FIND_KEY):
+        key = next(k for k in have if len(k) == kl and k[0] == kl & 255 and
+                   have.index(k) % 4 == 2)
+        i = have.index(key)
+        assert have[i - 2] == key[:-1] + bytes([key[-1] ^ 1])   # all but the last byte
+        assert have[i - 1] == key[:-1] and have[i + 1][:-1] == key  # prefix, and the reverse
+        assert {key, have[i - 2], key[:-1], have[i + 1]} <= set(keys)
+
+
 # ---- golden vectors regenerate -------------------------------------------------
 
 

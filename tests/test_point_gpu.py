@@ -13,6 +13,7 @@ import pytest
 import objectkv_amd as okv
 from objectkv_amd import _lib
 from objectkv_amd import reader as R
+from tests import staged_cases as SC
 from tests.conftest import descs_of, unpack
 from oracle import coracle as CO
 from tests.test_decode_gpu import _assert_same_as_oracle
@@ -309,6 +310,32 @@ def test_point_get_matches_oracle_row_loop(decoder, golden, comp):
                 assert got == _expect_get(ref, 0, key), (b, key[:20])
                 checked += 1
     assert checked > 200
+
+
+@pytest.mark.parametrize("name", SC.WALK + SC.STAGING + SC.KEYS)
+def test_point_staged_cases(decoder, nopoint, name):
+    """tests/staged_cases.py through the point path: the batch decode (runs of 1 to 129
+    equal records, equal lengths under other headers, a bad record at lane 1, 63 and 64,
+    OriginalSize against the run, 1 023 / 1 024 / 1 025 rows, offsets & 15 of 0, 1 and 15,
+    the segment's first and last byte, a 64 KiB block at offset & 15 == 15) == oracle ==
+    the device path of a NO_POINT context, and okv_point_get for every probe key on
+    every block (key lengths 0 to 8 192, all but the last byte, prefixes, duplicates,
+    absent keys) == the oracle's row loop."""
+    seg, d, keys = SC.cases()[name]
+    got = _point(decoder, seg, d)
+    ref = _assert_same_as_oracle(got, seg, d, 0, False)
+    other = nopoint.decode(seg, d)
+    assert not nopoint.last_path() & _lib.PATH_POINT
+    _same(got, other)
+    for b in range(d.shape[0]):
+        nrows = int(ref["row_start"][b + 1]) - int(ref["row_start"][b])
+        for key in keys:
+            res = _point_get(decoder, seg, d[b], 0, key)
+            assert decoder.last_path() == (_lib.PATH_POINT if len(key) <= SC.FIND_KEY else 0)
+            if len(key) > SC.FIND_KEY or nrows > SC.FAST_ROWS:
+                assert res[:2] == (0, -1), (b, len(key))  # the caller decodes the block in full
+            else:
+                assert res == _expect_get(ref, b, key), (b, key[:20])
 
 
 def test_point_get_reader_rows_and_fallback(decoder, nopoint):

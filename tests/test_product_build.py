@@ -145,6 +145,32 @@ def test_pack_kernels_are_the_product_form_only():
     assert m.group(0).strip("\n").count("\n") + 1 <= 25
 
 
+def test_staged_block_machinery_is_stated_once():
+    """A block staged in LDS has one byte source (okv_kernels.hpp's Staged), and one
+    speculative header walk, walk_staged_to; okv_point_kernel is a short sequence of
+    phases with no loop of its own over records."""
+    csrc = os.path.join(ROOT, "objectkv_amd", "csrc")
+    ballots = []
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if not os.path.isfile(path):
+            continue
+        src = open(path, errors="replace").read()
+        for word in ("StageWin", "LdsSrc", "StageSrc"):
+            assert word not in src, (name, word)
+        if name.endswith((".hip", ".hpp")):
+            ballots += [(name, m.start()) for m in re.finditer(r"__ballot\(brk\)", src)]
+    assert [name for name, _ in ballots] == ["okv_kernels.hpp"], ballots
+    hpp = open(os.path.join(csrc, "okv_kernels.hpp")).read()
+    start = hpp.rfind("void walk_staged_to(", 0, ballots[0][1])
+    assert start >= 0 and "\n}\n" not in hpp[start:ballots[0][1]]  # inside that definition
+    dec = open(os.path.join(csrc, "okv_decode.hip")).read()
+    m = re.search(r"\n[^\n;{}]*\bokv_point_kernel\s*\([^)]*\)\s*\{.*?\n\}", dec, flags=re.S)
+    assert m and "__global__" in m.group(0)
+    assert m.group(0).strip("\n").count("\n") + 1 <= 120
+    assert "while (" not in m.group(0)
+
+
 def test_zstd_stage_owns_its_scratch_and_diagnostics_are_out_of_line():
     """okv_zstd.hip's host part (everything after its last kernel) is the
     product sequence: the knobs, the profiling and the reports live in
