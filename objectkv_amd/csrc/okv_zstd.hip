@@ -1010,6 +1010,7 @@ sequences:
   // ---- sequences section (3.1.1.3.2)
   if (at >= n) return ZERR;
   uint32_t nseq = p[at];
+  const bool no_section = nseq == 0;  // Number_of_Sequences byte 0: the section is that byte
   if (nseq < 128) {
     at += 1;
   } else if (nseq < 255) {
@@ -1038,14 +1039,19 @@ sequences:
     lit_left -= ll;
     return true;
   };
-  if (nseq == 0) {  // literals only (bytes after the header are not read, as libzstd)
+  auto literals_only = [&]() -> int32_t {
     if (o.pos + lit_left > blk_end) return ZERR;
     if (o.pos + lit_left > o.cap) return kCap;
     emit_lits(lit_left);
     return kOK;
+  };
+  if (no_section) {  // literals only; a byte after the 0 is an error (libzstd: srcSize_wrong)
+    if (at != n) return ZERR;
+    return literals_only();
   }
   if constexpr (PRO) {
-    if (!pro->deferrable) return kSlow;
+    // (a count of 0 written in two bytes, 80 00, goes the general kernel's way below)
+    if (!pro->deferrable || nseq == 0) return kSlow;
   }
   if (at >= n) return ZERR;
   const uint32_t modes = rfl(p[at++]);
@@ -1101,6 +1107,10 @@ sequences:
     }
     return kDefer;
   } else {
+  // A count of 0 in two bytes (80 00): libzstd reads the modes byte and the
+  // tables, which may fail, then has no sequence to run and opens no bitstream;
+  // what follows the tables is not read.
+  if (nseq == 0) return literals_only();
   at = rfls64(at);
   nseq = rfl(nseq);
   lit_left = rfl64(lit_left);

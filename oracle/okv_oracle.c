@@ -470,7 +470,33 @@ static void zstd_load(void) {
  * block by block (ZSTD_decompressContinue) into out (out_len bytes, the
  * one-shot result's length); 0 if any block exceeds its limit or the
  * block-wise API rejects the input (e.g. legacy v0.5-v0.7 frames, which the
- * 1.4.8 one-shot path still accepts and RFC 8878 does not define). */
+ * 1.4.8 one-shot path still accepts and RFC 8878 does not define), or a
+ * compressed block has a reserved modes bit set (zstd_modes_reserved). */
+/* RFC 8878 3.1.1.3.2.1: the two low bits of Symbol_Compression_Modes are
+ * reserved and "must be all zeroes".  libzstd 1.4.8 does not look at them; the
+ * device decoder rejects them, as newer libzstd does.  1 if the Compressed_Block
+ * content b[0, n) (one libzstd has decoded) has one set. */
+static int zstd_modes_reserved(const uint8_t *b, uint64_t n) {
+  if (n < 1) return 0;
+  uint32_t lt = b[0] & 3, sf = (b[0] >> 2) & 3, hb, bits;
+  uint64_t v = 0, at;
+  if (lt < 2) { /* Raw / RLE literals */
+    hb = sf == 1 ? 2 : (sf == 3 ? 3 : 1);
+    bits = hb == 1 ? 3 : 4;
+  } else {
+    hb = sf < 2 ? 3 : sf + 2;
+    bits = sf < 2 ? 10 : (sf == 2 ? 14 : 18);
+  }
+  if (n < hb) return 0;
+  for (uint32_t i = 0; i < hb; i++) v |= (uint64_t)b[i] << (8 * i);
+  if (lt < 2)
+    at = hb + (lt == 0 ? v >> bits : 1);
+  else
+    at = hb + ((v >> (4 + bits)) & ((1u << bits) - 1));
+  if (at >= n || b[at] == 0) return 0;
+  at += b[at] < 128 ? 1 : (b[at] < 255 ? 2 : 3);
+  return at < n && (b[at] & 3) != 0;
+}
 static int zstd_blocks_within_max(const uint8_t *src, uint64_t n, uint8_t *out, uint64_t out_len) {
   void *d = z_mkd();
   if (!d) return 0;
@@ -478,6 +504,7 @@ static int zstd_blocks_within_max(const uint8_t *src, uint64_t n, uint8_t *out, 
   int ok = 1;
   while (ok && at < n) {
     zstd_fh_t fh;
+    uint32_t btype = 0;
     size_t r = z_fh(&fh, src + at, (size_t)(n - at));
     if (z_iserr(r) || r != 0 || z_iserr(z_begin(d))) {
       ok = 0;
@@ -490,12 +517,15 @@ static int zstd_blocks_within_max(const uint8_t *src, uint64_t n, uint8_t *out, 
         ok = 0;
         break;
       }
-      int kind = z_nit(d); /* ZSTDnit_block = 2, ZSTDnit_lastBlock = 3 */
+      int kind = z_nit(d); /* ZSTDnit_blockHeader = 1, _block = 2, _lastBlock = 3 */
       size_t m = z_cont(d, out + pos, (size_t)(out_len + 64 - pos), src + at, need);
-      if (z_iserr(m) || ((kind == 2 || kind == 3) && fh.frameType == 0 && m > fh.blockSizeMax)) {
+      if (z_iserr(m) || ((kind == 2 || kind == 3) && fh.frameType == 0 &&
+                         (m > fh.blockSizeMax ||
+                          (btype == 2 && zstd_modes_reserved(src + at, need))))) {
         ok = 0;
         break;
       }
+      if (kind == 1) btype = (src[at] >> 1) & 3;
       at += need;
       pos += m;
     }

@@ -85,6 +85,49 @@ def compress(data: bytes, level: int = 3, checksum: bool = True, content_size: b
         L.ZSTD_freeCCtx(cctx)
 
 
+class _Buffer(C.Structure):  # ZSTD_inBuffer / ZSTD_outBuffer (same layout)
+    _fields_ = [("p", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
+
+
+E_CONTINUE, E_FLUSH, E_END = 0, 1, 2  # ZSTD_EndDirective
+
+
+def compress_stream(data: bytes, level: int = 3, piece: int = 8192, checksum: bool = True) -> bytes:
+    """One zstd frame of `data` through ZSTD_compressStream2: ZSTD_e_flush after
+    every `piece` bytes, ZSTD_e_end at the end.  A flush closes a block inside
+    the frame, so the frame has about len(data) / piece blocks and the later
+    ones may repeat the earlier ones' tables and Huffman tree (Repeat_Mode,
+    Treeless_Literals_Block), which a one-shot ZSTD_compress2 of <= 128 KiB
+    never does.  No Frame_Content_Size: the stream's length is not announced."""
+    L = lib()
+    L.ZSTD_compressStream2.restype = C.c_size_t
+    L.ZSTD_compressStream2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    cctx = L.ZSTD_createCCtx()
+    try:
+        for prm, val in ((C_LEVEL, level), (C_CHECKSUM, int(checksum))):
+            assert not L.ZSTD_isError(L.ZSTD_CCtx_setParameter(cctx, prm, val))
+        cap = L.ZSTD_compressBound(len(data)) + 64 * (len(data) // piece + 2)
+        dst = C.create_string_buffer(cap)
+        src = C.create_string_buffer(bytes(data), max(len(data), 1))
+        ob = _Buffer(C.cast(dst, C.c_void_p), cap, 0)
+        at = 0
+        while True:
+            end = min(at + piece, len(data))
+            ib = _Buffer(C.cast(src, C.c_void_p), end, at)
+            mode = E_END if end == len(data) else E_FLUSH
+            while True:
+                r = L.ZSTD_compressStream2(cctx, C.byref(ob), C.byref(ib), mode)
+                assert not L.ZSTD_isError(r), "ZSTD_compressStream2"
+                if r == 0 and ib.pos == end:
+                    break
+                assert ob.pos < cap
+            at = end
+            if mode == E_END:
+                return dst.raw[:ob.pos]
+    finally:
+        L.ZSTD_freeCCtx(cctx)
+
+
 def _oneshot(L, frames: bytes, hint: int):
     src = C.create_string_buffer(bytes(frames), max(len(frames), 1))
     cap = max(min(hint, 1 << 24), 64) + 65536
@@ -104,7 +147,27 @@ class _FrameHeader(C.Structure):  # ZSTD_frameHeader (zstd.h, 1.4.x)
                 ("dictID", C.c_uint), ("checksumFlag", C.c_uint)]
 
 
-NIT_BLOCK, NIT_LAST_BLOCK = 2, 3  # ZSTD_nextInputType_e
+NIT_BLOCK_HEADER, NIT_BLOCK, NIT_LAST_BLOCK = 1, 2, 3  # ZSTD_nextInputType_e
+
+
+def _modes_reserved(b: bytes) -> bool:
+    """True if the Compressed_Block content `b` (one libzstd has decoded) has a
+    reserved bit set in Symbol_Compression_Modes: RFC 8878 3.1.1.3.2.1, "the last
+    field, Reserved, must be all zeroes".  libzstd 1.4.8 does not look at those
+    two bits; the device decoder rejects them, as newer libzstd does."""
+    if not b:
+        return False
+    lt, sf = b[0] & 3, (b[0] >> 2) & 3
+    if lt < 2:  # Raw / RLE literals
+        hb = (1, 2, 1, 3)[sf]
+        at = hb + ((int.from_bytes(b[:hb], "little") >> (3 if hb == 1 else 4)) if lt == 0 else 1)
+    else:
+        hb, bits = ((3, 10), (3, 10), (4, 14), (5, 18))[sf]
+        at = hb + ((int.from_bytes(b[:hb], "little") >> (4 + bits)) & ((1 << bits) - 1))
+    if at >= len(b) or b[at] == 0:
+        return False
+    at += 1 if b[at] < 128 else 2 if b[at] < 255 else 3
+    return at < len(b) and bool(b[at] & 3)
 
 
 def _blocks_within_max(L, frames: bytes, out_len: int) -> bool:
@@ -114,7 +177,8 @@ def _blocks_within_max(L, frames: bytes, out_len: int) -> bool:
     libzstd 1.4.8's one-shot decoder does not enforce that limit (an RLE block
     of 200 KiB decodes); the device decoder does, as the RFC -- and newer
     libzstd -- require.  Also False for input the block-wise API rejects
-    (e.g. the legacy v0.5-v0.7 frames 1.4.8's one-shot path still accepts)."""
+    (e.g. the legacy v0.5-v0.7 frames 1.4.8's one-shot path still accepts), and
+    for a compressed block with a reserved modes bit set (_modes_reserved)."""
     d = L.ZSTD_createDCtx()
     try:
         src = bytes(frames)
@@ -127,6 +191,7 @@ def _blocks_within_max(L, frames: bytes, out_len: int) -> bool:
             if L.ZSTD_isError(r) or r != 0:
                 return False
             bmax = fh.blockSizeMax
+            btype = 0
             if L.ZSTD_isError(L.ZSTD_decompressBegin(d)):
                 return False
             while True:
@@ -140,8 +205,11 @@ def _blocks_within_max(L, frames: bytes, out_len: int) -> bool:
                                               C.byref(sbuf, at), need)
                 if L.ZSTD_isError(n):
                     return False
-                if kind in (NIT_BLOCK, NIT_LAST_BLOCK) and fh.frameType == 0 and n > bmax:
-                    return False
+                if kind in (NIT_BLOCK, NIT_LAST_BLOCK) and fh.frameType == 0:
+                    if n > bmax or (btype == 2 and _modes_reserved(src[at:at + need])):
+                        return False
+                elif kind == NIT_BLOCK_HEADER:
+                    btype = (src[at] >> 1) & 3
                 at += need
                 pos += n
         return pos == out_len
@@ -152,7 +220,7 @@ def _blocks_within_max(L, frames: bytes, out_len: int) -> bool:
 def decompress(frames: bytes, hint: int = 0):
     """All frames of `frames` -> bytes, or None on a decode error (Go: the
     io.Copy error of segment_reader.go:326-330).  libzstd's one-shot decode,
-    plus RFC 8878's Block_Maximum_Size rule (_blocks_within_max).  The whole
+    plus RFC 8878's Block_Maximum_Size and reserved-bits rules (_blocks_within_max).  The whole
     frame set is inflated whatever the caller's OriginalSize (`hint` only
     sizes the first buffer): Go's io.Copy does the same before its record walk."""
     L = lib()

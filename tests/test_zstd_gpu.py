@@ -11,8 +11,21 @@ from objectkv_amd import reader as R
 from oracle import coracle as CO
 from oracle import pyoracle as P
 from tests import zstd_cases as ZC
+from tests import zstd_census as ZS
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def cases_reach_every_arm():
+    """Before any case runs: the blocks the oracle decodes hold every feature of
+    ZS.REQUIRED (header census, host only), so a libzstd that emits other frames
+    than 1.4.8 fails here and not by quietly testing less."""
+    tot = ZS.Counter()
+    for _name, seg, descs, _note in ZC.cases():
+        st = CO.decode_soa(seg, CO.descs_array(descs), P.COMP_ZSTD)["status"]
+        tot.update(ZS.segment(seg, descs, [int(x) for x in st]))
+    assert not ZS.missing(tot), ZS.missing(tot)
 
 @pytest.fixture(scope="module")
 def one_pass_decoder():
@@ -55,6 +68,8 @@ def test_zstd_cases(zdec, case):
     name, seg, descs, _note = case
     got = _check(zdec, seg, descs)
     assert int(got.status.max()) == 0, name
+    if name.startswith("hand_"):
+        assert zdec.last_path() & okv._lib.PATH_ZSTD, name
     _check(zdec, seg, descs, index_only=True)  # every block OKV_BLK_UNSUPPORTED
 
 
@@ -98,8 +113,10 @@ def test_zstd_bench_shape_blocks(zdec):
 
 
 def test_zstd_long_runs_and_rle_literals(zdec):
-    """Matches far longer than the executor's 1 KiB byte map, offset-1 runs,
-    and blocks whose literals are RLE."""
+    """Matches far longer than the executor's 1 KiB byte map and offset-1 runs.
+    (The name is older than the header census: libzstd codes these blocks with
+    raw literals, none with RLE literals -- tests/test_zstd_census.py holds that;
+    ZC.cases()' hand_rle_literals has the RLE_Literals_Blocks.)"""
     rows = []
     for i in range(120):
         v = bytes([i % 7]) * (4500 + 37 * i) if i % 3 else (b"ab" * 2100 + bytes(range(i % 50)))
@@ -179,6 +196,21 @@ def test_zstd_sequence_section_corruption_wide(decoder, one_pass_decoder):
     assert np.array_equal(staged.status, general.status)
     bad = int((staged.status != 0).sum())
     assert 0 < bad < len(dl)
+
+
+def test_zstd_handmade_frames_under_bit_flips(decoder, one_pass_decoder):
+    """Every small hand-made frame ten times with one bit flipped (half of the
+    flips in the headers): the arms that libzstd's own frames never take --
+    RLE and treeless literals, direct weights, Repeat_Mode, a block without
+    sequences, every frame header field -- under corruption.  Two-sided against
+    the oracle, statuses and the rows of what still decodes; both device paths.
+    (Found: a byte after Number_of_Sequences 0 was accepted.)"""
+    seg, descs = ZC.flipped_handmade()
+    staged = _check(decoder, seg, descs)
+    general = _check(one_pass_decoder, seg, descs)
+    assert np.array_equal(staged.status, general.status)
+    ok = int((staged.status == 0).sum())
+    assert len(descs) >= 300 and 30 < ok < len(descs) - 100
 
 
 def test_zstd_literal_stream_corruption(decoder, one_pass_decoder):
