@@ -41,7 +41,9 @@ extern "C" {
                                 OKV_F_BLOOM_DEVICE): purely additive -- new symbols and one
                                 new flag bit, no struct layout or behaviour change;
                                 still 6 with the batched GetRow (okv_index_*, okv_get_*,
-                                OKV_PATH_GET): new symbols only */
+                                OKV_PATH_GET): new symbols only;
+                                still 6 with the device zstd encoder (OKV_F_ZSTD_NATIVE,
+                                OKV_PATH_ZSTD_ENC): one new flag bit and one path bit */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -58,7 +60,8 @@ extern "C" {
 #define OKV_W_CLOSED (-103)          /* ErrWriterClosed */
 #define OKV_W_INVALID_KEY (-104)     /* ErrInvalidKey: empty key (WriteRow :89-91) */
 #define OKV_W_NIL_WRITER (-105)      /* Go panics in Close when no block is open (:212, Q1) */
-#define OKV_W_UNSUPPORTED (-106)     /* zstd level > 0: encoder not implemented */
+#define OKV_W_UNSUPPORTED (-106)     /* zstd level > 0 without OKV_F_ZSTD_NATIVE: the Go writer's
+                                        bytes cannot be produced (Q6) */
 #define OKV_W_NO_ROWS (-107)         /* ErrNoRowsWritten (:221-223) */
 
 /* ---- per-block status (okv_decode_out.blk_status) ---------------------- */
@@ -86,6 +89,29 @@ extern "C" {
                                 meta XXH64 and the 25-byte trailer are left to okv_encode_close */
 #define OKV_F_BLOOM_DEVICE 16u /* okv_encode_rows: opts->bloom is a DEVICE pointer (copied device
                                 to device on the ctx stream); independent of OKV_F_DEVICE_PTRS */
+/* okv_encode_rows / okv_encode_close with opts->compression == OKV_COMP_ZSTD: the device zstd
+ * encoder (okv_zstd_enc.hip).  Every block becomes one standard RFC 8878 frame
+ * (Single_Segment, Frame_Content_Size = OriginalSize, Content_Checksum) that inflates to the
+ * block's raw bytes; CompressedSize, the zero padding to DataBlockSize, Hash, Offset, the meta
+ * block (compression byte 1) and the trailer are the Go writer's (segment_writer.go:148-204,
+ * :284-328).  Opt-in, because two things differ from a Go writer with ZSTDCompressionLevel > 0:
+ *  - the frame bytes are this encoder's, not klauspost/compress v1.17.9's;
+ *  - a block is cut when its RAW length reaches threshold_bytes (the rule of
+ *    oracle/zstd_ref.py zstd_segment); Go cuts on the klauspost encoder's buffered output
+ *    length (Q6).  The row partition (blk_first_row, OriginalSize) is therefore the one the
+ *    uncompressed encode gives for the same rows and threshold.
+ * Without the flag OKV_COMP_ZSTD is OKV_W_UNSUPPORTED; the flag with any other compression is
+ * OKV_E_ARG.
+ * Capacity: compressed sizes exist only after the compress stage, so the sizes a call must
+ * be given come from the raw sizes alone.  A call whose capacities are too small (the size
+ * query included) sets n_blocks exactly and data_bytes / file_bytes to an upper bound -- every
+ * block as Raw_Blocks plus frame overhead, padded -- writes nothing and returns
+ * OKV_E_CAPACITY; a call with seg_cap >= that file_bytes and blk_cap >= n_blocks succeeds
+ * and sets the actual sizes (never above the bound). */
+#define OKV_F_ZSTD_NATIVE 64u
+/* The most source bytes the encoder puts into one zstd block of a frame, so
+ * CompressedSize <= OriginalSize + 3 * ceil(OriginalSize / OKV_ZSTD_ENC_UNIT) + 18. */
+#define OKV_ZSTD_ENC_UNIT 32768
 
 /* One data-block index entry: BlockStat (sst/block_stat.go:9-24) without
  * FirstKey and Hash, which the decode does not need. */
@@ -270,7 +296,8 @@ typedef struct okv_encode_opts {
   uint64_t block_size;      /* DataBlockSize (default 4096) */
   int compression;          /* OKV_COMP_NONE, or OKV_COMP_LZ4: Go writes raw bytes with
                                CompressedSize = OriginalSize and meta byte 2 (Q7);
-                               OKV_COMP_ZSTD -> OKV_W_UNSUPPORTED */
+                               OKV_COMP_ZSTD: with OKV_F_ZSTD_NATIVE the device encoder,
+                               else OKV_W_UNSUPPORTED */
   int strict_go;            /* 1: a Close with no open block panics in Go (Q1) ->
                                OKV_W_NIL_WRITER; 0: write the footer normally */
   const uint8_t *bloom;     /* bytes of BloomFilter.WriteTo (host memory; device memory with
@@ -304,7 +331,7 @@ typedef struct okv_encode_out {
 /*
  * Encode rows into one segment on the GPU.  flags: OKV_F_DEVICE_PTRS (rows and
  * every output pointer are device pointers; seg must be 16-byte aligned),
- * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE.  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
+ * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE, OKV_F_ZSTD_NATIVE.  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
  * written: call again with seg_cap >= file_bytes and blk_cap >= n_blocks --
  * a call with zero capacities is the size query); OKV_W_INVALID_KEY (bad_row
  * set); OKV_W_NIL_WRITER (strict_go and the last row closed a block, or no
@@ -576,6 +603,8 @@ int okv_profile_read(okv_ctx *ctx, double *ms, uint64_t *calls);
                                 blocks (GetRow, GetRange) in one launch over pinned memory */
 #define OKV_PATH_GET 8192u /* okv_get_rows: okv_get_locate_kernel, the grouping and
                              okv_get_search_kernel */
+#define OKV_PATH_ZSTD_ENC 16384u /* okv_encode_rows compressed the blocks on the device
+                                    (OKV_F_ZSTD_NATIVE: okv_zenc_unit_kernel and its placement) */
 uint32_t okv_last_path(const okv_ctx *ctx);
 
 /* Device / pinned-host memory helpers for callers without another allocator. */

@@ -28,6 +28,8 @@ BLK_OK, BLK_EOF, BLK_SHORT, BLK_PANIC, BLK_UNSUPPORTED, BLK_CAPACITY = 0, 1, 2, 
 COMP_NONE, COMP_ZSTD, COMP_LZ4 = 0, 1, 2
 F_DEVICE_PTRS, F_INDEX_ONLY, F_ASYNC, F_NO_CLOSE = 1, 2, 4, 8
 F_BLOOM_DEVICE = 16
+F_ZSTD_NATIVE = 64  # okv_encode_rows with COMP_ZSTD: the device zstd encoder (opt-in)
+ZSTD_ENC_UNIT = 32768  # OKV_ZSTD_ENC_UNIT: most source bytes in one zstd block of a frame
 BLOOM_FORCE_LDS, BLOOM_FORCE_GLOBAL = 32, 64
 BLOOM_PATH_LDS, BLOOM_PATH_GLOBAL = 1, 2
 OPEN_NO_FUSED, OPEN_ZSTD_ONE_PASS, OPEN_NO_POINT = 1, 2, 4
@@ -37,6 +39,7 @@ PATH_STAGED, PATH_GATHER, PATH_BIG, PATH_ZSTD = 16, 32, 64, 128
 PATH_ZSTD_REGROW, PATH_ENC_ONEPASS, PATH_STREAM = 256, 512, 1024
 PATH_POINT, PATH_GROUP = 2048, 4096
 PATH_GET = 8192
+PATH_ZSTD_ENC = 16384
 # okv_get_out.state (include/okv_sst.h OKV_GET_*)
 GET_FOUND, GET_BLOOM_NEGATIVE, GET_NO_BLOCK, GET_NOT_IN_BLOCK = 0, 1, 2, 3
 GET_BLOCK_ERROR, GET_FALLBACK = 4, 5

@@ -1,12 +1,12 @@
 // okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip), encode
 // (okv_encode.hip), zstd (okv_zstd.hip), merge (okv_merge.hip) and batched GetRow
-// (okv_get.hip) translation units.
+// (okv_get.hip) translation units, and the zstd encoder (okv_zstd_enc.hip).
 // Internal header.
 // Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
 // its capacity and frees itself with its owner; kernels get raw pointers from data().  The
 // owners are okv_ctx (decode), AblateState (the decode ablation arms) and, each defined in its
 // own file behind a forward declaration here and released by okv_close: EncScratch,
-// zst::Scratch, mrg::Scratch and get::Scratch.
+// zst::Scratch, mrg::Scratch, get::Scratch and zenc::Scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #define OKV_BUF_HIP
@@ -62,6 +62,20 @@ struct ZstdOut {
 int zstd_stage(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const Desc* descs,
                uint32_t nblk, ZstdOut* out);
 void zstd_release(okv_ctx* ctx);
+// okv_zstd_enc.hip: the zstd encoder (OKV_F_ZSTD_NATIVE).  img_desc[b] (device) says where
+// block b's raw records lie in the image: offset (16-byte aligned) and original_size.
+// zstd_enc_bound computes the units and *bound_bytes, the data bytes when every block is
+// stored as Raw_Blocks.  zstd_enc_run then compresses those blocks, writes the padded frames
+// at DataBlockSize D into seg, the BlockStats over desc, their hashes into hash (device
+// pointers) and the actual *data_bytes.
+namespace zenc {
+struct Scratch;  // okv_zstd_enc.hip
+}
+int zstd_enc_bound(okv_ctx* ctx, const Desc* img_desc, uint64_t nb, uint64_t D,
+                   uint64_t* bound_bytes);
+int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* desc, uint64_t nb,
+                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes);
+void zstd_enc_release(okv_ctx* ctx);
 }  // namespace okv
 
 namespace okv {
@@ -161,6 +175,7 @@ struct okv_ctx {
   okv::mrg::Scratch* merge = nullptr;  // merge scratch (okv_merge.hip)
   okv::zst::Scratch* zstd = nullptr;   // zstd stage scratch (okv_zstd.hip)
   okv::get::Scratch* get = nullptr;    // batched GetRow scratch (okv_get.hip)
+  okv::zenc::Scratch* zenc = nullptr;  // zstd encoder scratch (okv_zstd_enc.hip)
 };
 
 namespace okv {

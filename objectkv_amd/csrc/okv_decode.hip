@@ -2834,6 +2834,7 @@ void okv_close(okv_ctx* ctx) {
 #endif
   okv::enc_release(ctx);
   okv::zstd_release(ctx);
+  okv::zstd_enc_release(ctx);
   okv::merge_release(ctx);
   okv::get_release(ctx);
   const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;

@@ -118,6 +118,7 @@ struct EncScratch {
   // host-mode staging
   DevBuf<uint8_t> d_in;
   DevBuf<uint8_t> d_outseg;
+  DevBuf<uint8_t> zimg;          // zstd encode: the blocks' raw records, 16-byte padding unit
   PinBuf<uint8_t> close_buf[2];  // D2H chunks of the meta block (Close)
   hipEvent_t close_ev[2] = {nullptr, nullptr};
   // profiling (okv_encode_profile_read): cut, pack, hash, meta
@@ -2110,6 +2111,10 @@ int enc_pack(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
 #include "okv_encode_ablate_pack.inc"
 #endif
 
+int enc_meta(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
+             const Plan& pl, uint8_t* seg, bool bloom_dev, int comp_byte, bool from_seg,
+             bool fk_done, bool meta_done);
+
 // Data blocks, block hashes and the meta block into seg (E10-E12).
 int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
               const Plan& pl, uint8_t* seg, bool bloom_dev) {
@@ -2142,6 +2147,15 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
   if (!hashed)
     launch_hash(ctx->stream, seg, pl.data_bytes, e->desc.data(), uint32_t(pl.nb), e->hash.data());
   enc_mark(ctx, e, 3);
+  return enc_meta(ctx, e, R, o, pl, seg, bloom_dev, o.compression == OKV_COMP_LZ4 ? 2 : 0,
+                  o.compression == OKV_COMP_NONE, fk_done, meta_done);
+}
+
+// The meta block (E12) at seg + data_bytes: compression byte comp_byte; FirstKeys from the
+// packed blocks (from_seg), the pack kernel's copies (fk_done) or the row arrays.
+int enc_meta(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
+             const Plan& pl, uint8_t* seg, bool bloom_dev, int comp_byte, bool from_seg,
+             bool fk_done, bool meta_done) {
   MetaParams mp;
   mp.key_arena = R.ka;
   mp.key_off = R.ko;
@@ -2153,10 +2167,10 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
   mp.moff = e->moff.data();
   mp.nb = pl.nb;
   mp.count = pl.nb;
-  mp.comp_byte = o.compression == OKV_COMP_LZ4 ? 2 : 0;
+  mp.comp_byte = comp_byte;
   mp.meta = seg + pl.data_bytes;
   mp.bloom_len = o.bloom ? o.bloom_len : ~uint64_t(0);
-  mp.seg = o.compression == OKV_COMP_NONE ? seg : nullptr;
+  mp.seg = from_seg ? seg : nullptr;
   mp.fk = fk_done ? e->fk.data() : nullptr;
   mp.fkl = e->fkl.data();
   if (o.bloom && o.bloom_len)  // BloomFilter.WriteTo bytes at head - 10 - len (after flag + u64)
@@ -2179,6 +2193,46 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
   enc_mark(ctx, e, 4);
   OKV_HIP(hipGetLastError());
   return OKV_OK;
+}
+
+// OKV_F_ZSTD_NATIVE: the blocks' records packed into a scratch image (the plan `pl` and the
+// pack kernels at a 16-byte padding unit, `po`), each block compressed into one frame and
+// placed in seg at the caller's DataBlockSize (okv_zstd_enc.hip), block hashes, then the
+// meta block with compression byte 1.  pl leaves with the segment's sizes; e->desc and
+// e->hash with the BlockStats.
+int enc_write_zstd(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
+                   const okv_encode_opts& po, Plan* pl, uint8_t* seg, bool bloom_dev) {
+  enc_mark(ctx, e, 1);
+  int rc;
+  if ((rc = reserve(ctx, e->zimg, pl->data_bytes + 64))) return rc;
+  uint8_t* img = e->zimg.data();
+  PackParams pp;
+  pp.key_arena = R.ka;
+  pp.key_off = R.ko;
+  pp.key_len = R.kl;
+  pp.val_arena = R.va;
+  pp.val_off = R.vo;
+  pp.val_len = R.vl;
+  pp.pl = e->pl.data();
+  pp.tp = e->tile_pre.data();
+  pp.first = e->first.data();
+  pp.desc = e->desc.data();
+  pp.seg = img;
+  pp.hash = e->hash.data();
+  pp.meta = nullptr;
+  pp.moff = e->moff.data();
+  pp.fk = nullptr;
+  bool hashed = false, fk_done = false;
+  if ((rc = enc_pack(ctx, e, R, po, *pl, img, pp, &hashed, &fk_done))) return rc;
+  enc_mark(ctx, e, 2);
+  uint64_t data_bytes = 0;
+  if ((rc = zstd_enc_run(ctx, img, pl->data_bytes, e->desc.data(), pl->nb, o.block_size, seg,
+                         e->hash.data(), &data_bytes)))
+    return rc;
+  pl->data_bytes = data_bytes;
+  pl->file_bytes = data_bytes + pl->meta_bytes + 25;
+  enc_mark(ctx, e, 3);
+  return enc_meta(ctx, e, R, o, *pl, seg, bloom_dev, 1, false, false, false);
 }
 
 // The 25-byte trailer (segment_writer.go:226-276): meta offset, XXH64(meta),
@@ -2309,9 +2363,12 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   out->n_blocks = out->data_bytes = out->meta_bytes = out->file_bytes = 0;
   out->meta_hash = 0;
   out->bad_row = kNone;
-  if (opts->compression == OKV_COMP_ZSTD)
+  const bool zn = flags & OKV_F_ZSTD_NATIVE;  // the device zstd encoder (opt-in)
+  if (zn && opts->compression != OKV_COMP_ZSTD)
+    return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_NATIVE without OKV_COMP_ZSTD");
+  if (opts->compression == OKV_COMP_ZSTD && !zn)
     return set_err(ctx, OKV_W_UNSUPPORTED, "zstd encode not implemented");
-  if (opts->compression != OKV_COMP_NONE && opts->compression != OKV_COMP_LZ4)
+  if (!zn && opts->compression != OKV_COMP_NONE && opts->compression != OKV_COMP_LZ4)
     return set_err(ctx, OKV_E_ARG, "compression");
   if (opts->block_size == 0) return set_err(ctx, OKV_E_ARG, "block_size == 0");
   const uint64_t n = rows->n_rows;
@@ -2365,30 +2422,50 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   bool general = true;
 #ifdef OKV_ABLATE
   // A/B (OKV_ENC_ONEPASS=1): the single-pass plan kernel, falling back to E1-E9
-  if (okv::knob("OKV_ENC_ONEPASS") && atoi(okv::knob("OKV_ENC_ONEPASS")))
+  if (!(flags & OKV_F_ZSTD_NATIVE) && okv::knob("OKV_ENC_ONEPASS") &&
+      atoi(okv::knob("OKV_ENC_ONEPASS")))
     rc = enc_plan_fast(ctx, e, R, *opts, &pl, &bad, &general);
   else
 #endif
     rc = OKV_OK, enc_mark(ctx, e, 0);
-  if (!rc && general) rc = enc_plan(ctx, e, R, *opts, &pl, &bad);
-  ctx->last_path = general ? 0u : OKV_PATH_ENC_ONEPASS;
+  // zstd: the same cut over raw lengths, laid out as a scratch image of uncompressed
+  // blocks at a 16-byte padding unit
+  okv_encode_opts po = *opts;
+  if (zn) po.compression = OKV_COMP_NONE, po.block_size = 16;
+  if (!rc && general) rc = enc_plan(ctx, e, R, po, &pl, &bad);
+  ctx->last_path = (general ? 0u : OKV_PATH_ENC_ONEPASS) | (zn ? OKV_PATH_ZSTD_ENC : 0u);
   if (rc == OKV_W_INVALID_KEY) out->bad_row = bad;
   if (rc) return rc;
+  uint64_t need = pl.file_bytes;
+  if (zn) {  // sizes before the compress stage: the bound from the raw sizes
+    uint64_t bound = 0;
+    if ((rc = zstd_enc_bound(ctx, e->desc.data(), pl.nb, opts->block_size, &bound))) return rc;
+    need = bound + pl.meta_bytes + 25;
+    out->data_bytes = bound;
+  } else {
+    out->data_bytes = pl.data_bytes;
+  }
   out->n_blocks = pl.nb;
-  out->data_bytes = pl.data_bytes;
   out->meta_bytes = pl.meta_bytes;
-  out->file_bytes = pl.file_bytes;
+  out->file_bytes = need;
   if (opts->strict_go && pl.last_raw >= opts->threshold_bytes)
     return set_err(ctx, OKV_W_NIL_WRITER, "Close on nil blockWriter (Q1): last row closed a block");
   const bool want_idx = out->blk_first_row || out->blk_desc || out->blk_hash;
-  if (out->seg_cap < pl.file_bytes || (want_idx && out->blk_cap < pl.nb) || !out->seg)
+  if (out->seg_cap < need || (want_idx && out->blk_cap < pl.nb) || !out->seg)
     return set_err(ctx, OKV_E_CAPACITY, "encode output capacity too small (sizes set)");
   uint8_t* seg = out->seg;
   if (!dev) {
-    if ((rc = reserve(ctx, e->d_outseg, pl.file_bytes + 64))) return rc;
+    if ((rc = reserve(ctx, e->d_outseg, need + 64))) return rc;
     seg = e->d_outseg.data();
   }
-  if ((rc = enc_write(ctx, e, R, *opts, pl, seg, flags & OKV_F_BLOOM_DEVICE))) return rc;
+  const bool bloom_dev = flags & OKV_F_BLOOM_DEVICE;
+  if (zn) {
+    if ((rc = enc_write_zstd(ctx, e, R, *opts, po, &pl, seg, bloom_dev))) return rc;
+    out->data_bytes = pl.data_bytes;
+    out->file_bytes = pl.file_bytes;
+  } else if ((rc = enc_write(ctx, e, R, *opts, pl, seg, bloom_dev))) {
+    return rc;
+  }
   const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (out->blk_first_row)
     OKV_HIP(hipMemcpyAsync(out->blk_first_row, e->first.data(), (pl.nb + 1) * 8, k, ctx->stream));

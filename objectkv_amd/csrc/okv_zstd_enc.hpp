@@ -1,0 +1,296 @@
+// okv_zstd_enc.hpp -- the zstd block encoder's format, stated once (RFC 8878): the
+// predefined distributions turned into FSE encode tables, the literal-length /
+// match-length / offset codes with their extra bits, the FSE state step, and the
+// byte encoders of the frame, block, literals and sequence-count headers.  The device
+// encoder (okv_zstd_enc.hip) and tests/zenc_main.cpp on the CPU run these statements.
+// Internal header; it includes no HIP header: the functions are __host__ __device__
+// when a HIP compiler defines those, plain inline otherwise.
+//
+// What the encoder emits and nothing else: Raw_Literals_Block, all three sequence
+// tables in Predefined_Mode, every offset as Offset_Value = offset + 3 (no repeat
+// codes), Raw_Blocks.  Huffman literals and custom FSE tables are not here.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "okv_sst.h"
+
+#if defined(__host__) && defined(__device__)
+#define OKV_ZE_HD __host__ __device__ inline
+#else
+#define OKV_ZE_HD inline
+#endif
+
+namespace okv {
+namespace zenc {
+
+constexpr uint32_t kUnit = OKV_ZSTD_ENC_UNIT;  // source bytes per zstd block
+constexpr uint32_t kMinMatch = 4;
+constexpr uint32_t kLL = 0, kML = 1, kOF = 2;  // table order used throughout
+constexpr uint32_t kMaxSyms = 53;
+
+OKV_ZE_HD uint32_t highbit(uint32_t v) { return 31u - uint32_t(__builtin_clz(v)); }  // v > 0
+
+// ---- predefined distributions (RFC 8878 3.1.1.3.2.2.1-3) ------------------------
+OKV_ZE_HD uint32_t table_log(uint32_t t) { return t == kOF ? 5u : 6u; }
+OKV_ZE_HD uint32_t table_syms(uint32_t t) { return t == kLL ? 36u : t == kML ? 53u : 29u; }
+OKV_ZE_HD int predefined_norm(uint32_t t, uint32_t s) {
+  if (t == kLL) {
+    if (s == 0) return 4;
+    if (s == 1 || s == 25) return 3;
+    if (s >= 32) return -1;
+    if ((s >= 13 && s <= 15) || s >= 27) return 1;
+    return 2;
+  }
+  if (t == kML) {
+    if (s == 0) return 1;
+    if (s == 1) return 4;
+    if (s == 2) return 3;
+    if (s <= 8) return 2;
+    return s >= 46 ? -1 : 1;
+  }
+  if (s >= 24) return -1;
+  return (s >= 6 && s <= 8) ? 2 : 1;
+}
+
+// ---- FSE encode table (FSE_buildCTable's construction) ---------------------------
+struct CTable {
+  uint16_t state[64];      // next-state table, sorted by symbol
+  int32_t dfs[kMaxSyms];   // deltaFindState
+  uint32_t dnb[kMaxSyms];  // deltaNbBits
+  uint32_t log;
+};
+
+OKV_ZE_HD void build_ctable(CTable& ct, uint32_t t) {
+  const uint32_t log = table_log(t), nsym = table_syms(t), size = 1u << log, mask = size - 1;
+  const uint32_t step = (size >> 1) + (size >> 3) + 3;
+  uint8_t sym_at[64];
+  uint16_t cumul[kMaxSyms + 1];
+  uint32_t high = size - 1;
+  cumul[0] = 0;
+  for (uint32_t s = 0; s < nsym; ++s) {
+    const int nrm = predefined_norm(t, s);
+    if (nrm == -1) {
+      cumul[s + 1] = uint16_t(cumul[s] + 1);
+      sym_at[high--] = uint8_t(s);
+    } else {
+      cumul[s + 1] = uint16_t(cumul[s] + nrm);
+    }
+  }
+  uint32_t pos = 0;
+  for (uint32_t s = 0; s < nsym; ++s) {
+    const int nrm = predefined_norm(t, s);
+    for (int i = 0; i < nrm; ++i) {
+      sym_at[pos] = uint8_t(s);
+      pos = (pos + step) & mask;
+      while (pos > high) pos = (pos + step) & mask;
+    }
+  }
+  for (uint32_t u = 0; u < size; ++u) ct.state[cumul[sym_at[u]]++] = uint16_t(size + u);
+  uint32_t total = 0;
+  for (uint32_t s = 0; s < nsym; ++s) {
+    const int nrm = predefined_norm(t, s);
+    if (nrm == -1 || nrm == 1) {
+      ct.dnb[s] = (log << 16) - size;
+      ct.dfs[s] = int32_t(total) - 1;
+      total += 1;
+    } else {  // (no predefined symbol has probability 0)
+      const uint32_t max_bits = log - highbit(uint32_t(nrm) - 1);
+      ct.dnb[s] = (max_bits << 16) - (uint32_t(nrm) << max_bits);
+      ct.dfs[s] = int32_t(total) - nrm;
+      total += uint32_t(nrm);
+    }
+  }
+  ct.log = log;
+}
+
+// The state a chain starts in (FSE_initCState2): the symbol of the LAST sequence.
+OKV_ZE_HD uint32_t fse_init(const CTable& ct, uint32_t sym) {
+  const uint32_t dnb = ct.dnb[sym];
+  const uint32_t nb = (dnb + (1u << 15)) >> 16;
+  const uint32_t value = (nb << 16) - dnb;
+  return ct.state[int32_t(value >> nb) + ct.dfs[sym]];
+}
+// One step (FSE_encodeSymbol): the low nb bits of the state go out, then the state moves.
+OKV_ZE_HD uint32_t fse_step(const CTable& ct, uint32_t state, uint32_t sym, uint32_t& nb,
+                            uint32_t& bits) {
+  nb = (state + ct.dnb[sym]) >> 16;
+  bits = state & ((1u << nb) - 1);
+  return ct.state[int32_t(state >> nb) + ct.dfs[sym]];
+}
+
+// ---- codes and extra bits (RFC 8878 3.1.1.3.2.1.1) -------------------------------
+OKV_ZE_HD uint32_t ll_code(uint32_t ll) {
+  if (ll < 16) return ll;
+  if (ll < 24) return 16 + ((ll - 16) >> 1);
+  if (ll < 32) return 20 + ((ll - 24) >> 2);
+  if (ll < 48) return 22 + ((ll - 32) >> 3);
+  if (ll < 64) return 24;
+  return highbit(ll) + 19;
+}
+OKV_ZE_HD uint32_t ll_bits(uint32_t c) {
+  return c < 16 ? 0 : c < 20 ? 1 : c < 22 ? 2 : c < 24 ? 3 : c == 24 ? 4 : c == 25 ? 6 : c - 19;
+}
+OKV_ZE_HD uint32_t ll_base(uint32_t c) {
+  if (c < 16) return c;
+  if (c < 20) return 16 + 2 * (c - 16);
+  if (c < 22) return 24 + 4 * (c - 20);
+  if (c < 24) return 32 + 8 * (c - 22);
+  if (c == 24) return 48;
+  return 1u << (c - 19);
+}
+// match lengths are coded as ml - 3 ("mb" below)
+OKV_ZE_HD uint32_t ml_code(uint32_t mb) {
+  if (mb < 32) return mb;
+  if (mb < 40) return 32 + ((mb - 32) >> 1);
+  if (mb < 48) return 36 + ((mb - 40) >> 2);
+  if (mb < 64) return 38 + ((mb - 48) >> 3);
+  if (mb < 96) return 40 + ((mb - 64) >> 4);
+  if (mb < 128) return 42;
+  return highbit(mb) + 36;
+}
+OKV_ZE_HD uint32_t ml_bits(uint32_t c) {
+  return c < 32 ? 0 : c < 36 ? 1 : c < 38 ? 2 : c < 40 ? 3 : c < 42 ? 4 : c == 42 ? 5 : c - 36;
+}
+OKV_ZE_HD uint32_t ml_base(uint32_t c) {  // of ml - 3
+  if (c < 32) return c;
+  if (c < 36) return 32 + 2 * (c - 32);
+  if (c < 38) return 40 + 4 * (c - 36);
+  if (c < 40) return 48 + 8 * (c - 38);
+  if (c < 42) return 64 + 16 * (c - 40);
+  if (c == 42) return 96;
+  return 1u << (c - 36);
+}
+
+// One sequence as the bitstream wants it: three symbols, and per field the number of
+// extra bits and their value.  off is the match distance (>= 1); it is always coded as
+// Offset_Value = off + 3, so no repeat-offset history exists on either side.
+struct SeqCode {
+  uint32_t sym[3];  // kLL, kML, kOF
+  uint32_t xb[3];   // extra bit counts
+  uint32_t xv[3];   // extra bit values
+};
+OKV_ZE_HD SeqCode seq_code(uint32_t ll, uint32_t ml, uint32_t off) {
+  SeqCode c;
+  c.sym[kLL] = ll_code(ll);
+  c.xb[kLL] = ll_bits(c.sym[kLL]);
+  c.xv[kLL] = ll - ll_base(c.sym[kLL]);
+  const uint32_t mb = ml - 3;
+  c.sym[kML] = ml_code(mb);
+  c.xb[kML] = ml_bits(c.sym[kML]);
+  c.xv[kML] = mb - ml_base(c.sym[kML]);
+  const uint32_t ov = off + 3;
+  c.sym[kOF] = highbit(ov);
+  c.xb[kOF] = c.sym[kOF];
+  c.xv[kOF] = ov - (1u << c.sym[kOF]);
+  return c;
+}
+// The symbol alone, for a state chain that walks one table.
+OKV_ZE_HD uint32_t seq_sym(uint32_t t, uint32_t ll, uint32_t ml, uint32_t off) {
+  return t == kLL ? ll_code(ll) : t == kML ? ml_code(ml - 3) : highbit(off + 3);
+}
+
+// The bits one sequence adds, in stream order (low bits first), as zstd's
+// ZSTD_encodeSequences adds them: for every sequence but the last the three state
+// steps -- offset, match length, literal length -- and then for every sequence the
+// extra bits: literal length, match length, offset.  `st` holds the (nb, bits) each
+// chain's step gave for this sequence (nb = 0 for the last sequence, whose symbols
+// the chains start from).  At most 17 + 16 + 16 + 28 bits: two words.
+struct SeqBits {
+  uint64_t lo, hi;  // hi is used only past 64 bits
+  uint32_t nb;
+};
+OKV_ZE_HD void bits_push(SeqBits& b, uint64_t v, uint32_t n) {
+  if (!n) return;
+  if (b.nb < 64) {
+    b.lo |= v << b.nb;
+    if (b.nb + n > 64) b.hi |= v >> (64 - b.nb);
+  } else {
+    b.hi |= v << (b.nb - 64);
+  }
+  b.nb += n;
+}
+OKV_ZE_HD SeqBits seq_bits(const SeqCode& c, const uint32_t st_nb[3], const uint32_t st_bits[3]) {
+  SeqBits b = {0, 0, 0};
+  bits_push(b, st_bits[kOF], st_nb[kOF]);
+  bits_push(b, st_bits[kML], st_nb[kML]);
+  bits_push(b, st_bits[kLL], st_nb[kLL]);
+  bits_push(b, c.xv[kLL], c.xb[kLL]);
+  bits_push(b, c.xv[kML], c.xb[kML]);
+  bits_push(b, c.xv[kOF], c.xb[kOF]);
+  return b;
+}
+// What closes the stream after the first sequence's bits: the final states, match
+// length, offset, literal length, each in its table's log bits, then the end mark.
+OKV_ZE_HD SeqBits close_bits(const uint32_t fin[3]) {
+  SeqBits b = {0, 0, 0};
+  bits_push(b, fin[kML] & 63u, 6);
+  bits_push(b, fin[kOF] & 31u, 5);
+  bits_push(b, fin[kLL] & 63u, 6);
+  bits_push(b, 1, 1);
+  return b;
+}
+
+// ---- header bytes ----------------------------------------------------------------
+// Frame header: magic, Single_Segment, Content_Checksum, no dictionary, and
+// Frame_Content_Size in the smallest field that holds it.  Returns its length (6..13).
+OKV_ZE_HD uint32_t frame_header_size(uint64_t fcs) {
+  return 5 + (fcs < 256 ? 1 : fcs < 65792 ? 2 : fcs < (uint64_t(1) << 32) ? 4 : 8);
+}
+OKV_ZE_HD uint32_t frame_header(uint8_t* p, uint64_t fcs) {
+  const uint32_t flag = fcs < 256 ? 0 : fcs < 65792 ? 1 : fcs < (uint64_t(1) << 32) ? 2 : 3;
+  const uint32_t nb = flag == 0 ? 1 : flag == 1 ? 2 : flag == 2 ? 4 : 8;
+  const uint64_t v = flag == 1 ? fcs - 256 : fcs;
+  p[0] = 0x28, p[1] = 0xB5, p[2] = 0x2F, p[3] = 0xFD;
+  p[4] = uint8_t((flag << 6) | (1u << 5) | (1u << 2));
+  for (uint32_t i = 0; i < nb; ++i) p[5 + i] = uint8_t(v >> (8 * i));
+  return 5 + nb;
+}
+constexpr uint32_t kBlockRaw = 0, kBlockRle = 1, kBlockCompressed = 2;
+OKV_ZE_HD void block_header(uint8_t* p, bool last, uint32_t type, uint32_t size) {
+  const uint32_t v = (last ? 1u : 0u) | (type << 1) | (size << 3);
+  p[0] = uint8_t(v), p[1] = uint8_t(v >> 8), p[2] = uint8_t(v >> 16);
+}
+// Raw_Literals_Block header: the 1-, 2- and 3-byte size formats.
+OKV_ZE_HD uint32_t lit_header_size(uint32_t n) { return n < 32 ? 1 : n < 4096 ? 2 : 3; }
+OKV_ZE_HD uint32_t lit_header(uint8_t* p, uint32_t n) {
+  if (n < 32) {
+    p[0] = uint8_t(n << 3);
+    return 1;
+  }
+  if (n < 4096) {
+    const uint32_t v = (n << 4) | (1u << 2);
+    p[0] = uint8_t(v), p[1] = uint8_t(v >> 8);
+    return 2;
+  }
+  const uint32_t v = (n << 4) | (3u << 2);
+  p[0] = uint8_t(v), p[1] = uint8_t(v >> 8), p[2] = uint8_t(v >> 16);
+  return 3;
+}
+// Number_of_Sequences: 1 byte below 128, 2 bytes below 0x7F00, else 3.
+OKV_ZE_HD uint32_t nseq_header_size(uint32_t n) { return n < 128 ? 1 : n < 0x7F00 ? 2 : 3; }
+OKV_ZE_HD uint32_t nseq_header(uint8_t* p, uint32_t n) {
+  if (n < 128) {
+    p[0] = uint8_t(n);
+    return 1;
+  }
+  if (n < 0x7F00) {
+    p[0] = uint8_t((n >> 8) + 128), p[1] = uint8_t(n);
+    return 2;
+  }
+  p[0] = 255, p[1] = uint8_t(n - 0x7F00), p[2] = uint8_t((n - 0x7F00) >> 8);
+  return 3;
+}
+// A Compressed_Block's size from its parts; the bitstream carries `bits` sequence bits
+// (close_bits included), rounded up to bytes.
+OKV_ZE_HD uint32_t compressed_size(uint32_t nlit, uint32_t nseq, uint64_t bits) {
+  return lit_header_size(nlit) + nlit + nseq_header_size(nseq) + 1 + uint32_t((bits + 7) >> 3);
+}
+// Upper bound of a frame for `orig` raw bytes: every unit a Raw_Block.
+OKV_ZE_HD uint64_t frame_bound(uint64_t orig) {
+  const uint64_t units = orig ? (orig + kUnit - 1) / kUnit : 1;
+  return orig + 3 * units + 18;
+}
+
+}  // namespace zenc
+}  // namespace okv

@@ -404,11 +404,13 @@ class Iter:
 
 
 def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, block_size=4096,
-            direction=DirectionAscending):
+            direction=DirectionAscending, zstd=False):
     """Merge resident segments (DeviceSegment, level) in priority order (newest
     first) into one new segment, on the GPU: every key's owning row (GetRange's
-    rule, :294-331), L0 tombstones dropped when drop_tombstones.  Returns the
-    sst.Encoded result (segment bytes + block index)."""
+    rule, :294-331), L0 tombstones dropped when drop_tombstones.  zstd: write the
+    output segment zstd-compressed with the device encoder (OKV_F_ZSTD_NATIVE:
+    its own frames, blocks cut on raw lengths).  Returns the Compacted result
+    (segment bytes + block index)."""
     import torch
     srcs = [(ds.t, 0, ds.n, lvl) for ds, lvl in segments]
     dev = torch.device("cuda", encoder.device)
@@ -428,9 +430,10 @@ def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, bl
                 for ds, _ in segments) - vb
     rows = {"key_arena": _Addr(kb), "key_off": out["key_off"], "key_len": out["key_len"],
             "val_arena": _Addr(vb), "val_off": out["val_off"], "val_len": out["val_len"]}
-    try:  # size query (zero capacities)
-        encoder.encode_device(rows, n, {}, threshold, block_size, COMP_NONE, False,
-                              key_arena_bytes=kspan, val_arena_bytes=vspan)
+    comp = _lib.COMP_ZSTD if zstd else COMP_NONE
+    try:  # size query (zero capacities; with zstd file_bytes is an upper bound)
+        encoder.encode_device(rows, n, {}, threshold, block_size, comp, False,
+                              key_arena_bytes=kspan, val_arena_bytes=vspan, zstd_native=zstd)
         raise AssertionError("size query must report OKV_E_CAPACITY")
     except OkvError as e:
         if e.code != _lib.OKV_E_CAPACITY:
@@ -441,8 +444,8 @@ def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, bl
             "first_row": torch.empty(nb + 1, dtype=torch.int64, device=dev),
             "desc": torch.empty((nb, 4), dtype=torch.int64, device=dev),
             "hash": torch.empty(nb, dtype=torch.int64, device=dev)}
-    eo = encoder.encode_device(rows, n, eout, threshold, block_size, COMP_NONE, False,
-                               key_arena_bytes=kspan, val_arena_bytes=vspan)
+    eo = encoder.encode_device(rows, n, eout, threshold, block_size, comp, False,
+                               key_arena_bytes=kspan, val_arena_bytes=vspan, zstd_native=zstd)
     return Compacted(eout["seg"][:int(eo.file_bytes)].cpu().numpy(), int(eo.file_bytes), n,
                      int(eo.n_blocks), eout, eo)
 
