@@ -43,7 +43,9 @@ extern "C" {
                                 still 6 with the batched GetRow (okv_index_*, okv_get_*,
                                 OKV_PATH_GET): new symbols only;
                                 still 6 with the device zstd encoder (OKV_F_ZSTD_NATIVE,
-                                OKV_PATH_ZSTD_ENC): one new flag bit and one path bit */
+                                OKV_PATH_ZSTD_ENC): one new flag bit and one path bit;
+                                still 6 with the snapshot GetRows (okv_snap_*,
+                                OKV_PATH_SNAP_GET): new symbols and one path bit */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -489,6 +491,83 @@ int okv_get_rows(okv_ctx *ctx, const uint8_t *seg, uint64_t seg_bytes, const okv
 int okv_get_totals(okv_ctx *ctx, okv_get_out *out);
 
 /* ======================================================================== *
+ * Snapshot GetRows: snapshot_reader.Reader.GetRow (snapshot_reader.go:104-149)
+ * for many keys against the segments of a snapshot, in one call.  Per key, in
+ * Go's order: the candidate segments (getPossibleSegmentsForKey, :152-171:
+ * DescendLessOrEqual over blockRangeTree from {FirstKey: key}, collecting while
+ * FirstKey <= key <= LastKey and stopping at the first record that fails, so a
+ * segment below a non-covering one is never asked); the candidates by Level
+ * ascending, then ID descending (:109-116); SegmentReader.GetRow of each in
+ * turn as okv_get_rows states it -- ErrNoRows moves on, a block error ends the
+ * key, a found row answers, and an empty value found at level 0 is a delete
+ * (:136-141).  A candidate after the one that answers is never consulted: the
+ * device probes every candidate (speculatively) and hides those outcomes.
+ * DESIGN.md 22.
+ *
+ * okv_snap is blockRangeTree on the device.  segs come in tree order
+ * (blockRangeLessFunc, :28-60: the host computes it) and `priority` is the
+ * segment's rank in GetRow's order: 0 is asked first; the priorities of a
+ * snapshot are a permutation of 0 .. n_segs - 1 (else OKV_E_ARG).  The snapshot
+ * keeps the pointers it is given: it owns neither the segments' bytes nor their
+ * indexes nor their filters, which must all outlive it and belong to ctx.
+ * ======================================================================== */
+typedef struct okv_snap okv_snap;
+typedef struct okv_snap_seg {
+  const uint8_t *seg;      /* device memory, 16-byte aligned; reads stay inside round16(seg_bytes) */
+  uint64_t seg_bytes;
+  const okv_index *index;  /* of ctx (another context: OKV_E_ARG) */
+  const okv_bloom *bloom;  /* of ctx, or NULL: no probe.  m == 0 with k > 0, or k > 4096:
+                              OKV_E_ARG, as okv_get_rows */
+  const uint8_t *first_key; /* host bytes: SegmentRecord.Metadata.FirstKey / LastKey */
+  const uint8_t *last_key;
+  uint16_t first_len, last_len;
+  int32_t compression;     /* OKV_COMP_* */
+  uint32_t level;
+  uint32_t priority;
+} okv_snap_seg;
+/* n_segs == 0 is legal (every key: OKV_SNAP_NO_ROWS); fewer than 2^32 - 1 blocks in all */
+int okv_snap_new(okv_ctx *ctx, const okv_snap_seg *segs, uint32_t n_segs, okv_snap **out);
+void okv_snap_free(okv_snap *snap);
+
+#define OKV_SNAP_FOUND 0     /* val_off / val_len (0 <=> nil) in segment `seg` */
+#define OKV_SNAP_NO_ROWS 1   /* ErrNoRows: no candidate has the row */
+#define OKV_SNAP_DELETED 2   /* ErrNoRows too: an empty value found at level 0 (:136-141) */
+#define OKV_SNAP_SEG_ERROR 3 /* blk_status[i] = OKV_BLK_EOF / _SHORT / _PANIC of segment `seg` */
+#define OKV_SNAP_FALLBACK 4  /* the resolution reached, before any answer, a candidate this path
+                                does not take (zstd, BlockSize > 64 KiB): send the whole key
+                                through the single-key path */
+
+typedef struct okv_snap_out {
+  int32_t *state;      /* [n] OKV_SNAP_* */
+  uint32_t *seg;       /* [n] the answering (FOUND, DELETED) or failing (SEG_ERROR, FALLBACK)
+                          segment's position in segs as given; UINT32_MAX when none */
+  int32_t *blk_status; /* [n] OKV_BLK_* of that segment's floor block (OKV_BLK_OK otherwise) */
+  uint32_t *entry;     /* [n] file index of that floor block, UINT32_MAX when none */
+  uint64_t *val_off;   /* [n] FOUND: byte offset of the value in that segment (else 0) */
+  uint32_t *val_len;   /* [n] FOUND: its length, 0 <=> nil (else 0) */
+  uint64_t *val_pos;   /* [n] or NULL: offset of the value in val_arena, 16-byte aligned;
+                          keys that are not FOUND take no room */
+  uint8_t *val_arena;  /* or NULL (index only); each value is zero-padded to 16 bytes;
+                          a device arena must be 16-byte aligned */
+  uint64_t val_cap;
+  /* filled on return (also with OKV_E_CAPACITY, then val_arena is not written): */
+  uint64_t n_found, n_deleted, n_fallback, val_bytes;
+  uint64_t pairs_probed;    /* (key, candidate segment) pairs: every candidate is probed */
+  uint64_t blocks_searched; /* distinct (segment, floor block) staged and walked, once each */
+} okv_snap_out;
+
+/*
+ * keys, flags, n_rows == 0 and OKV_E_CAPACITY as okv_get_rows.  Fewer than 2^32 keys,
+ * and n_rows * n_segs < 2^32 (the pair scratch is sized for every key meeting every
+ * segment; more: OKV_E_ARG).  There is no cap on the candidates of one key.
+ */
+int okv_snap_get_rows(okv_ctx *ctx, const okv_snap *snap, const okv_rows *keys,
+                      okv_snap_out *out, uint32_t flags);
+/* After an OKV_F_ASYNC okv_snap_get_rows and okv_sync(): the totals of the context's last
+ * call (OKV_E_CAPACITY as the synchronous call would have returned it). */
+int okv_snap_totals(okv_ctx *ctx, okv_snap_out *out);
+
+/* ======================================================================== *
  * Merge: snapshot_reader.Reader.GetRange's k-way merge
  * (/root/reference/snapshot_reader/snapshot_reader.go:214-372) on the device,
  * and the same newest-wins merge as a compaction feed.
@@ -605,6 +684,8 @@ int okv_profile_read(okv_ctx *ctx, double *ms, uint64_t *calls);
                              okv_get_search_kernel */
 #define OKV_PATH_ZSTD_ENC 16384u /* okv_encode_rows compressed the blocks on the device
                                     (OKV_F_ZSTD_NATIVE: okv_zenc_unit_kernel and its placement) */
+#define OKV_PATH_SNAP_GET 32768u /* okv_snap_get_rows: route, locate, the grouping, the search
+                                    and okv_snap_resolve_kernel */
 uint32_t okv_last_path(const okv_ctx *ctx);
 
 /* Device / pinned-host memory helpers for callers without another allocator. */

@@ -10,8 +10,10 @@ from .sst import (Decoded, Decoder, Encoded, Encoder, GpuSegmentWriter, Metadata
                   synth_segment, xxh64)
 from .bloom import DeviceBloom  # noqa: F401
 from .get import DeviceIndex, get_rows  # noqa: F401
+from .snap import DeviceSnapshot, snap_get_rows  # noqa: F401
 
 __all__ = ["build", "lib", "Decoder", "Decoded", "DeviceBloom", "DeviceIndex", "get_rows",
+           "DeviceSnapshot", "snap_get_rows",
            "Encoder", "Encoded",
            "GpuSegmentWriter",
            "Metadata", "OkvError", "SegmentWriter", "pack_rows",

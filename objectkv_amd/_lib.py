@@ -40,9 +40,12 @@ PATH_ZSTD_REGROW, PATH_ENC_ONEPASS, PATH_STREAM = 256, 512, 1024
 PATH_POINT, PATH_GROUP = 2048, 4096
 PATH_GET = 8192
 PATH_ZSTD_ENC = 16384
+PATH_SNAP_GET = 32768
 # okv_get_out.state (include/okv_sst.h OKV_GET_*)
 GET_FOUND, GET_BLOOM_NEGATIVE, GET_NO_BLOCK, GET_NOT_IN_BLOCK = 0, 1, 2, 3
 GET_BLOCK_ERROR, GET_FALLBACK = 4, 5
+# okv_snap_out.state (include/okv_sst.h OKV_SNAP_*)
+SNAP_FOUND, SNAP_NO_ROWS, SNAP_DELETED, SNAP_SEG_ERROR, SNAP_FALLBACK = 0, 1, 2, 3, 4
 # SegmentWriter sentinels (okv_sst.h OKV_W_*)
 W_KEY_TOO_LARGE, W_VALUE_TOO_LARGE, W_CLOSED, W_INVALID_KEY = -101, -102, -103, -104
 W_NIL_WRITER, W_UNSUPPORTED, W_NO_ROWS = -105, -106, -107
@@ -65,6 +68,7 @@ SYMBOLS = [
     "okv_bloom_info", "okv_bloom_clear", "okv_bloom_add_rows", "okv_bloom_test_rows",
     "okv_bloom_write_to", "okv_bloom_last_path",
     "okv_index_new", "okv_index_free", "okv_index_info", "okv_get_rows", "okv_get_totals",
+    "okv_snap_new", "okv_snap_free", "okv_snap_get_rows", "okv_snap_totals",
     "okv_writer_new", "okv_writer_write_row", "okv_writer_close", "okv_writer_data",
     "okv_writer_meta", "okv_writer_num_blocks", "okv_writer_block", "okv_writer_free",
     "okv_writer_set_bloom",
@@ -140,6 +144,24 @@ class GetOut(C.Structure):
                 ("val_off", C.c_void_p), ("val_len", C.c_void_p), ("val_pos", C.c_void_p),
                 ("val_arena", C.c_void_p), ("val_cap", C.c_uint64), ("n_found", C.c_uint64),
                 ("n_fallback", C.c_uint64), ("val_bytes", C.c_uint64),
+                ("blocks_searched", C.c_uint64)]
+
+
+class SnapSeg(C.Structure):
+    """okv_snap_seg (include/okv_sst.h)."""
+    _fields_ = [("seg", C.c_void_p), ("seg_bytes", C.c_uint64), ("index", C.c_void_p),
+                ("bloom", C.c_void_p), ("first_key", C.c_void_p), ("last_key", C.c_void_p),
+                ("first_len", C.c_uint16), ("last_len", C.c_uint16), ("compression", C.c_int32),
+                ("level", C.c_uint32), ("priority", C.c_uint32)]
+
+
+class SnapOut(C.Structure):
+    """okv_snap_out (include/okv_sst.h)."""
+    _fields_ = [("state", C.c_void_p), ("seg", C.c_void_p), ("blk_status", C.c_void_p),
+                ("entry", C.c_void_p), ("val_off", C.c_void_p), ("val_len", C.c_void_p),
+                ("val_pos", C.c_void_p), ("val_arena", C.c_void_p), ("val_cap", C.c_uint64),
+                ("n_found", C.c_uint64), ("n_deleted", C.c_uint64), ("n_fallback", C.c_uint64),
+                ("val_bytes", C.c_uint64), ("pairs_probed", C.c_uint64),
                 ("blocks_searched", C.c_uint64)]
 
 
@@ -243,6 +265,10 @@ def lib():
         "okv_index_info": (i32, [p, C.POINTER(u64), C.POINTER(u64)]),
         "okv_get_rows": (i32, [p, p, u64, p, p, C.POINTER(Rows), i32, C.POINTER(GetOut), u32]),
         "okv_get_totals": (i32, [p, C.POINTER(GetOut)]),
+        "okv_snap_new": (i32, [p, C.POINTER(SnapSeg), u32, C.POINTER(p)]),
+        "okv_snap_free": (None, [p]),
+        "okv_snap_get_rows": (i32, [p, p, C.POINTER(Rows), C.POINTER(SnapOut), u32]),
+        "okv_snap_totals": (i32, [p, C.POINTER(SnapOut)]),
         "okv_writer_new": (p, [u64, u64, i32, i32]),
         "okv_writer_write_row": (i32, [p, p, C.c_size_t, p, C.c_size_t]),
         "okv_writer_close": (i32, [p, i32, C.POINTER(u64), C.POINTER(u64)]),

@@ -1,12 +1,12 @@
 // okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip), encode
 // (okv_encode.hip), zstd (okv_zstd.hip), merge (okv_merge.hip) and batched GetRow
-// (okv_get.hip) translation units, and the zstd encoder (okv_zstd_enc.hip).
+// (okv_get.hip, okv_snap.hip) translation units, and the zstd encoder (okv_zstd_enc.hip).
 // Internal header.
 // Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
 // its capacity and frees itself with its owner; kernels get raw pointers from data().  The
 // owners are okv_ctx (decode), AblateState (the decode ablation arms) and, each defined in its
 // own file behind a forward declaration here and released by okv_close: EncScratch,
-// zst::Scratch, mrg::Scratch, get::Scratch and zenc::Scratch.
+// zst::Scratch, mrg::Scratch, get::Scratch, snap::Scratch and zenc::Scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #define OKV_BUF_HIP
@@ -31,6 +31,10 @@ namespace get {
 struct Scratch;  // okv_get.hip
 }
 void get_release(okv_ctx* ctx);
+namespace snap {
+struct Scratch;  // okv_snap.hip
+}
+void snap_release(okv_ctx* ctx);
 // okv_bloom.hip: what another translation unit's kernel needs to probe a device filter.
 struct BloomView {
   okv_ctx* ctx;
@@ -175,6 +179,7 @@ struct okv_ctx {
   okv::mrg::Scratch* merge = nullptr;  // merge scratch (okv_merge.hip)
   okv::zst::Scratch* zstd = nullptr;   // zstd stage scratch (okv_zstd.hip)
   okv::get::Scratch* get = nullptr;    // batched GetRow scratch (okv_get.hip)
+  okv::snap::Scratch* snap = nullptr;  // snapshot GetRows scratch (okv_snap.hip)
   okv::zenc::Scratch* zenc = nullptr;  // zstd encoder scratch (okv_zstd_enc.hip)
 };
 

@@ -2837,6 +2837,7 @@ void okv_close(okv_ctx* ctx) {
   okv::zstd_enc_release(ctx);
   okv::merge_release(ctx);
   okv::get_release(ctx);
+  okv::snap_release(ctx);
   const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;
   delete ctx;  // every scratch buffer releases itself
   if (owned) (void)hipStreamDestroy(owned);

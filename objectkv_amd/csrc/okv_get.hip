@@ -17,39 +17,21 @@
 //                           round16(val_len) of the found keys scanned in key order, the
 //                           values copied out with 16-byte stores
 //
+// The bodies of the locate, scan, scatter, search and value steps are in
+// okv_get_kernels.hpp, which okv_snap.hip (the same batch against a whole snapshot) shares.
+//
 // No kernel waits for another workgroup, and every loop is bounded by an argument of
 // the call: the binary search by 64 steps, the probe by k <= 4096, a walk by
 // BlockSize / 6 records, a compare by the key length (u16), the lists by the key count.
-#include "okv_ctx.hpp"
+#include "okv_get_kernels.hpp"
 
 #include <cstring>
 #include <memory>
 
 #include "okv_bloom_hash.hpp"
-#include "okv_index.hpp"
-
-struct okv_index {
-  okv_ctx* ctx = nullptr;
-  uint64_t nt = 0, nf = 0;     // tree entries, entries given
-  uint64_t max_block = 0;      // largest BlockSize in the tree
-  uint32_t n_cu = 0;
-  okv::DevBuf<okv::Desc> descs;        // [nt] tree order
-  okv::DevBuf<uint32_t> file_index;    // [nt]
-  okv::DevBuf<uint8_t> arena;          // first keys
-  okv::DevBuf<uint64_t> off;           // [nt]
-  okv::DevBuf<uint16_t> len;           // [nt]
-  okv::DevBuf<uint64_t> prefix;        // [nt]
-};
 
 namespace okv {
 namespace get {
-
-constexpr uint32_t kNone = 0xffffffffu;
-constexpr uint32_t kSmallCap = 8192;       // the search kernel's small stage (4 KiB blocks)
-constexpr uint32_t kSearchThreads = 1024;  // 16 waves share a staged block's keys
-constexpr uint32_t kScanPer = 8;           // elements per thread of a scan tile
-constexpr uint32_t kScanTile = kThreads * kScanPer;
-constexpr uint64_t kMaxK = 4096;           // as okv_bloom.hip
 
 struct GetTotals {
   uint64_t n_found, n_fallback, val_bytes, blocks;
@@ -111,41 +93,11 @@ __global__ __launch_bounds__(kThreads) void okv_get_locate_kernel(Params P) {
        i += uint64_t(gridDim.x) * kThreads) {
     const uint8_t* key = P.ka + P.ko[i];
     const uint32_t kl = P.kl[i];
-    int32_t state = OKV_GET_NOT_IN_BLOCK, bst = OKV_BLK_OK;
-    uint32_t entry = kNone, t = kNone;
-    bool maybe = true;
-    if (P.k) {  // Test (:371-378): a location >= length reads as unset (bitset.Test)
-      uint64_t h[4];
-      bloom::base_hashes(key, kl, h);
-      for (uint32_t j = 0; j < P.k; ++j) {
-        const uint64_t loc = bloom::location(h, j, P.mod);
-        if (loc >= P.length || !((P.words[loc >> 6] >> (loc & 63)) & 1)) {
-          maybe = false;
-          break;
-        }
-      }
-    }
-    if (!maybe) {
-      state = OKV_GET_BLOOM_NEGATIVE;
-    } else {
-      const uint64_t up = index::floor_upper(P.ix, key, kl, index::prefix8(key, kl));
-      if (up == 0) {
-        state = OKV_GET_NO_BLOCK;  // :387-389
-      } else {
-        const uint32_t tt = uint32_t(up - 1);
-        const Desc d = P.descs[tt];
-        entry = P.file_index[tt];
-        bst = go_read_status(d, P.seg_bytes);  // :303-316, before any read
-        if (bst != OKV_BLK_OK) {
-          state = OKV_GET_BLOCK_ERROR;
-        } else if (P.comp == OKV_COMP_ZSTD || d.block_size > uint64_t(kStage)) {
-          state = OKV_GET_FALLBACK;
-        } else {
-          t = tt;
-          atomicAdd(&P.cnt[tt], 1u);
-        }
-      }
-    }
+    int32_t state, bst;
+    uint32_t entry, t;
+    locate_key(key, kl, Filter{P.words, P.mod, P.k, P.length}, P.ix, P.descs, P.file_index,
+               P.seg_bytes, P.comp, state, bst, entry, t);
+    if (t != kNone) atomicAdd(&P.cnt[t], 1u);
     P.state[i] = state;
     P.blk_status[i] = bst;
     P.entry[i] = entry;
@@ -155,87 +107,29 @@ __global__ __launch_bounds__(kThreads) void okv_get_locate_kernel(Params P) {
   }
 }
 
-// ---- exclusive scan of a u64 per element: tile sums (wg_excl_scan, okv_kernels.hpp), their
-// scan by the encode's one-workgroup kernel (launch_scan_u64), the tiles again.  Three
-// launches; no workgroup waits for another. -------------------------------------------
-struct CntLoad {  // keys on the block | (block touched) << 32
-  const uint32_t* cnt;
-  __device__ uint64_t operator()(uint64_t i) const {
-    const uint32_t c = cnt[i];
-    return uint64_t(c) | (uint64_t(c != 0) << 32);
-  }
-};
-struct ValLoad {  // arena room of the key's value
-  const int32_t* state;
-  const uint32_t* val_len;
-  __device__ uint64_t operator()(uint64_t i) const {
-    return state[i] == OKV_GET_FOUND ? round16(val_len[i]) : 0;
-  }
-};
-
-template <class Load>
-__global__ __launch_bounds__(kThreads) void okv_get_scan_sums_kernel(Load ld, uint64_t n,
-                                                                     uint64_t* __restrict__ tsum) {
-  __shared__ uint64_t sm[kThreads / 64 + 1];
-  const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
-  uint64_t s = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < kScanPer; ++j)
-    if (base + j < n) s += ld(base + j);
-  uint64_t total;
-  (void)wg_excl_scan(s, sm, total);
-  if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-// out[i] = sum of ld(j), j < i; out[n] = the total; out2 (may be null): out[0 .. n) again
-template <class Load>
-__global__ __launch_bounds__(kThreads) void okv_get_scan_write_kernel(
-    Load ld, uint64_t n, const uint64_t* __restrict__ tsum, uint64_t* __restrict__ out,
-    uint64_t* __restrict__ out2) {
-  __shared__ uint64_t sm[kThreads / 64 + 1];
-  const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
-  uint64_t v[kScanPer], s = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < kScanPer; ++j) {
-    v[j] = base + j < n ? ld(base + j) : 0;
-    s += v[j];
-  }
-  uint64_t total;
-  uint64_t x = wg_excl_scan(s, sm, total) + tsum[blockIdx.x];
-#pragma unroll
-  for (uint32_t j = 0; j < kScanPer; ++j) {
-    if (base + j < n) {
-      out[base + j] = x;
-      if (out2) out2[base + j] = x;
-    }
-    x += v[j];
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = tsum[gridDim.x];
-}
-
 // ---- grouping: keys into per-block lists, touched blocks into the work list ----
 __global__ __launch_bounds__(kThreads) void okv_get_scatter_kernel(Params P) {
-  const uint64_t stride = uint64_t(gridDim.x) * kThreads;
-  const uint64_t first = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-  for (uint64_t i = first; i < P.n; i += stride) {
-    const uint32_t t = P.tpos[i];
-    if (t == kNone) continue;
-    // (the count is taken down as the list fills: zero again for the next call)
-    const uint32_t slot = uint32_t(P.gscan[t]) + atomicSub(&P.cnt[t], 1u) - 1u;
-    P.list[slot] = uint32_t(i);
-  }
-  for (uint64_t t = first; t < P.ix.nt; t += stride) {
-    const uint64_t a = P.gscan[t], b = P.gscan[t + 1];
-    if (uint32_t(a) != uint32_t(b)) P.work[uint32_t(a >> 32)] = uint32_t(t);
-  }
-  if (first == 0) P.tot->blocks = P.gscan[P.ix.nt] >> 32;
+  scatter_items(P.n, P.ix.nt, P.tpos, P.gscan, P.cnt, P.list, P.work, &P.tot->blocks);
 }
 
 // ---- search --------------------------------------------------------------------
-template <uint32_t kCap>
-struct __align__(16) SearchSmem {
-  uint4 stage[(kCap + kStagePad) / 16];  // [16 B guard][block image][guard]
-  uint16_t rec[kCap / 6 + 2];            // every record's position (< 64 KiB)
+struct GetSrc {  // search_blocks over one segment: an item is a key
+  const Params& P;
+  int32_t* state;
+  int32_t* blk_status;
+  uint64_t* val_off;
+  uint32_t* val_len;
+  __device__ __forceinline__ uint32_t touched() const { return uint32_t(P.gscan[P.ix.nt] >> 32); }
+  __device__ __forceinline__ void block(uint32_t w, const uint8_t*& seg, int& comp, Desc& d,
+                                        uint32_t& k0, uint32_t& k1) const {
+    const uint32_t t = P.work[w];
+    seg = P.seg, comp = P.comp, d = P.descs[t];
+    k0 = uint32_t(P.gscan[t]), k1 = uint32_t(P.gscan[t + 1]);
+  }
+  __device__ __forceinline__ uint32_t item(uint32_t j) const { return P.list[j]; }
+  __device__ __forceinline__ void key(uint32_t i, const uint8_t*& key, uint32_t& kl) const {
+    key = P.ka + P.ko[i], kl = P.kl[i];
+  }
 };
 
 template <uint32_t kCap>
@@ -243,68 +137,7 @@ __global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P
   __shared__ SearchSmem<kCap> sm;
   __shared__ int32_t s_st;
   __shared__ uint32_t s_rows;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t touched = uint32_t(P.gscan[P.ix.nt] >> 32);
-  for (uint32_t w = blockIdx.x; w < touched; w += gridDim.x) {
-    const uint32_t t = P.work[w];
-    const Desc d = P.descs[t];
-    const uint32_t k0 = uint32_t(P.gscan[t]), k1 = uint32_t(P.gscan[t + 1]);
-    if (d.block_size > kCap) continue;  // (the launch sized kCap for the whole index)
-    // the block passed go_read_status in the locate kernel: its BlockSize bytes are
-    // in the segment.  Q7 (:331-333): the LZ4 flag decodes an empty buffer
-    const uint32_t L = P.comp == OKV_COMP_LZ4 ? 0u : uint32_t(d.block_size);
-    const Staged src{sm.stage, stage_block_wg<kSearchThreads>(sm.stage, P.seg, d.offset, L)};
-    __syncthreads();
-    if (tid < 64) {  // ReadBlockWithStat's record loop (:338-352) in full, by wave 0
-      int32_t st = OKV_BLK_OK;
-      uint64_t rows = 0, kb = 0, vb = 0, pend = 0;
-      uint16_t* rec = sm.rec;
-      walk_staged_to(src, L, d.original_size,
-                     [rec](uint32_t row, uint32_t pos) { rec[row] = uint16_t(pos); }, lane, st,
-                     rows, kb, vb, pend);
-      if (lane == 0) {
-        s_st = st;
-        s_rows = uint32_t(rows);
-      }
-    }
-    __syncthreads();
-    const int32_t st = s_st;
-    const uint32_t rows = s_rows;
-    // the block's keys over the waves; per key, lanes over the rows in block order
-    for (uint32_t j = k0 + wave; j < k1; j += kSearchThreads / 64) {
-      const uint32_t i = P.list[j];
-      if (st != OKV_BLK_OK) {  // a failed block fails its keys, wherever the bad record is
-        if (lane == 0) {
-          P.state[i] = OKV_GET_BLOCK_ERROR;
-          P.blk_status[i] = st;
-        }
-        continue;
-      }
-      const uint8_t* key = P.ka + P.ko[i];
-      const uint32_t kl = P.kl[i];
-      uint32_t hit = kNone;
-      for (uint32_t r0 = 0; r0 < rows; r0 += 64) {
-        const uint32_t r = r0 + lane;
-        const bool eq = r < rows && key_equal(src, sm.rec[r], kl, [key, kl](uint32_t b) {
-                          return key_dword(key, kl, b);
-                        });
-        const uint64_t bm = __ballot(eq);
-        if (bm) {  // the lowest matching row of the earliest round: the first in block order
-          hit = r0 + uint32_t(__builtin_ctzll(bm));
-          break;
-        }
-      }
-      if (lane == 0 && hit != kNone) {
-        const uint32_t pos = sm.rec[hit];
-        uint32_t rkl, rvl;
-        src.header(pos, rkl, rvl);
-        P.state[i] = OKV_GET_FOUND;
-        P.val_off[i] = d.offset + pos + 6 + rkl;
-        P.val_len[i] = rvl;
-      }
-    }
-    __syncthreads();  // the stage and the positions are reused by the next block
-  }
+  search_blocks<kCap>(GetSrc{P, P.state, P.blk_status, P.val_off, P.val_len}, sm, s_st, s_rows);
 }
 
 // ---- values ----------------------------------------------------------------------
@@ -341,36 +174,15 @@ __global__ __launch_bounds__(kThreads) void okv_get_values_kernel(Params P) {
     if (P.state[i] != OKV_GET_FOUND) continue;
     const uint32_t vl = P.val_len[i];
     const uint64_t off = P.val_off[i];
-    uint4* dst = reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]);
-    for (uint32_t c = lane; c < (vl + 15) / 16; c += 64) {
-      const uint4 v = window16(P.seg, P.seg_bytes, int64_t(off + 16ull * c));
-      const int32_t nb = int32_t(min(16u, vl - 16 * c));
-      dst[c] = merge_bytes(make_uint4(0, 0, 0, 0), v, 0, nb);
-    }
+    copy_value(P.seg, P.seg_bytes, off, vl, reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]),
+               lane);
   }
 }
 
 // ---- host ------------------------------------------------------------------------
-uint32_t ceil_div(uint64_t a, uint64_t b) { return uint32_t((a + b - 1) / b); }
-
 Scratch* scratch(okv_ctx* ctx) {
   if (!ctx->get) ctx->get = new Scratch();
   return ctx->get;
-}
-
-template <class Load>
-int scan(okv_ctx* ctx, Scratch* s, Load ld, uint64_t n, uint64_t* out, uint64_t* out2) {
-  const uint32_t ntiles = ceil_div(n, kScanTile);  // (n > 0)
-  if (int rc = reserve(ctx, s->tsum, size_t(ntiles) + 1)) return rc;
-  if (int rc = reserve(ctx, s->tsum_in, size_t(ntiles))) return rc;
-  hipLaunchKernelGGL(okv_get_scan_sums_kernel<Load>, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
-                     ld, n, s->tsum_in.data());
-  launch_scan_u64(ctx->stream, s->tsum_in.data(), ntiles, s->tsum.data(),
-                  reinterpret_cast<unsigned long long*>(s->tsum.data() + ntiles));
-  hipLaunchKernelGGL(okv_get_scan_write_kernel<Load>, dim3(ntiles), dim3(kThreads), 0, ctx->stream,
-                     ld, n, s->tsum.data(), out, out2);
-  OKV_HIP(hipGetLastError());
-  return OKV_OK;
 }
 
 // Everything up to the totals, enqueued: locate, grouping, search, the value scan
@@ -395,7 +207,7 @@ int run(okv_ctx* ctx, Scratch* s, const okv_index* ix, Params& P, uint64_t* val_
   hipLaunchKernelGGL(okv_get_locate_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
   if (nt) {
-    if (int rc = scan(ctx, s, CntLoad{P.cnt}, nt, P.gscan, nullptr)) return rc;
+    if (int rc = scan(ctx, s->tsum_in, s->tsum, CntLoad{P.cnt}, nt, P.gscan, nullptr)) return rc;
     const uint32_t gs = std::max(1u, std::min(ceil_div(std::max(n, nt), kThreads), cap));
     hipLaunchKernelGGL(okv_get_scatter_kernel, dim3(gs), dim3(kThreads), 0, ctx->stream, P);
     const uint64_t most = std::min(n, nt);  // touched blocks at most
@@ -410,7 +222,7 @@ int run(okv_ctx* ctx, Scratch* s, const okv_index* ix, Params& P, uint64_t* val_
     }
     OKV_HIP(hipGetLastError());
   }
-  if (int rc = scan(ctx, s, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos)) return rc;
+  if (int rc = scan(ctx, s->tsum_in, s->tsum, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos)) return rc;
   hipLaunchKernelGGL(okv_get_count_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
   return OKV_OK;

@@ -139,10 +139,18 @@ inline View view_of(const Image& im) {
   return View{im.prefix.data(), im.arena.data(), im.off.data(), im.len.data(), im.prefix.size()};
 }
 
+// a <= b for two keys whose prefix8 tie: the bytes from min(8, shorter length) on (the
+// bytes before are equal then) and last the lengths.
+OKV_INDEX_HD bool tie_le(const uint8_t* a, uint32_t al, const uint8_t* b, uint32_t bl) {
+  const uint32_t n = al < bl ? al : bl;
+  int c = 0;
+  for (uint32_t j = n < 8 ? n : 8; j < n && c == 0; ++j) c = int(a[j]) - int(b[j]);
+  return c != 0 ? c < 0 : al <= bl;
+}
+
 // upper(k) over the image: the number of tree entries whose FirstKey <= k, so the
 // floor entry of DescendLessOrEqual is the one before it (none when 0).  kp is
-// prefix8(k).  A step compares the prefixes; when they tie, the bytes from
-// min(8, shorter length) on (the bytes before are equal then) and last the lengths.
+// prefix8(k).  A step compares the prefixes; when they tie, tie_le.
 // At most 64 steps (nt < 2^64).
 OKV_INDEX_HD uint64_t floor_upper(const View& v, const uint8_t* k, uint32_t kl, uint64_t kp) {
   uint64_t lo = 0, hi = v.nt;
@@ -150,16 +158,10 @@ OKV_INDEX_HD uint64_t floor_upper(const View& v, const uint8_t* k, uint32_t kl, 
     const uint64_t m = lo + (hi - lo) / 2;
     const uint64_t ep = v.prefix[m];
     bool le;  // entry m <= k
-    if (ep != kp) {
+    if (ep != kp)
       le = ep < kp;
-    } else {
-      const uint32_t el = v.len[m];
-      const uint8_t* e = v.arena + v.off[m];
-      const uint32_t n = el < kl ? el : kl;
-      int c = 0;
-      for (uint32_t j = n < 8 ? n : 8; j < n && c == 0; ++j) c = int(e[j]) - int(k[j]);
-      le = c != 0 ? c < 0 : el <= kl;
-    }
+    else
+      le = tie_le(v.arena + v.off[m], v.len[m], k, kl);
     if (le)
       lo = m + 1;
     else

@@ -2,7 +2,8 @@
 
 Mirrors /root/reference/snapshot_reader/snapshot_reader.go and
 snapshot_iter.go: Reader (NewReader, UpdateSegments, GetRow, GetRange,
-RowIter) and Iter (Next, Peek).  The segment index (the two btrees and their
+RowIter) and Iter (Next, Peek); GetRows is GetRow for a batch of keys in one device
+call (okv_snap_get_rows, objectkv_amd/snap.py) over the segments' raw bytes.  The segment index (the two btrees and their
 quirky descend-and-stop search, :149-193) and the per-segment Seek positions
 are host control logic, restated statement by statement; every block read is
 the batched GPU decode and every GetRange merge is okv_merge_rows
@@ -246,6 +247,8 @@ class Reader:
         self.readerFactory = factory
         self.decoder = decoder or Decoder(0)
         self._segs: dict[str, DeviceSegment] = {}
+        self._raw: dict[str, tuple] = {}  # GetRows: raw bytes, block index and filter by ID
+        self._snap = None                 # GetRows: the DeviceSnapshot of the current set
 
     def _seg(self, rec) -> DeviceSegment:
         s = self._segs.get(rec.ID)
@@ -260,10 +263,13 @@ class Reader:
                 continue
             self.blockRangeTree.delete(d)
             self._segs.pop(d.ID, None)
+            self._raw.pop(d.ID, None)
         for a in add or []:
             self.segmentIDTree.replace_or_insert(a)
             self.blockRangeTree.replace_or_insert(a)
             self._segs.pop(a.ID, None)
+            self._raw.pop(a.ID, None)
+        self._snap = None
 
     def _possible_for_key(self, key):  # :149-170
         out = []
@@ -298,6 +304,73 @@ class Reader:
                 raise SnapshotError("ErrNoRows")  # a delete
             return row.Value
         raise SnapshotError("ErrNoRows")
+
+    def _raw_seg(self, rec):
+        """The segment's raw bytes, block index and filter on the device, uploaded once
+        per segment ID -> DeviceSnapshot's segment tuple."""
+        s = self._raw.get(rec.ID)
+        if s is None:
+            import torch
+            from .bloom import DeviceBloom
+            from .get import DeviceIndex
+            data, n = self.readerFactory(rec)
+            raw = np.frombuffer(bytes(data), np.uint8)
+            md = fetch_metadata(raw, n)
+            t = torch.zeros(raw.size + 32, dtype=torch.uint8,
+                            device=torch.device("cuda", self.decoder.device))
+            if raw.size:
+                t[:raw.size] = torch.from_numpy(raw.copy())
+            bb = _bloom_bytes(raw, n)
+            bloom = DeviceBloom.from_bytes(self.decoder, bb) if bb is not None else None
+            s = self._raw[rec.ID] = (t, raw.size, DeviceIndex.from_metadata(self.decoder, md),
+                                     bloom, md.compression)
+        return s + (rec.Level, rec.ID, rec.FirstKey, rec.LastKey)
+
+    def _device_snapshot(self):
+        """The DeviceSnapshot of blockRangeTree, rebuilt when the segment set changed; None
+        when a segment carries a filter the device refuses (OKV_E_ARG)."""
+        if self._snap is None:
+            from .snap import DeviceSnapshot
+            try:
+                self._snap = DeviceSnapshot(self.decoder,
+                                            [self._raw_seg(r) for r in self.blockRangeTree.items])
+            except OkvError as e:
+                if e.code != _lib.OKV_E_ARG:
+                    raise
+                self._snap = False
+        return self._snap or None
+
+    def _get_row_outcome(self, key):
+        try:
+            return self.GetRow(key)
+        except (SnapshotError, SnapshotPanic) as e:
+            return e
+
+    def GetRows(self, keys):
+        """GetRow for every key in one device call (okv_snap_get_rows): per key the value
+        GetRow returns (None for nil), or the SnapshotError / SnapshotPanic Go's GetRow
+        would give (returned, not raised).  Keys the device hands back (OKV_SNAP_FALLBACK)
+        and snapshots with a filter the device refuses go through GetRow."""
+        from . import snap as S
+        ks = [_b(k) for k in keys]
+        if not ks:
+            return []
+        ds = self._device_snapshot()
+        if ds is None:
+            return [self._get_row_outcome(k) for k in ks]
+        res = S.snap_get_rows(self.decoder, ds, ks)
+        out = []
+        for i, k in enumerate(ks):
+            st = int(res.state[i])
+            if st == S.SNAP_FOUND:
+                out.append(res.value(i))
+            elif st in (S.SNAP_NO_ROWS, S.SNAP_DELETED):
+                out.append(SnapshotError("ErrNoRows"))
+            elif st == S.SNAP_SEG_ERROR:
+                out.append(_block_error(int(res.blk_status[i]), ds.ids[int(res.seg[i])]))
+            else:
+                out.append(self._get_row_outcome(k))
+        return out
 
     def GetRange(self, start, end, limit, direction):  # :214-372
         if _cmp(start, end) >= 0:
@@ -347,6 +420,29 @@ class Reader:
 
     def RowIter(self, start, direction, bufferSize=100):  # :430-443
         return Iter(self, start, direction, bufferSize)
+
+
+def _bloom_bytes(raw, file_len):
+    """The filter bytes of the segment's meta block (BloomFilter.WriteTo), or None."""
+    import ctypes as C
+    L = _lib.lib()
+    h = C.c_void_p()
+    if L.okv_meta_fetch(raw.ctypes.data, raw.size, file_len, C.byref(h)):
+        return None
+    try:
+        n = C.c_uint64()
+        p = L.okv_meta_bloom_bytes(h, C.byref(n))
+        return C.string_at(p, n.value) if p else None
+    finally:
+        L.okv_meta_free(h)
+
+
+def _block_error(blk_status, seg_id):
+    """ReadBlockWithStat's failure (segment_reader.go:303-352) as GetRow passes it on."""
+    if blk_status == _lib.BLK_PANIC:
+        return SnapshotPanic(f"mustReadBytes: ErrUnexpectedBytesRead in segment {seg_id}")
+    kind = "EOF" if blk_status == _lib.BLK_EOF else "ErrUnexpectedBytesRead"
+    return SnapshotError(kind, f"reading a block of segment {seg_id}")
 
 
 def _getrow_less(x, y):  # :103-110
