@@ -645,6 +645,82 @@ typedef struct okv_merge_out {
 int okv_merge_rows(okv_ctx *ctx, const okv_merge_src *srcs, uint32_t nsrc,
                    const okv_merge_opts *opts, okv_merge_out *out, uint32_t flags);
 
+/* ======================================================================== *
+ * Range reads from resident segments: the two device steps either side of
+ * okv_merge_rows when Reader.GetRange is served from segments that stay on the
+ * device.  okv_seek_rows positions the streams (RowIter.Seek and the first Next,
+ * segment_row_iter.go:102-207), okv_gather_rows packs the rows the merge picked.
+ * DESIGN.md 23.
+ * ======================================================================== */
+
+/* A resident segment as the seek reads it: the decoded rows' keys (offsets into
+ * key_arena; for an index-only decode that is the segment itself) and the first row
+ * of every block, the decode's row_start.  Device pointers; the rows ascend by key
+ * and block_first_row has n_blocks + 1 entries, the last one n_rows. */
+typedef struct okv_seek_src {
+  const uint8_t *key_arena;
+  const uint64_t *key_off;
+  const uint16_t *key_len;
+  const uint64_t *block_first_row;
+  uint64_t n_rows;
+  uint64_t n_blocks;
+} okv_seek_src;
+
+/*
+ * For triple i = (src_of[i], key i of `keys`, direction[i]): the rows
+ * [row_lo[i], row_hi[i]) that RowIter(direction).Seek(key) followed by Next() to the
+ * end yields, in ascending row numbers (a descending stream is consumed from
+ * row_hi - 1): the okv_merge_src range.  An empty key is UnboundStart, the key 0xff
+ * UnboundEnd.  Ascending: from the first row >= key to the end (UnboundEnd: nothing).
+ * Descending: the walk starts at the last row of the last block whose FirstKey <= key
+ * -- of the block before it when that FirstKey equals the key and it is not block 0
+ * (DescendLessOrEqual keeps walking, :113-116), which skips that row -- and yields the
+ * rows <= key from there down; UnboundStart and a key below every block yield nothing.
+ * srcs is a host array (at most 65535 sources); of `keys` only key_arena, key_off,
+ * key_len, n_rows and key_arena_bytes are read; fewer than 2^32 triples; n_rows == 0
+ * succeeds and launches nothing.  src_of[i] >= nsrc: OKV_E_ARG in host mode, an empty
+ * range with OKV_F_DEVICE_PTRS.
+ * flags: without OKV_F_DEVICE_PTRS the key arrays, src_of, direction, row_lo and row_hi
+ * are host memory (staged; the call synchronises); with it they are device memory and,
+ * with OKV_F_ASYNC, the call only enqueues.
+ */
+int okv_seek_rows(okv_ctx *ctx, const okv_seek_src *srcs, uint32_t nsrc, const okv_rows *keys,
+                  const uint32_t *src_of, const uint8_t *direction, uint64_t *row_lo,
+                  uint64_t *row_hi, uint32_t flags);
+
+typedef struct okv_gather_out {
+  uint64_t *key_pos;  /* [n] offset of the key in key_arena, 16-byte aligned */
+  uint16_t *key_len;  /* [n] */
+  uint64_t *val_pos;  /* [n] offset of the value in val_arena, 16-byte aligned */
+  uint32_t *val_len;  /* [n] 0 <=> Go nil */
+  uint8_t *key_arena; /* or NULL (sizes only); every key zero-padded to 16 bytes; a device
+                         arena must be 16-byte aligned */
+  uint8_t *val_arena; /* likewise */
+  uint64_t key_cap;
+  uint64_t val_cap;
+  /* filled on return (also with OKV_E_CAPACITY, then neither arena is written): */
+  uint64_t key_bytes;
+  uint64_t val_bytes;
+} okv_gather_out;
+
+/*
+ * Rows (src[i], row[i]), i < n -- what okv_merge_out.src / .row hold, so nothing goes
+ * to the host between merge and gather -- copied into packed arenas.  Of every
+ * okv_merge_src only the six array pointers are read (row_lo, row_hi and level are
+ * not); srcs is a host array of device pointers, at most 65535.  The arenas of a source
+ * must be 16-byte aligned; the copy reads the aligned 16-byte lines that hold a byte of
+ * the key or value, nothing else.  src and row are device memory always (src[i] >= nsrc
+ * gives an empty row).  flags: without OKV_F_DEVICE_PTRS the outputs are host memory
+ * (staged; the call synchronises); with it they are device memory; OKV_F_ASYNC is not
+ * taken (the totals come back with the call).  n == 0 succeeds and launches nothing.
+ * Returns OKV_OK, OKV_E_CAPACITY (an arena was given and key_bytes > key_cap or
+ * val_bytes > val_cap: the totals and the four per-row arrays are set, the arenas are
+ * not written; a call with both arenas NULL is the size query and returns OKV_OK), or
+ * an error.  Fewer than 2^32 rows.
+ */
+int okv_gather_rows(okv_ctx *ctx, const okv_merge_src *srcs, uint32_t nsrc, const uint32_t *src,
+                    const uint64_t *row, uint64_t n, okv_gather_out *out, uint32_t flags);
+
 /* Per-kernel timing with HIP events recorded on the context stream around
  * each stage of okv_decode_blocks.  okv_profile(ctx, 1) enables and resets;
  * okv_profile_read synchronises the stream and returns the summed

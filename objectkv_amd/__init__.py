@@ -11,9 +11,10 @@ from .sst import (Decoded, Decoder, Encoded, Encoder, GpuSegmentWriter, Metadata
 from .bloom import DeviceBloom  # noqa: F401
 from .get import DeviceIndex, get_rows  # noqa: F401
 from .snap import DeviceSnapshot, snap_get_rows  # noqa: F401
+from .range import gather_rows, seek_rows  # noqa: F401
 
 __all__ = ["build", "lib", "Decoder", "Decoded", "DeviceBloom", "DeviceIndex", "get_rows",
-           "DeviceSnapshot", "snap_get_rows",
+           "DeviceSnapshot", "snap_get_rows", "seek_rows", "gather_rows",
            "Encoder", "Encoded",
            "GpuSegmentWriter",
            "Metadata", "OkvError", "SegmentWriter", "pack_rows",

@@ -69,6 +69,7 @@ SYMBOLS = [
     "okv_bloom_write_to", "okv_bloom_last_path",
     "okv_index_new", "okv_index_free", "okv_index_info", "okv_get_rows", "okv_get_totals",
     "okv_snap_new", "okv_snap_free", "okv_snap_get_rows", "okv_snap_totals",
+    "okv_seek_rows", "okv_gather_rows",
     "okv_writer_new", "okv_writer_write_row", "okv_writer_close", "okv_writer_data",
     "okv_writer_meta", "okv_writer_num_blocks", "okv_writer_block", "okv_writer_free",
     "okv_writer_set_bloom",
@@ -172,6 +173,21 @@ class MergeSrc(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class SeekSrc(C.Structure):
+    """okv_seek_src (include/okv_sst.h)."""
+    _fields_ = [("key_arena", C.c_void_p), ("key_off", C.c_void_p), ("key_len", C.c_void_p),
+                ("block_first_row", C.c_void_p), ("n_rows", C.c_uint64),
+                ("n_blocks", C.c_uint64)]
+
+
+class GatherOut(C.Structure):
+    """okv_gather_out (include/okv_sst.h)."""
+    _fields_ = [("key_pos", C.c_void_p), ("key_len", C.c_void_p), ("val_pos", C.c_void_p),
+                ("val_len", C.c_void_p), ("key_arena", C.c_void_p), ("val_arena", C.c_void_p),
+                ("key_cap", C.c_uint64), ("val_cap", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("val_bytes", C.c_uint64)]
+
+
 class MergeOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("direction", C.c_int), ("drop_tombstones", C.c_int),
                 ("pad", C.c_int), ("limit", C.c_uint64), ("bound", C.c_void_p),
@@ -269,6 +285,9 @@ def lib():
         "okv_snap_free": (None, [p]),
         "okv_snap_get_rows": (i32, [p, p, C.POINTER(Rows), C.POINTER(SnapOut), u32]),
         "okv_snap_totals": (i32, [p, C.POINTER(SnapOut)]),
+        "okv_seek_rows": (i32, [p, C.POINTER(SeekSrc), u32, C.POINTER(Rows), p, p, p, p, u32]),
+        "okv_gather_rows": (i32, [p, C.POINTER(MergeSrc), u32, p, p, u64,
+                                  C.POINTER(GatherOut), u32]),
         "okv_writer_new": (p, [u64, u64, i32, i32]),
         "okv_writer_write_row": (i32, [p, p, C.c_size_t, p, C.c_size_t]),
         "okv_writer_close": (i32, [p, i32, C.POINTER(u64), C.POINTER(u64)]),

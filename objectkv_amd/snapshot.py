@@ -7,7 +7,10 @@ call (okv_snap_get_rows, objectkv_amd/snap.py) over the segments' raw bytes.  Th
 quirky descend-and-stop search, :149-193) and the per-segment Seek positions
 are host control logic, restated statement by statement; every block read is
 the batched GPU decode and every GetRange merge is okv_merge_rows
-(objectkv_amd/csrc/okv_merge.hip).  There is no CPU merge path.
+(objectkv_amd/csrc/okv_merge.hip).  There is no CPU merge path.  GetRanges is GetRange
+for a batch of queries served from the resident segments (objectkv_amd/range.py): the seek
+on the device, the merge over windows of limit + slack rows (cut_windows / accept_window),
+the result rows gathered on the device.
 
 Segments must be written in key order (the Go writer's stated precondition,
 segment_writer.go:78): the merge reads each segment as one sorted row array.
@@ -25,6 +28,9 @@ from . import _lib
 from .sst import COMP_NONE, Decoder, Encoder, OkvError, fetch_metadata
 
 DirectionAscending, DirectionDescending = 0, 1  # segment_row_iter.go:22-25
+_RANGE_STATS = ("seeks", "seek_calls", "gather_calls", "rows_merged", "windows_accepted",
+                "reruns", "rows_gathered")
+_GATHER_SOURCES = 60000  # streams of one okv_gather_rows call (it takes 65535 sources)
 UnboundStart = None  # segment_reader.go:60
 UnboundEnd = b"\xff"  # :62
 
@@ -178,6 +184,57 @@ class DeviceSegment:
         raise SnapshotError("ErrNoRows")
 
 
+# ---- windows: what a GetRange merge has to look at -------------------------------------
+
+
+def window_size(limit: int) -> int:
+    """Rows of each stream a merge for `limit` rows looks at: limit + 1 and a slack that
+    lets a page with a few tombstones or duplicate keys still be accepted."""
+    return limit + 1 + max(16, limit // 4)
+
+
+def cut_windows(streams, c, direction):
+    """streams [(lo, hi)] cut to at most c rows from the end the iteration starts at:
+    ascending [lo, min(hi, lo + c)), descending [max(lo, hi - c), hi).
+    -> (windows, frontier): frontier[i] is the row of a truncated stream i that lies
+    furthest into the iteration (its last window row), None when the stream was not cut."""
+    windows, frontier = [], []
+    for lo, hi in streams:
+        if direction == DirectionAscending:
+            w = (lo, min(hi, lo + c))
+            frontier.append(w[1] - 1 if w[1] < hi else None)
+        else:
+            w = (max(lo, hi - c), hi)
+            frontier.append(w[0] if w[0] > lo else None)
+        windows.append(w)
+    return windows, frontier
+
+
+def accept_window(frontier_keys, eof, n_rows, limit, last_key, bound, direction) -> bool:
+    """Whether the GetRange loop over the windows gave what it gives over the full streams.
+    frontier_keys: the keys of cut_windows' frontier rows (truncated streams only); eof: the
+    merge ended in io.EOF (OKV_M_EOF); n_rows, last_key: the rows it returned and the last
+    one's key; bound: `end` ascending, `start` descending.
+
+    Let F be the frontier key the iteration reaches first.  Every event of the loop at a
+    key strictly before F sees the same rows and the same successors as in the full
+    streams; a truncated stream can only look run-out at F or beyond.  So the result
+    stands when the loop ended before F (the limit-th row lies strictly before F), or when
+    F is at or past the bound: past the bound the loop only skips L0 tombstones or breaks,
+    and a spurious run-out there happens on a skip and yields io.EOF, which is rejected."""
+    if not frontier_keys:
+        return True
+    if eof:
+        return False
+    asc = direction == DirectionAscending
+    f = min(frontier_keys) if asc else max(frontier_keys)
+    if (_cmp(f, bound) >= 0) if asc else (_cmp(f, bound) <= 0):
+        return True
+    if n_rows < limit:
+        return False
+    return (_cmp(last_key, f) < 0) if asc else (_cmp(last_key, f) > 0)
+
+
 # ---- the snapshot reader --------------------------------------------------------------
 
 
@@ -248,6 +305,12 @@ class Reader:
         self.decoder = decoder or Decoder(0)
         self._segs: dict[str, DeviceSegment] = {}
         self._raw: dict[str, tuple] = {}  # GetRows: raw bytes, block index and filter by ID
+        self._bytes: dict[str, tuple] = {}  # the raw bytes on the device and the metadata by ID
+        self._rows: dict = {}             # GetRanges: range.ResidentRows by ID
+        self._garena = None               # GetRanges: the gather's device arenas (key, value)
+        self.range_stats = dict.fromkeys(_RANGE_STATS, 0)
+        self.range_profile = False        # GetRanges: also time seek / merges / gather (events)
+        self._pstream = None
         self._snap = None                 # GetRows: the DeviceSnapshot of the current set
 
     def _seg(self, rec) -> DeviceSegment:
@@ -262,14 +325,16 @@ class Reader:
             if not self.segmentIDTree.delete(d):
                 continue
             self.blockRangeTree.delete(d)
-            self._segs.pop(d.ID, None)
-            self._raw.pop(d.ID, None)
+            self._drop(d.ID)
         for a in add or []:
             self.segmentIDTree.replace_or_insert(a)
             self.blockRangeTree.replace_or_insert(a)
-            self._segs.pop(a.ID, None)
-            self._raw.pop(a.ID, None)
+            self._drop(a.ID)
         self._snap = None
+
+    def _drop(self, ID):
+        for cache in (self._segs, self._raw, self._bytes, self._rows):
+            cache.pop(ID, None)
 
     def _possible_for_key(self, key):  # :149-170
         out = []
@@ -310,9 +375,21 @@ class Reader:
         per segment ID -> DeviceSnapshot's segment tuple."""
         s = self._raw.get(rec.ID)
         if s is None:
-            import torch
             from .bloom import DeviceBloom
             from .get import DeviceIndex
+            t, size, md, bb = self._raw_bytes(rec)
+            bloom = DeviceBloom.from_bytes(self.decoder, bb) if bb is not None else None
+            s = self._raw[rec.ID] = (t, size, DeviceIndex.from_metadata(self.decoder, md),
+                                     bloom, md.compression)
+        return s + (rec.Level, rec.ID, rec.FirstKey, rec.LastKey)
+
+    def _raw_bytes(self, rec):
+        """The segment's bytes on the device (32 spare bytes after them: the kernels read
+        aligned 16-byte lines), uploaded once per segment ID -> (device tensor, byte count,
+        metadata, filter bytes or None).  No host copy of the segment is kept."""
+        s = self._bytes.get(rec.ID)
+        if s is None:
+            import torch
             data, n = self.readerFactory(rec)
             raw = np.frombuffer(bytes(data), np.uint8)
             md = fetch_metadata(raw, n)
@@ -320,11 +397,26 @@ class Reader:
                             device=torch.device("cuda", self.decoder.device))
             if raw.size:
                 t[:raw.size] = torch.from_numpy(raw.copy())
-            bb = _bloom_bytes(raw, n)
-            bloom = DeviceBloom.from_bytes(self.decoder, bb) if bb is not None else None
-            s = self._raw[rec.ID] = (t, raw.size, DeviceIndex.from_metadata(self.decoder, md),
-                                     bloom, md.compression)
-        return s + (rec.Level, rec.ID, rec.FirstKey, rec.LastKey)
+            s = self._bytes[rec.ID] = (t, raw.size, md, _bloom_bytes(raw, n))
+        return s
+
+    def _resident(self, rec):
+        """The segment's rows on the device (range.ResidentRows), decoded once per segment
+        ID.  A block that fails to decode and first keys that do not ascend raise what
+        DeviceSegment raises."""
+        r = self._rows.get(rec.ID)
+        if r is None:
+            from .range import ResidentRows
+            t, size, md, _bb = self._raw_bytes(rec)
+            r = ResidentRows(self.decoder, t, size, md)
+            if r.status.size and int(np.abs(r.status).max()) != 0:
+                raise OkvError(-309, f"segment blocks failed to decode: {np.unique(r.status)}")
+            for a, b in zip(md.first_keys, md.first_keys[1:]):
+                if _cmp(a, b) >= 0:
+                    raise NotImplementedError(
+                        "segment not written in key order (segment_writer.go:78)")
+            self._rows[rec.ID] = r
+        return r
 
     def _device_snapshot(self):
         """The DeviceSnapshot of blockRangeTree, rebuilt when the segment set changed; None
@@ -418,8 +510,218 @@ class Reader:
         row = out["row"][:n].cpu().numpy()
         return [KVPair(dsegs[s].key(int(r)), dsegs[s].value(int(r))) for s, r in zip(src, row)]
 
-    def RowIter(self, start, direction, bufferSize=100):  # :430-443
-        return Iter(self, start, direction, bufferSize)
+    # -- GetRange for a batch of queries, from the resident segments ------------------
+
+    def GetRanges(self, queries):
+        """GetRange for every (start, end, limit, direction) of queries: per query the list
+        of KVPair, None (no candidate segment), or the SnapshotError / SnapshotPanic Go's
+        GetRange would give (returned, not raised).  One okv_seek_rows call positions every
+        (query, candidate) stream; each query's merge (okv_merge_rows) runs over windows
+        of window_size(limit) rows and is run again over the whole streams only when
+        accept_window refuses its result; one okv_gather_rows packs the rows of the whole
+        batch on the device and they come back once per batch (the row arrays, the key arena,
+        the value arena), not per row.  More than 64 candidates of one query is the merge's
+        OKV_E_ARG, as in GetRange.  range_stats counts the call:
+        seeks (triples), seek_calls, gather_calls, rows_merged (rows given to merges),
+        windows_accepted (queries with a cut stream whose windowed result stood), reruns,
+        rows_gathered.  With range_profile set it also holds seek_ms, merge_ms and gather_ms:
+        device events on the decoder's stream around the three steps."""
+        from . import range as RG
+        st = self.range_stats = dict.fromkeys(_RANGE_STATS, 0)
+        if self.range_profile:
+            st.update(seek_ms=0.0, merge_ms=0.0, gather_ms=0.0)
+        results = [None] * len(queries)
+        plans, sources, src_at = [], [], {}
+        keys, src_of, dirs = [], [], []
+        for qi, (start, end, limit, direction) in enumerate(queries):
+            if _cmp(start, end) >= 0:
+                results[qi] = SnapshotError("ErrInvalidRange",
+                                            "end must be strictly greater than start")
+                continue
+            segs = self._possible_for_range(start, end)
+            if not segs:
+                continue
+            segs.sort(key=functools.cmp_to_key(
+                lambda a, b: -1 if _getrange_less(a, b, direction) else
+                (1 if _getrange_less(b, a, direction) else 0)))
+            start_range = end if direction == DirectionDescending else start
+            for rec in segs:
+                if rec.ID not in src_at:
+                    src_at[rec.ID] = len(sources)
+                    sources.append(self._resident(rec))
+                keys.append(_b(start_range))
+                src_of.append(src_at[rec.ID])
+                dirs.append(direction)
+            plans.append((qi, segs, len(keys) - len(segs)))
+        if not plans:
+            return results
+        t0 = self._mark()
+        lo, hi = RG.seek_rows(self.decoder, sources, keys, src_of, dirs)
+        self._span("seek_ms", t0)
+        st["seeks"], st["seek_calls"] = len(keys), 1
+
+        jobs = []  # per query still to merge: its streams, windows and frontier rows
+        for qi, segs, at in plans:
+            limit, direction = queries[qi][2], queries[qi][3]
+            streams = [(int(lo[at + j]), int(hi[at + j])) for j in range(len(segs))]
+            empty = [rec for rec, (a, b) in zip(segs, streams) if b <= a]
+            if empty:  # RowIter.Next after Seek returns io.EOF (:276-280)
+                results[qi] = SnapshotError("EOF", f"error in sst.RowIter.Next() after start "
+                                                   f"range for segment {empty[0].ID}")
+                continue
+            if limit < 0:
+                results[qi] = SnapshotPanic("makeslice: len out of range")
+                continue
+            lim = limit if limit > 0 else 1  # limit 0 panics only once a row is appended
+            windows, frontier = cut_windows(streams, window_size(lim), direction)
+            jobs.append({"qi": qi, "segs": segs, "src": src_of[at:at + len(segs)], "lim": lim,
+                         "streams": streams, "windows": windows, "frontier": frontier})
+        self._merge_jobs(jobs, sources, queries, results, windowed=True)
+        again = [j for j in jobs if j.get("rerun")]
+        st["reruns"] = len(again)
+        self._merge_jobs(again, sources, queries, results, windowed=False)
+        return results
+
+    def _merge_jobs(self, jobs, sources, queries, results, windowed):
+        """_merge_group over groups of jobs whose streams fit one gather's source list."""
+        group, streams = [], 0
+        for j in jobs:
+            if group and streams + len(j["src"]) > _GATHER_SOURCES:
+                self._merge_group(group, sources, queries, results, windowed)
+                group, streams = [], 0
+            group.append(j)
+            streams += len(j["src"])
+        if group:
+            self._merge_group(group, sources, queries, results, windowed)
+
+    def _merge_group(self, jobs, sources, queries, results, windowed):
+        """One merge per job into slices of one device src / row array, then one gather
+        and one copy back.  The gather's sources are the jobs' streams one after the other,
+        so a merge's stream numbers need only the job's base added.  windowed: over the
+        jobs' windows, with the frontier rows added to the gather list; a refused result
+        marks the job for the rerun."""
+        import torch
+        st = self.range_stats
+        dev = torch.device("cuda", self.decoder.device)
+        extra, gsrc = [], []  # the frontier rows, in front of the merges' rows
+        for j in jobs:
+            j["ranges"] = j["windows"] if windowed else j["streams"]
+            j["base"], j["fr_at"] = len(gsrc), len(extra)
+            gsrc += [sources[s] for s in j["src"]]
+            if windowed:
+                extra += [(j["base"] + i, r) for i, r in enumerate(j["frontier"]) if r is not None]
+            j["cap"] = min(sum(b - a for a, b in j["ranges"]), j["lim"])
+        ne = len(extra)
+        total = ne + sum(j["cap"] for j in jobs)
+        d_src = torch.full((max(total, 1),), -1, dtype=torch.int32, device=dev)
+        d_row = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
+        if ne:  # one upload
+            up = torch.tensor([e[0] for e in extra] + [e[1] for e in extra],
+                              dtype=torch.int64).to(dev)
+            d_src[:ne] = up[:ne].to(torch.int32)
+            d_row[:ne] = up[ne:]
+        # torch filled the arrays on its stream; the decoder's kernels run on another
+        torch.cuda.current_stream(dev).synchronize()
+        pos = ne
+        t0 = self._mark()
+        for j in jobs:
+            start, end, _l, direction = queries[j["qi"]]
+            bound = _b(end if direction == DirectionAscending else start)
+            srcs = [(sources[s].t, a, b, rec.Level)
+                    for s, rec, (a, b) in zip(j["src"], j["segs"], j["ranges"])]
+            st["rows_merged"] += sum(b - a for a, b in j["ranges"])
+            out = {"src": d_src[pos:pos + j["cap"]], "row": d_row[pos:pos + j["cap"]]}
+            mo = self.decoder.merge_device(srcs, _lib.MERGE_GETRANGE, direction, j["lim"], bound,
+                                           out=out, row_cap=j["cap"])
+            j["eof"] = mo.status == _lib.M_EOF
+            j["n"] = 0 if j["eof"] else int(mo.n_rows)
+            j["at"] = pos
+            if j["n"] and j["base"]:  # the merge counts its inputs from 0
+                d_src[pos:pos + j["n"]] += j["base"]
+            pos += j["n"]
+        torch.cuda.current_stream(dev).synchronize()
+        t1 = self._span("merge_ms", t0)
+        g = self._gather(gsrc, d_src, d_row, pos)
+        self._span("gather_ms", t1)
+        st["gather_calls"] += 1
+        st["rows_gathered"] += pos
+        for j in jobs:
+            qi = j["qi"]
+            direction, limit = queries[qi][3], queries[qi][2]
+            bound = _b(queries[qi][1] if direction == DirectionAscending else queries[qi][0])
+            if windowed:
+                nf = sum(r is not None for r in j["frontier"])
+                fkeys = [g.key(j["fr_at"] + i) for i in range(nf)]
+                last = g.key(j["at"] + j["n"] - 1) if j["n"] else None
+                if not accept_window(fkeys, j["eof"], j["n"], j["lim"], last, bound, direction):
+                    j["rerun"] = True
+                    continue
+                st["windows_accepted"] += bool(fkeys)
+            if j["eof"]:
+                results[qi] = SnapshotError("EOF", "error in sst.RowIter.Next() rolling forward")
+            elif limit == 0 and j["n"]:
+                results[qi] = SnapshotPanic("index out of range [0] with length 0")
+            else:
+                results[qi] = [KVPair(k, v) for k, v in g.pairs(j["at"], j["at"] + j["n"])]
+
+    def _mark(self):
+        """range_profile: an event recorded on the decoder's stream now, else None."""
+        if not self.range_profile:
+            return None
+        import torch
+        if self._pstream is None:
+            self._pstream = torch.cuda.ExternalStream(self.decoder.stream)
+        e = torch.cuda.Event(enable_timing=True)
+        e.record(self._pstream)
+        return e
+
+    def _span(self, name, since):
+        """range_profile: add the device time since the event to range_stats[name]."""
+        e = self._mark()
+        if e is not None:
+            e.synchronize()
+            self.range_stats[name] += since.elapsed_time(e)
+        return e
+
+    def _gather(self, sources, d_src, d_row, n):
+        """okv_gather_rows of rows (d_src, d_row)[:n] into the reader's device arenas (grown
+        when the call reports OKV_E_CAPACITY), copied back -> range.GatherResult on the host.
+        The four per-row arrays are one device buffer: one copy brings them back."""
+        import torch
+        from . import range as RG
+        dev = d_src.device
+        m = max(n, 1)
+        buf = torch.empty(24 * m, dtype=torch.uint8, device=dev)
+        out = {"key_pos": buf[:8 * m].view(torch.int64), "val_pos": buf[8 * m:16 * m].view(torch.int64),
+               "val_len": buf[16 * m:20 * m].view(torch.int32),
+               "key_len": buf[20 * m:22 * m].view(torch.int16)}
+        srcs = RG.merge_srcs(sources)
+        if self._garena is None:
+            self._garena = (torch.empty(1 << 16, dtype=torch.uint8, device=dev),
+                            torch.empty(1 << 20, dtype=torch.uint8, device=dev))
+        for _attempt in range(2):
+            out["key_arena"], out["val_arena"] = self._garena
+            try:
+                g = RG.gather_rows(self.decoder, srcs, d_src, d_row, n, out=out)
+                break
+            except OkvError as e:
+                if e.code != _lib.OKV_E_CAPACITY or _attempt:
+                    raise
+                need = e.result
+                self._garena = (
+                    torch.empty(max(need.key_bytes * 3 // 2, 1 << 16), dtype=torch.uint8, device=dev),
+                    torch.empty(max(need.val_bytes * 3 // 2, 1 << 20), dtype=torch.uint8, device=dev))
+        h = buf.cpu().numpy()
+        host = {"key_pos": h[:8 * m].view(np.uint64)[:n], "val_pos": h[8 * m:16 * m].view(np.uint64)[:n],
+                "val_len": h[16 * m:20 * m].view(np.uint32)[:n],
+                "key_len": h[20 * m:22 * m].view(np.uint16)[:n]}
+        return RG.GatherResult(host, out["key_arena"][:g.key_bytes].cpu().numpy(),
+                               out["val_arena"][:g.val_bytes].cpu().numpy(), g)
+
+    def RowIter(self, start, direction, bufferSize=100, resident=False):  # :430-443
+        """resident: the Iter pages through GetRanges (the resident segments) instead of
+        GetRange."""
+        return Iter(self, start, direction, bufferSize, resident)
 
 
 def _bloom_bytes(raw, file_len):
@@ -464,9 +766,10 @@ def _getrange_less(x, y, direction):  # :235-254
 class Iter:
     """snapshot_iter.go:11-116: pages through GetRange."""
 
-    def __init__(self, reader, start, direction, bufferSize):
+    def __init__(self, reader, start, direction, bufferSize, resident=False):
         self.reader, self.lastKey, self.direction = reader, start, direction
         self.bufferSize, self.rowBuffer, self.done = bufferSize, [], False
+        self.resident = resident
 
     def Next(self):  # :37-47
         self._check_load()
@@ -485,7 +788,12 @@ class Iter:
             s, e = UnboundStart, self.lastKey
         else:
             s, e = self.lastKey, UnboundEnd
-        rows = self.reader.GetRange(s, e, self.bufferSize, self.direction)
+        if self.resident:
+            rows = self.reader.GetRanges([(s, e, self.bufferSize, self.direction)])[0]
+            if isinstance(rows, Exception):
+                raise rows
+        else:
+            rows = self.reader.GetRange(s, e, self.bufferSize, self.direction)
         if not rows:
             self.done = True
             raise SnapshotError("EOF")
