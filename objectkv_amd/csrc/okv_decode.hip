@@ -355,16 +355,6 @@ struct CopyParams {
   uint64_t span_cap;          // okv_tile_kernel: blocks whose walk ends past it are big
 };
 
-// The value sweep runs when every row's index is written by the per-block
-// pass 3 and the value arena is gap-free: no big block (okv_copy_kernel's
-// rows) and no capacity failure.  Every workgroup of both kernels reads the
-// same scalars, so they agree.
-constexpr uint32_t kSwTile = 4096;  // value-arena bytes per sweep tile
-__device__ __forceinline__ bool sweep_safe(const Totals& T, uint32_t nbig, uint64_t row_cap,
-                                           uint64_t key_cap, uint64_t val_cap) {
-  return nbig == 0 && T.rows <= row_cap && T.kb <= key_cap && T.vb <= val_cap;
-}
-
 // Global row / arena bases of block b and its final status (capacity check).
 struct BlockBase {
   uint64_t row0, kb0, vb0;
@@ -572,45 +562,6 @@ __device__ __forceinline__ void write_row_index(const CopyParams& P, const Gathe
   }
 }
 
-// Value-sweep hand-off (lane r = row r): each row's value source, the row
-// owning each value-arena tile that starts inside its value, and the row's
-// boundary chunk.  A 16-byte chunk holding the end of row r's value (end not
-// 16-aligned) mixes rows (or the block's zero padding); the lane of the row
-// owning its first byte assembles it from the block's row table into
-// bchunk[row], and the sweep stores it with its tile (whole lines).  The
-// loads are issued first (with the key loads in flight: see okv_rows_kernel).
-__device__ __forceinline__ uint4 boundary_chunk(const CopyParams& P, const GatherSmem& sm,
-                                                const BlockMeta& m, int rows) {
-  const uint32_t t = threadIdx.x;
-  uint4 out = make_uint4(0, 0, 0, 0);
-  if (int(t) >= rows) return out;
-  const uint32_t v0 = sm.vpre[t], e = sm.vpre[t + 1];
-  const uint32_t C = e & ~15u;
-  if (e == v0 || (e & 15) == 0 || v0 > C) return out;  // no chunk of mine to assemble
-  out = merge_bytes(out, window16(P.seg, P.seg_bytes, int64_t(m.off + sm.vsb[t] + C)), 0,
-                    int32_t(e - C));
-  for (uint32_t j = t + 1; int(j) < rows && sm.vpre[j] < C + 16; ++j) {
-    const uint32_t q0 = sm.vpre[j], q1 = sm.vpre[j + 1];
-    if (q1 == q0) continue;
-    const uint4 w = window16(P.seg, P.seg_bytes, int64_t(m.off + sm.vsb[j] + C));
-    out = merge_bytes(out, w, int32_t(q0 - C), int32_t(min(q1, C + 16) - C));
-  }
-  return out;
-}
-__device__ __forceinline__ void sweep_handoff(const CopyParams& P, const GatherSmem& sm,
-                                              const BlockMeta& m, int rows, const uint4& bc) {
-  const uint32_t t = threadIdx.x;
-  if (int(t) >= rows) return;
-  const uint64_t g = m.B.row0 + t;
-  const uint32_t kl = sm.kpre[t + 1] - sm.kpre[t];
-  const uint32_t v0 = sm.vpre[t], e = sm.vpre[t + 1];
-  P.vsrc[g] = m.off + sm.rec[t] + 6 + kl;
-  P.bchunk[g] = bc;
-  for (uint64_t x = (m.B.vb0 + v0 + kSwTile - 1) & ~uint64_t(kSwTile - 1); x < m.B.vb0 + e;
-       x += kSwTile)
-    P.vtile[x / kSwTile] = uint32_t(g);
-}
-
 // ---------------------------------------------------------------------------
 // Pass 3, source tiles (large blocks).  Block b is cut into
 // tiles of kT source bytes, tile t = block bytes [t kT, (t + 1) kT), one
@@ -678,52 +629,49 @@ __device__ __forceinline__ uint4 funnel_u(const uint4& x, const uint4& y, uint32
   }
 }
 
-// A destination chunk of a tile whose owned bytes [lo, hi) span rows or
-// padding: each row's piece from a global window (rare; kept out of line).
-__device__ __noinline__ uint4 tile_chunk_pieces(const uint8_t* seg, uint64_t seg_bytes, uint64_t off,
-                                                const uint32_t* pre, const uint32_t* sb,
-                                                uint32_t rows, uint32_t r, uint32_t x,
-                                                uint32_t lo, uint32_t hi) {
-  const uint32_t dend = min(hi, pre[rows]);
-  uint4 out = make_uint4(0, 0, 0, 0);
-  for (uint32_t d = lo; d < dend; ++r) {
-    const uint32_t e = min(dend, pre[r + 1]);
-    if (e > d) {  // bytes [d, e) of the chunk from row r
-      out = merge_bytes(out, window16(seg, seg_bytes, int64_t(off + sb[r] + x)), int32_t(d - x),
-                        int32_t(e - x));
-      d = e;
-    }
-  }
-  return out;
+// The tile pass is a sequence of phases (tile_pass, below), each a function
+// of small plain structs.  (The measured alternatives -- other cuts, phase
+// probes, per-chunk lookups, direct global loads, omitted output classes --
+// are compositions of these phases in okv_decode_ablate.inc, ablation build
+// only.)
+constexpr uint32_t kLineExt = 512;  // source bytes a tile stages past its end (the line cut's reach)
+struct TileBlock {  // the tile's block: uniform (SGPRs)
+  uint32_t b, t;    // block, tile of the block
+  uint64_t off, row0, kb0, vb0;
+  int32_t st;
+  uint64_t rows, pend;
+};
+struct TileExtent {  // the tile: source bytes [P0, P1) of the block, stage lines [A, A + 16 np)
+  uint32_t rows, lastr, P0, P1;
+  bool last_tile;
+  int64_t A;
+  uint32_t np;
+};
+struct TileLane {  // wave 0, lane r = row r: lengths, exclusive prefixes, block positions
+  uint32_t k, v, kp, vp, ks, vs;
+  bool live;
+};
+struct TileCuts {  // owned key range [x0, x1), value range [x2, x3) (region bytes)
+  uint32_t x[4], KT, VT, jv;  // region totals; jv: the row holding x2
+};
+struct TileOwned {  // what every wave reads back from the LDS tables
+  uint32_t kx0, kx1, vx0, vx1, nunit, nbnd;
+};
+
+template <bool kXcd>
+__device__ __forceinline__ uint32_t tile_index() {
+  if constexpr (kXcd) return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  return blockIdx.x;
 }
 
-// (The measured alternatives -- other tile sizes and widths, phase probes,
-// per-chunk lookups, direct global loads -- are tile_pass_diag in
-// okv_decode_ablate.inc, ablation build only.)
-// kSkip (ablation build only, okv_tile_kernel_skip): output classes left
-// unwritten, to attribute the pass's HBM write traffic -- 1 the SoA row index,
-// 2 value runs, 4 key chunks, 8 boundary value chunks, 16 partial chunks;
-// forms: 64 the round-5 cuts (no line cut, below); 128 whole 64-byte sectors
-// per store (+ 256 key cuts unrounded, + 512 the stage extension).
-template <uint32_t kT, uint32_t kNT, bool kXcd, uint32_t kSkip = 0>
-__device__ __forceinline__ void tile_pass(const CopyParams& P, uint32_t tpb, uint32_t ntile) {
-  constexpr uint32_t kG = kT / 64 + 8;  // 64-byte destination granules of the key range
-  constexpr bool kSector = (kSkip & 128) != 0;       // whole 64-byte sectors per store
-  constexpr bool kLineCut = !(kSkip & 64) && !kSector;  // the product: value cuts on lines
-  constexpr bool kKeyRound = kSector && !(kSkip & 256);  // (256: key cuts left as they are)
-  constexpr uint32_t kLineExt = (kLineCut || (kSkip & 512)) ? 512 : 0;  // (512: stage extension)
-  __shared__ TileRows<kT> R;
-  __shared__ uint8_t gt[1][kG];         // row holding key byte max(64 g, range start)
-  __shared__ uint4 stage[(kT + kLineExt) / 16 + 4];
-  uint32_t L = blockIdx.x;
-  if constexpr (kXcd) L = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  if (L >= ntile) return;
+// The block's scalars, bases and status, and (wave 0) its record table: one trip.
+__device__ __forceinline__ TileBlock tile_block(const CopyParams& P, uint32_t L, uint32_t tpb,
+                                                uint32_t& rec, uint32_t& kl) {
   // uniform block index (an SGPR: the loads below are scalar, all in one trip)
   const uint32_t b = __builtin_amdgcn_readfirstlane(L / tpb);
   const uint32_t t = L - b * tpb;
   const uint32_t tid = threadIdx.x, lane = tid & 63;
-  // one trip: the block's scalars and (wave 0) its record table
-  uint32_t rec = 0, kl = 0;
+  rec = 0, kl = 0;
   if (tid < 64) {
     rec = P.rt_pos[rec_index(P.nblk, b, lane)];
     kl = P.rt_kl[rec_index(P.nblk, b, lane)];
@@ -741,368 +689,383 @@ __device__ __forceinline__ void tile_pass(const CopyParams& P, uint32_t tpb, uin
                     (P.index_only ||
                      (kb0 + round16(c.kbytes) <= P.key_cap && vb0 + round16(c.vbytes) <= P.val_cap));
   const int32_t st = (c.status == OKV_BLK_OK && !fits) ? int32_t(OKV_BLK_CAPACITY) : c.status;
-  // Tile 0 writes the block outputs and the SoA row index.  Stores wait
-  // until the LDS tables are built: the compiler makes wave 0's LDS writes
-  // wait for the wave's outstanding memory operations (it cannot tell them
-  // from the DMA's LDS target).
-  auto block_outputs = [&]() {
-    if (t == 0 && tid == 0) {
-      P.row_start[b] = row0;
-      if (P.key_base) P.key_base[b] = kb0;
-      if (P.val_base) P.val_base[b] = vb0;
-      P.blk_status[b] = st;
-    }
-  };
-  const uint64_t pend = c.pend;
-  const uint32_t P0 = t * kT;
-  // big blocks are okv_copy_kernel's (the same test as okv_count_kernel's)
-  if (st != OKV_BLK_OK || c.rows == 0 || c.rows > uint64_t(kRCap) || pend > P.span_cap ||
-      pend >= (uint64_t(1) << 32) || P0 >= pend) {
-    block_outputs();
-    return;
+  return {b, t, off, row0, kb0, vb0, st, c.rows, c.pend};
+}
+
+// Tile 0 writes the block outputs and the SoA row index.  Stores wait
+// until the LDS tables are built: the compiler makes wave 0's LDS writes
+// wait for the wave's outstanding memory operations (it cannot tell them
+// from the DMA's LDS target).
+__device__ __forceinline__ void block_outputs(const CopyParams& P, const TileBlock& B) {
+  if (B.t == 0 && threadIdx.x == 0) {
+    P.row_start[B.b] = B.row0;
+    if (P.key_base) P.key_base[B.b] = B.kb0;
+    if (P.val_base) P.val_base[B.b] = B.vb0;
+    P.blk_status[B.b] = B.st;
   }
-  const uint32_t rows = uint32_t(c.rows), lastr = rows - 1;
-  const uint32_t P1 = uint32_t(min<uint64_t>(uint64_t(P0) + kT, pend));
-  const bool last_tile = P1 == pend;
+}
+
+// The early outs: nothing for this tile to copy.
+template <uint32_t kT>
+__device__ __forceinline__ bool tile_idle(const CopyParams& P, const TileBlock& B) {
+  // big blocks are okv_copy_kernel's (the same test as okv_count_kernel's)
+  return B.st != OKV_BLK_OK || B.rows == 0 || B.rows > uint64_t(kRCap) || B.pend > P.span_cap ||
+         B.pend >= (uint64_t(1) << 32) || B.t * kT >= B.pend;
+}
+
+template <uint32_t kT>
+__device__ __forceinline__ TileExtent tile_extent(const TileBlock& B) {
+  const uint32_t rows = uint32_t(B.rows), P0 = B.t * kT;
+  const uint32_t P1 = uint32_t(min<uint64_t>(uint64_t(P0) + kT, B.pend));
+  const bool last_tile = P1 == B.pend;
   // stage = segment lines [A, E): the line before the one holding the tile's
   // first byte (a chunk's window begins up to 15 bytes before its first owned
-  // byte) through the line after the one holding its last byte + 15
-  const int64_t A = int64_t((off + P0) & ~uint64_t(15)) - 16;
-  const int64_t E = int64_t((off + P1 + 15) & ~uint64_t(15)) + 16 + (last_tile ? 0 : kLineExt);
-  const uint32_t np = uint32_t((E - A) >> 4);
-  // Waves 1.. issue the DMA; wave 0 builds the row table meanwhile.  (With a
-  // share of the DMA in flight, wave 0's LDS row-table writes would wait for
-  // it: the compiler cannot tell them apart from the DMA's LDS target.)
+  // byte) through the line after the one holding its last byte + 15, and the
+  // line cut's extension
+  const int64_t A = int64_t((B.off + P0) & ~uint64_t(15)) - 16;
+  const int64_t E = int64_t((B.off + P1 + 15) & ~uint64_t(15)) + 16 + (last_tile ? 0 : kLineExt);
+  return {rows, rows - 1, P0, P1, last_tile, A, uint32_t((E - A) >> 4)};
+}
+
+// Waves 1.. issue the DMA; wave 0 builds the row table meanwhile.  (With a
+// share of the DMA in flight, wave 0's LDS row-table writes would wait for
+// it: the compiler cannot tell them apart from the DMA's LDS target.)
+template <uint32_t kNT>
+__device__ __forceinline__ void tile_dma(const CopyParams& P, const TileBlock& B,
+                                         const TileExtent& X, uint4* stage) {
+  const uint32_t tid = threadIdx.x;
   if (!P.index_only && tid >= 64) {
     const int64_t lim = int64_t(round16(P.seg_bytes));
     const uint32_t u = tid - 64;
-    for (uint32_t k0 = 0; k0 < np; k0 += kNT - 64) {
+    for (uint32_t k0 = 0; k0 < X.np; k0 += kNT - 64) {
       const uint32_t i = k0 + u;
-      if (i < np) {
-        int64_t a = A + (int64_t(i) << 4);
-        if (a < 0 || a + 16 > lim) a = int64_t(off) & ~int64_t(15);  // bytes never used
+      if (i < X.np) {
+        int64_t a = X.A + (int64_t(i) << 4);
+        if (a < 0 || a + 16 > lim) a = int64_t(B.off) & ~int64_t(15);  // bytes never used
         __builtin_amdgcn_global_load_lds(P.seg + a, OKV_LDS_PTR(stage + k0 + (u & ~63u)), 16,
                                          0, 0);
       }
     }
   }
-  // row table (wave 0, lane r = row r) while the tile is in flight
-  if (tid < 64) {
-    const bool live = lane < rows;
-    uint32_t nxt = __builtin_amdgcn_update_dpp(0u, rec, 0x130, 0xf, 0xf, false);  // rec[lane + 1]
-    if (lane == lastr) nxt = uint32_t(pend);
-    const uint32_t k = live ? kl : 0u, v = live ? nxt - rec - 6 - kl : 0u;
-    const uint32_t ki = wave_scan_dpp(k), vi = wave_scan_dpp(v);
-    const uint32_t kp = ki - k, vp = vi - v;
-    const uint32_t ks = rec + 6, vs = rec + 6 + k;  // block positions of the key / value
-    if (live) {
-      R.pre[0][lane] = kp;
-      R.pre[1][lane] = vp;
-      R.sb[0][lane] = ks - kp;
-      R.sb[1][lane] = vs - vp;
-      if (lane == lastr) {
-        R.pre[0][rows] = ki;
-        R.pre[1][rows] = vi;
-      }
-    }
-    if (!P.index_only) {
-      // the owned ranges: [first byte whose source is >= P0, same for P1); the
-      // last tile also owns the 16-byte padding after the region
-      const uint32_t KT = __builtin_amdgcn_readlane(ki, lastr);
-      const uint32_t VT = __builtin_amdgcn_readlane(vi, lastr);
-      // (row: the lane holding that byte; lastr when none does)
-      auto first_at = [&](uint32_t len, uint32_t src, uint32_t pr, uint32_t tot, uint32_t Q,
-                          uint32_t& row) {
-        const uint64_t mk = __ballot(live && len && src + len > Q);
-        row = lastr;
-        if (!mk) return tot;
-        const uint32_t j = uint32_t(__ffsll(static_cast<unsigned long long>(mk)) - 1);
-        row = j;
-        const uint32_t s0 = __builtin_amdgcn_readlane(src, j), p0 = __builtin_amdgcn_readlane(pr, j);
-        return Q > s0 ? p0 + (Q - s0) : p0;
-      };
-      uint32_t X[4], jx, jv;
-      X[0] = first_at(k, ks, kp, KT, P0, jx);
-      X[1] = last_tile ? uint32_t(round16(KT)) : first_at(k, ks, kp, KT, P1, jx);
-      X[2] = first_at(v, vs, vp, VT, P0, jv);
-      X[3] = last_tile ? uint32_t(round16(VT)) : first_at(v, vs, vp, VT, P1, jx);
-      if constexpr (kLineCut) {
-        // a cut Y at source Q moves up to the next 128-byte line of the arena
-        // when the bytes it adds have their sources within kLineExt - 32 of Q
-        // (the tile before the cut stages that far); both tiles of a cut
-        // decide from the same row table, so they agree
-        auto line_cut = [&](uint32_t Y, uint32_t Q) -> uint32_t {
-          const uint32_t end = uint32_t(round16(VT));
-          uint32_t Yl = uint32_t(((vb0 + Y + 127) & ~uint64_t(127)) - vb0);
-          Yl = Yl > end ? end : Yl;
-          if (Yl <= Y || Y >= VT) return Yl <= Y ? Y : Yl;
-          const uint32_t y = min(Yl, VT) - 1;  // the last real byte the tile would add
-          const uint64_t mk = __ballot(live && v && vp <= y && y < vp + v);
-          if (!mk) return Y;
-          const uint32_t j = uint32_t(__ffsll(static_cast<unsigned long long>(mk)) - 1);
-          const uint32_t sy = __builtin_amdgcn_readlane(vs, j) + (y - __builtin_amdgcn_readlane(vp, j));
-          return sy + 32 <= Q + kLineExt ? Yl : Y;
-        };
-        if (t != 0) X[2] = line_cut(X[2], P0);
-        if (!last_tile) X[3] = line_cut(X[3], P1);
-        if (X[2] > X[3]) X[2] = X[3];
-        // the row holding X2 (head chunk: none when X2 is line-aligned)
-        const uint64_t mh = __ballot(live && v && vp <= X[2] && X[2] < vp + v);
-        jv = mh ? uint32_t(__ffsll(static_cast<unsigned long long>(mh)) - 1) : lastr;
-      }
-      // (sector form) the unrounded value cut at P1: value bytes before it
-      // have their sources in this tile's stage
-      const uint32_t Yv1 = X[3];
-      if constexpr (kSector) {
-        // every cut between two tiles of a block moves up to a 64-byte sector
-        // of the arena, so no destination sector is shared by two tiles; the
-        // few bytes this adds to the tile before the cut come from global
-        // windows when they lie past its stage
-        auto sector_up = [](uint32_t Y, uint64_t base, uint32_t tot) -> uint32_t {
-          const uint32_t end = uint32_t(round16(tot));
-          const uint32_t Ys = uint32_t(((base + Y + 63) & ~uint64_t(63)) - base);
-          return Ys > end ? end : Ys;
-        };
-        if (t != 0) {
-          if (kKeyRound) X[0] = sector_up(X[0], kb0, KT);
-          X[2] = sector_up(X[2], vb0, VT);
-        }
-        if (!last_tile) {
-          if (kKeyRound) X[1] = sector_up(X[1], kb0, KT);
-          X[3] = sector_up(X[3], vb0, VT);
-        }
-        X[0] = min(X[0], X[1]);
-        X[2] = min(X[2], X[3]);
-      }
-      if (lane == 0) {
-        R.x[0] = X[0];
-        R.x[1] = X[1];
-        R.x[2] = X[2];
-        R.x[3] = X[3];
-      }
-      // granule table of the key range: gt[0][g - (X0 >> 6)] = row holding byte
-      // max(64 g, X0); granules past the last row's bytes (padding) keep the
-      // preset lastr.  Values need none: their boundary chunks carry their row.
-#pragma unroll
-      for (uint32_t reg = 0; reg < 1u; ++reg) {
-        const uint32_t X0 = X[2 * reg], X1 = X[2 * reg + 1];
-        if (X1 <= X0) continue;
-        const uint32_t g0 = X0 >> 6, gl = (X1 - 1) >> 6;
-        for (uint32_t g = g0 + lane; g <= gl; g += 64) gt[reg][g - g0] = uint8_t(lastr);
-        const uint32_t pr = reg ? vp : kp, ln = reg ? v : k;
-        if (live && ln) {
-          const uint32_t e = pr + ln;
-          if (pr <= X0 && X0 < e) gt[reg][0] = uint8_t(lane);
-          const uint32_t gs = max(g0 + 1, (pr + 63) >> 6), ge = min(gl, ((e + 63) >> 6) - 1);
-          for (uint32_t g = gs; g <= ge; ++g) gt[reg][g - g0] = uint8_t(lane);
-        }
-      }
-      if constexpr (kSector) {
-        // row pieces of the owned value range: [a, e) = row r's bytes in [X2, X3).
-        // Runs: the whole 64-byte sectors inside a piece (and before Yv1), in
-        // units of <= 64 chunks -- one wave store writes whole sectors.  Every
-        // other sector a piece touches is a mixed sector: its four chunks are
-        // assembled by four adjacent lanes and stored by one instruction.
-        const uint32_t X2 = X[2], X3 = X[3];
-        const uint32_t a = max(vp, X2), e = min(vp + v, X3);
-        const bool piece = live && v && a < e;
-        const uint64_t va = vb0 + a, ve = vb0 + min(e, Yv1);
-        const uint64_t s0 = (va + 63) & ~uint64_t(63), s1 = ve & ~uint64_t(63);
-        const bool run = piece && s1 > s0;
-        const uint32_t cs = run ? uint32_t((s0 - vb0) >> 4) : 0u;
-        const uint32_t wc = run ? uint32_t((s1 - s0) >> 4) : 0u;
-        const uint32_t nu = (wc + 63) >> 6;
-        const uint32_t ui = wave_scan_dpp(nu);
-        const uint32_t sbias0 = uint32_t(int64_t(off) - A);
-        for (uint32_t q = 0; q < nu; ++q) {
-          const uint32_t u = ui - nu + q;
-          R.unit[0][u] = cs + 64 * q;
-          R.unit[1][u] = vs - vp + 16 * (cs + 64 * q) + sbias0;
-          R.unit[2][u] = min(64u, wc - 64 * q);
-        }
-        // mixed sectors, as (sector - the region's first sector) << 8 | the
-        // lowest row with bytes in it (rows in order, head before tail; equal
-        // neighbours skipped by the consumer)
-        const uint64_t vs0 = vb0 >> 6;
-        const uint32_t hsec = uint32_t(((vb0 + a) >> 6) - vs0);
-        const uint32_t tsec = uint32_t(((vb0 + e - 1) >> 6) - vs0);
-        const bool need_h = piece && (!run || s0 > va);
-        const bool need_t = piece && (run ? s1 < vb0 + e : tsec != hsec);
-        const uint32_t nme = uint32_t(need_h) + uint32_t(need_t);
-        const uint32_t mi = wave_scan_dpp(nme) - nme;
-        if (need_h) R.bnd[mi] = (hsec << 8) | lane;
-        if (need_t) R.bnd[mi + uint32_t(need_h)] = (tsec << 8) | lane;
-        const uint32_t nunit = __builtin_amdgcn_readlane(ui, 63);
-        const uint32_t nmix = __builtin_amdgcn_readlane(mi + nme, 63);
-        if (lane == 0) {
-          R.nbnd = nmix;
-          R.nunit = nunit;
-        }
-      } else {
-        // row pieces of the owned value range: [a, e) = row r's bytes in [X2, X3)
-        const uint32_t X2 = X[2], X3 = X[3];
-        const uint32_t a = max(vp, X2), e = min(vp + v, X3);
-        const bool piece = live && v && a < e;
-        const uint32_t cs = piece ? (a + 15) >> 4 : 0u, ce = piece ? e >> 4 : 0u;
-        const uint32_t wc = ce > cs ? ce - cs : 0u;
-        const uint32_t nu = (wc + 63) >> 6;
-        const uint32_t ui = wave_scan_dpp(nu);
-        const uint32_t sbias0 = uint32_t(int64_t(off) - A);
-        for (uint32_t q = 0; q < nu; ++q) {
-          const uint32_t u = ui - nu + q;
-          R.unit[0][u] = cs + 64 * q;
-          R.unit[1][u] = vs - vp + 16 * (cs + 64 * q) + sbias0;
-          R.unit[2][u] = min(64u, wc - 64 * q);
-        }
-        // boundary chunks: where a piece ends inside a chunk, and the range's
-        // first chunk when it starts inside one (in order; equal neighbours
-        // skipped), as chunk << 8 | the row holding the chunk's first owned
-        // byte: the lowest row whose piece ends in the chunk (a row before it
-        // holding that byte would end in the chunk too), or for the head chunk
-        // the row holding X2
-        const bool eb = piece && (e & 15);
-        const uint64_t m = __ballot(eb);
-        const uint32_t head = (X2 < X3 && (X2 & 15)) ? 1u : 0u;
-        const uint32_t idx = head + uint32_t(__builtin_amdgcn_mbcnt_hi(
-                                        uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u)));
-        if (eb) R.bnd[idx] = ((e >> 4) << 8) | lane;
-        // read lane 63 with the whole wave active (inside the lane-0 branch the
-        // compiler may compute ui for lane 0 only)
-        const uint32_t nunit = __builtin_amdgcn_readlane(ui, 63);
-        if (lane == 0) {
-          if (head) R.bnd[0] = ((X2 >> 4) << 8) | jv;
-          R.nbnd = head + uint32_t(__builtin_popcountll(m));
-          R.nunit = nunit;
-        }
-      }
-    }
-    if (P.index_only && t == 0 && live) {  // the SoA row index (spans into seg)
-      const uint64_t g = row0 + lane;
-      P.key_len[g] = uint16_t(k);
-      P.val_len[g] = v;
-      P.key_off[g] = off + ks;
-      P.val_off[g] = off + vs;
+}
+
+// The row table (wave 0, lane r = row r) while the tile is in flight.
+template <class Rows>
+__device__ __forceinline__ TileLane tile_row_table(const TileBlock& B, const TileExtent& X,
+                                                   uint32_t rec, uint32_t kl, Rows& R) {
+  const uint32_t lane = threadIdx.x & 63;
+  const bool live = lane < X.rows;
+  uint32_t nxt = __builtin_amdgcn_update_dpp(0u, rec, 0x130, 0xf, 0xf, false);  // rec[lane + 1]
+  if (lane == X.lastr) nxt = uint32_t(B.pend);
+  const uint32_t k = live ? kl : 0u, v = live ? nxt - rec - 6 - kl : 0u;
+  const uint32_t ki = wave_scan_dpp(k), vi = wave_scan_dpp(v);
+  const uint32_t kp = ki - k, vp = vi - v;
+  const uint32_t ks = rec + 6, vs = rec + 6 + k;  // block positions of the key / value
+  if (live) {
+    R.pre[0][lane] = kp;
+    R.pre[1][lane] = vp;
+    R.sb[0][lane] = ks - kp;
+    R.sb[1][lane] = vs - vp;
+    if (lane == X.lastr) {
+      R.pre[0][X.rows] = ki;
+      R.pre[1][X.rows] = vi;
     }
   }
-  if (P.index_only) {
-    block_outputs();
-    return;
+  return {k, v, kp, vp, ks, vs, live};
+}
+
+// The first region byte whose source is >= Q (tot when none is).
+// (row: the lane holding that byte; lastr when none does)
+__device__ __forceinline__ uint32_t first_at(bool live, uint32_t lastr, uint32_t len, uint32_t src,
+                                             uint32_t pr, uint32_t tot, uint32_t Q,
+                                             uint32_t& row) {
+  const uint64_t mk = __ballot(live && len && src + len > Q);
+  row = lastr;
+  if (!mk) return tot;
+  const uint32_t j = uint32_t(__ffsll(static_cast<unsigned long long>(mk)) - 1);
+  row = j;
+  const uint32_t s0 = __builtin_amdgcn_readlane(src, j), p0 = __builtin_amdgcn_readlane(pr, j);
+  return Q > s0 ? p0 + (Q - s0) : p0;
+}
+
+// The owned ranges: [first byte whose source is >= P0, same for P1); the
+// last tile also owns the 16-byte padding after the region.
+__device__ __forceinline__ TileCuts tile_owned_ranges(const TileLane& W, const TileExtent& X) {
+  TileCuts C;
+  uint32_t jx;
+  C.KT = __builtin_amdgcn_readlane(W.kp + W.k, X.lastr);
+  C.VT = __builtin_amdgcn_readlane(W.vp + W.v, X.lastr);
+  C.x[0] = first_at(W.live, X.lastr, W.k, W.ks, W.kp, C.KT, X.P0, jx);
+  C.x[1] = X.last_tile ? uint32_t(round16(C.KT))
+                       : first_at(W.live, X.lastr, W.k, W.ks, W.kp, C.KT, X.P1, jx);
+  C.x[2] = first_at(W.live, X.lastr, W.v, W.vs, W.vp, C.VT, X.P0, C.jv);
+  C.x[3] = X.last_tile ? uint32_t(round16(C.VT))
+                       : first_at(W.live, X.lastr, W.v, W.vs, W.vp, C.VT, X.P1, jx);
+  return C;
+}
+
+// A value cut Y at source Q moves up to the next 128-byte line of the arena
+// when the bytes it adds have their sources within kLineExt - 32 of Q
+// (the tile before the cut stages that far); both tiles of a cut
+// decide from the same row table, so they agree.
+__device__ __forceinline__ uint32_t line_cut(const TileLane& W, uint64_t vb0, uint32_t VT,
+                                             uint32_t Y, uint32_t Q) {
+  const uint32_t end = uint32_t(round16(VT));
+  uint32_t Yl = uint32_t(((vb0 + Y + 127) & ~uint64_t(127)) - vb0);
+  Yl = Yl > end ? end : Yl;
+  if (Yl <= Y || Y >= VT) return Yl <= Y ? Y : Yl;
+  const uint32_t y = min(Yl, VT) - 1;  // the last real byte the tile would add
+  const uint64_t mk = __ballot(W.live && W.v && W.vp <= y && y < W.vp + W.v);
+  if (!mk) return Y;
+  const uint32_t j = uint32_t(__ffsll(static_cast<unsigned long long>(mk)) - 1);
+  const uint32_t sy = __builtin_amdgcn_readlane(W.vs, j) + (y - __builtin_amdgcn_readlane(W.vp, j));
+  return sy + 32 <= Q + kLineExt ? Yl : Y;
+}
+__device__ __forceinline__ void tile_line_cut(const TileBlock& B, const TileExtent& X,
+                                              const TileLane& W, TileCuts& C) {
+  if (B.t != 0) C.x[2] = line_cut(W, B.vb0, C.VT, C.x[2], X.P0);
+  if (!X.last_tile) C.x[3] = line_cut(W, B.vb0, C.VT, C.x[3], X.P1);
+  if (C.x[2] > C.x[3]) C.x[2] = C.x[3];
+  // the row holding X2 (head chunk: none when X2 is line-aligned)
+  const uint64_t mh = __ballot(W.live && W.v && W.vp <= C.x[2] && C.x[2] < W.vp + W.v);
+  C.jv = mh ? uint32_t(__ffsll(static_cast<unsigned long long>(mh)) - 1) : X.lastr;
+}
+
+template <class Rows>
+__device__ __forceinline__ void tile_put_cuts(const TileCuts& C, Rows& R) {
+  if ((threadIdx.x & 63) == 0) {
+    R.x[0] = C.x[0];
+    R.x[1] = C.x[1];
+    R.x[2] = C.x[2];
+    R.x[3] = C.x[3];
   }
-  // the DMA waves wait for their loads (wave 0 has none: its SoA stores drain
-  // on their own)
-  if (tid >= 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+// Granule table of a range [X0, X1) of a region: gt[g - (X0 >> 6)] = row
+// holding byte max(64 g, X0); granules past the last row's bytes (padding)
+// keep the preset lastr.  The product builds the key range's only: the
+// values' boundary chunks carry their row.  (pr, ln: the lane's prefix and
+// length in the region.)
+__device__ __forceinline__ void tile_granules(const TileExtent& X, bool live, uint32_t pr,
+                                              uint32_t ln, uint32_t X0, uint32_t X1, uint8_t* gt) {
+  const uint32_t lane = threadIdx.x & 63;
+  if (X1 <= X0) return;
+  const uint32_t g0 = X0 >> 6, gl = (X1 - 1) >> 6;
+  for (uint32_t g = g0 + lane; g <= gl; g += 64) gt[g - g0] = uint8_t(X.lastr);
+  if (live && ln) {
+    const uint32_t e = pr + ln;
+    if (pr <= X0 && X0 < e) gt[0] = uint8_t(lane);
+    const uint32_t gs = max(g0 + 1, (pr + 63) >> 6), ge = min(gl, ((e + 63) >> 6) - 1);
+    for (uint32_t g = gs; g <= ge; ++g) gt[g - g0] = uint8_t(lane);
+  }
+}
+
+// The value units and boundary chunks of the owned value range.
+template <class Rows>
+__device__ __forceinline__ void tile_value_units(const TileBlock& B, const TileExtent& X,
+                                                 const TileLane& W, const TileCuts& C, Rows& R) {
+  const uint32_t lane = threadIdx.x & 63;
+  // row pieces of the owned value range: [a, e) = row r's bytes in [X2, X3)
+  const uint32_t X2 = C.x[2], X3 = C.x[3];
+  const uint32_t a = max(W.vp, X2), e = min(W.vp + W.v, X3);
+  const bool piece = W.live && W.v && a < e;
+  const uint32_t cs = piece ? (a + 15) >> 4 : 0u, ce = piece ? e >> 4 : 0u;
+  const uint32_t wc = ce > cs ? ce - cs : 0u;
+  const uint32_t nu = (wc + 63) >> 6;
+  const uint32_t ui = wave_scan_dpp(nu);
+  const uint32_t sbias0 = uint32_t(int64_t(B.off) - X.A);
+  for (uint32_t q = 0; q < nu; ++q) {
+    const uint32_t u = ui - nu + q;
+    R.unit[0][u] = cs + 64 * q;
+    R.unit[1][u] = W.vs - W.vp + 16 * (cs + 64 * q) + sbias0;
+    R.unit[2][u] = min(64u, wc - 64 * q);
+  }
+  // boundary chunks: where a piece ends inside a chunk, and the range's
+  // first chunk when it starts inside one (in order; equal neighbours
+  // skipped), as chunk << 8 | the row holding the chunk's first owned
+  // byte: the lowest row whose piece ends in the chunk (a row before it
+  // holding that byte would end in the chunk too), or for the head chunk
+  // the row holding X2
+  const bool eb = piece && (e & 15);
+  const uint64_t m = __ballot(eb);
+  const uint32_t head = (X2 < X3 && (X2 & 15)) ? 1u : 0u;
+  const uint32_t idx = head + uint32_t(__builtin_amdgcn_mbcnt_hi(
+                                  uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u)));
+  if (eb) R.bnd[idx] = ((e >> 4) << 8) | lane;
+  // read lane 63 with the whole wave active (inside the lane-0 branch the
+  // compiler may compute ui for lane 0 only)
+  const uint32_t nunit = __builtin_amdgcn_readlane(ui, 63);
+  if (lane == 0) {
+    if (head) R.bnd[0] = ((X2 >> 4) << 8) | C.jv;
+    R.nbnd = head + uint32_t(__builtin_popcountll(m));
+    R.nunit = nunit;
+  }
+}
+
+// Index-only decodes: tile 0 writes the SoA row index (spans into seg).
+__device__ __forceinline__ void tile_index_rows(const CopyParams& P, const TileBlock& B,
+                                                const TileLane& W) {
+  if (P.index_only && B.t == 0 && W.live) {
+    const uint64_t g = B.row0 + (threadIdx.x & 63);
+    P.key_len[g] = uint16_t(W.k);
+    P.val_len[g] = W.v;
+    P.key_off[g] = B.off + W.ks;
+    P.val_off[g] = B.off + W.vs;
+  }
+}
+
+// The DMA waves wait for their loads (wave 0 has none: its SoA stores drain
+// on their own); then the tables and the stage are everyone's.
+__device__ __forceinline__ void tile_wait_stage() {
+  if (threadIdx.x >= 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (t == 0 && tid < 64) {  // the block outputs and SoA row index (from the LDS tables)
-    block_outputs();
-    if (!(kSkip & 1) && lane < rows) {
-      const uint64_t g = row0 + lane;
+}
+
+// Tile 0: the block outputs and the SoA row index (from the LDS tables).
+template <class Rows>
+__device__ __forceinline__ void tile_row_index(const CopyParams& P, const TileBlock& B,
+                                               const TileExtent& X, const Rows& R) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  if (B.t == 0 && tid < 64) {
+    block_outputs(P, B);
+    if (lane < X.rows) {
+      const uint64_t g = B.row0 + lane;
       const uint32_t kp = R.pre[0][lane], vp = R.pre[1][lane];
       P.key_len[g] = uint16_t(R.pre[0][lane + 1] - kp);
       P.val_len[g] = R.pre[1][lane + 1] - vp;
-      P.key_off[g] = kb0 + kp;
-      P.val_off[g] = vb0 + vp;
+      P.key_off[g] = B.kb0 + kp;
+      P.val_off[g] = B.vb0 + vp;
     }
   }
-  const uint32_t kx0 = R.x[0], kx1 = R.x[1], vx0 = R.x[2], vx1 = R.x[3];
-  const uint32_t nk = kx1 > kx0 ? ((kx1 + 15) >> 4) - (kx0 >> 4) : 0u;
-  const uint32_t sbias = uint32_t(int64_t(off) - A);  // stage byte of block position s: s + sbias
-  {
-    // value runs: one unit of <= 64 whole chunks of one row per wave iteration
-    const uint32_t nunit = R.nunit, nbnd = R.nbnd;
-    uint8_t* const varena = P.val_arena + vb0;
-    for (uint32_t u = tid >> 6; u < ((kSkip & 2) ? 0u : nunit); u += kNT / 64) {
-      const uint32_t c0 = __builtin_amdgcn_readfirstlane(R.unit[0][u]);
-      const uint32_t sbyte = __builtin_amdgcn_readfirstlane(R.unit[1][u]);
-      const uint32_t cnt = __builtin_amdgcn_readfirstlane(R.unit[2][u]);
-      if (lane < cnt) {
-        const uint32_t line = (sbyte >> 4) + lane;
-        const uint4 w = funnel_u(stage[line], stage[line + 1], sbyte & 15);
-        *reinterpret_cast<uint4*>(varena + (uint64_t(c0 + lane) << 4)) = w;
-      }
-    }
-    if constexpr (kSector) {
-      // keys (from the first chunk of the range's first sector, so each wave
-      // store covers whole sectors) and the mixed value sectors, four lanes
-      // each: per-lane lookup; sources past the stage from global windows
-      const uint32_t kc0 = kx0 >> 4;
-      const uint32_t kph = uint32_t(((kb0 >> 4) + kc0) & 3u);
-      const uint32_t nk4 = nk ? (kph + nk + 3) & ~3u : 0u;
-      const uint32_t vph = uint32_t(vb0 & 63);
-      for (uint32_t j = tid; j < nk4 + 4 * nbnd; j += kNT) {
-        const uint32_t reg = j >= nk4;
-        if ((kSkip & 4) && !reg) continue;
-        uint32_t r;
-        int32_t xs;
-        if (reg) {
-          const uint32_t ei = (j - nk4) >> 2;
-          const uint32_t bv = R.bnd[ei];
-          if (ei && (bv >> 8) == (R.bnd[ei - 1] >> 8)) continue;
-          xs = int32_t((bv >> 8) * 64u) - int32_t(vph) + int32_t(16 * ((j - nk4) & 3u));
-          r = bv & 255u;
-        } else {
-          xs = int32_t(16 * (kc0 + j)) - int32_t(16 * kph);
-          r = 0;
-        }
-        const uint32_t X0 = reg ? vx0 : kx0, X1 = reg ? vx1 : kx1;
-        if (xs + 16 <= int32_t(X0) || xs >= int32_t(X1)) continue;
-        const uint32_t x = uint32_t(xs);
-        const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
-        const uint32_t* pre = R.pre[reg];
-        const uint32_t* sb = R.sb[reg];
-        if (!reg) r = uint32_t(gt[0][(lo >> 6) - (X0 >> 6)]);
-        while (r < lastr && pre[r + 1] <= lo) ++r;
-        uint8_t* dst = (reg ? P.val_arena + vb0 : P.key_arena + kb0) + x;
-        const uint32_t dend = min(hi, pre[rows]);
-        uint4 out = make_uint4(0, 0, 0, 0);
-        for (uint32_t d = lo; d < dend; ++r) {
-          const uint32_t e = min(dend, pre[r + 1]);
-          if (e > d) {
-            const uint32_t bi = sb[r] + x + sbias;
-            const uint4 w = ((bi >> 4) + 1 < np)
-                                ? load16_lds_b128(stage, bi)
-                                : window16(P.seg, P.seg_bytes, int64_t(off) + sb[r] + x);
-            out = merge_bytes(out, w, int32_t(d - x), int32_t(e - x));
-            d = e;
-          }
-        }
-        if (lo == x && hi == x + 16)
-          *reinterpret_cast<uint4*>(dst) = out;
-        else
-          store_partial(dst, out, lo - x, hi - x);
-      }
-      return;
-    }
-    // keys and the boundary value chunks: per-lane lookup
-    for (uint32_t j = tid; j < nk + nbnd; j += kNT) {
-      const uint32_t reg = j >= nk;
-      if ((kSkip & 4) && !reg) continue;
-      if ((kSkip & 8) && reg) continue;
-      const uint32_t bv = reg ? R.bnd[j - nk] : 0u;
-      if (reg && j > nk && (bv >> 8) == (R.bnd[j - nk - 1] >> 8)) continue;
-      const uint32_t X0 = reg ? vx0 : kx0, X1 = reg ? vx1 : kx1;
-      const uint32_t x = reg ? (bv >> 8) << 4 : ((kx0 >> 4) + j) << 4;
-      const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
-      const uint32_t* pre = R.pre[reg];
-      const uint32_t* sb = R.sb[reg];
-      uint32_t r = reg ? (bv & 255u) : uint32_t(gt[0][(lo >> 6) - (X0 >> 6)]);
-      while (r < lastr && pre[r + 1] <= lo) ++r;
-      uint8_t* dst = (reg ? P.val_arena + vb0 : P.key_arena + kb0) + x;
-      const uint32_t dend = min(hi, pre[rows]);
-      uint4 out = make_uint4(0, 0, 0, 0);
-      for (uint32_t d = lo; d < dend; ++r) {
-        const uint32_t e = min(dend, pre[r + 1]);
-        if (e > d) {
-          out = merge_bytes(out, load16_lds_b128(stage, sb[r] + x + sbias), int32_t(d - x),
-                            int32_t(e - x));
-          d = e;
-        }
-      }
-      if (lo == x && hi == x + 16)
-        *reinterpret_cast<uint4*>(dst) = out;
-      else if (!(kSkip & 16))
-        store_partial(dst, out, lo - x, hi - x);
+}
+
+// The ranges and counts wave 0 left in LDS (read together: one trip).
+template <class Rows>
+__device__ __forceinline__ TileOwned tile_owned(const Rows& R) {
+  return {R.x[0], R.x[1], R.x[2], R.x[3], R.nunit, R.nbnd};
+}
+
+// Value runs: one unit of <= 64 whole chunks of one row per wave iteration.
+template <uint32_t kNT, class Rows>
+__device__ __forceinline__ void tile_store_runs(const CopyParams& P, const TileBlock& B,
+                                                const Rows& R, const uint4* stage,
+                                                uint32_t nunit) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  uint8_t* const varena = P.val_arena + B.vb0;
+  for (uint32_t u = tid >> 6; u < nunit; u += kNT / 64) {
+    const uint32_t c0 = __builtin_amdgcn_readfirstlane(R.unit[0][u]);
+    const uint32_t sbyte = __builtin_amdgcn_readfirstlane(R.unit[1][u]);
+    const uint32_t cnt = __builtin_amdgcn_readfirstlane(R.unit[2][u]);
+    if (lane < cnt) {
+      const uint32_t line = (sbyte >> 4) + lane;
+      const uint4 w = funnel_u(stage[line], stage[line + 1], sbyte & 15);
+      *reinterpret_cast<uint4*>(varena + (uint64_t(c0 + lane) << 4)) = w;
     }
   }
+}
+// Bytes [lo, hi) of the region's chunk [x, x + 16), row by row from row r on
+// (zero past the region): src(s) = the 16 bytes at block position s.
+template <class Src>
+__device__ __forceinline__ uint4 chunk_bytes(const uint32_t* pre, const uint32_t* sb,
+                                             uint32_t rows, uint32_t r, uint32_t x, uint32_t lo,
+                                             uint32_t hi, Src src) {
+  const uint32_t dend = min(hi, pre[rows]);
+  uint4 out = make_uint4(0, 0, 0, 0);
+  for (uint32_t d = lo; d < dend; ++r) {
+    const uint32_t e = min(dend, pre[r + 1]);
+    if (e > d) {  // bytes [d, e) of the chunk from row r
+      out = merge_bytes(out, src(sb[r] + x), int32_t(d - x), int32_t(e - x));
+      d = e;
+    }
+  }
+  return out;
+}
+
+// Chunk j of the keys (j < nk) and the boundary value chunks, by per-lane
+// lookup: its 16 bytes at dst, of which [lo, hi) are the tile's.  False for a
+// boundary chunk equal to its neighbour (nothing to store).
+struct TileChunk {
+  uint8_t* dst;
+  uint4 out;
+  uint32_t lo, hi;
+};
+template <class Rows>
+__device__ __forceinline__ bool tile_chunk(const CopyParams& P, const TileBlock& B,
+                                           const TileExtent& X, const Rows& R, const uint8_t* gt,
+                                           const uint4* stage, const TileOwned& O, uint32_t nk,
+                                           uint32_t j, TileChunk& c) {
+  const uint32_t sbias = uint32_t(int64_t(B.off) - X.A);  // stage byte of block position s: s + sbias
+  const uint32_t reg = j >= nk;
+  const uint32_t bv = reg ? R.bnd[j - nk] : 0u;
+  if (reg && j > nk && (bv >> 8) == (R.bnd[j - nk - 1] >> 8)) return false;
+  const uint32_t X0 = reg ? O.vx0 : O.kx0, X1 = reg ? O.vx1 : O.kx1;
+  const uint32_t x = reg ? (bv >> 8) << 4 : ((O.kx0 >> 4) + j) << 4;
+  const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
+  const uint32_t* pre = R.pre[reg];
+  const uint32_t* sb = R.sb[reg];
+  uint32_t r = reg ? (bv & 255u) : uint32_t(gt[(lo >> 6) - (X0 >> 6)]);
+  while (r < X.lastr && pre[r + 1] <= lo) ++r;
+  c.dst = (reg ? P.val_arena + B.vb0 : P.key_arena + B.kb0) + x;
+  c.out = chunk_bytes(pre, sb, X.rows, r, x, lo, hi,
+                      [&](uint32_t s) { return load16_lds_b128(stage, s + sbias); });
+  c.lo = lo - x;
+  c.hi = hi - x;
+  return true;
+}
+
+// Keys and the boundary value chunks.  A whole chunk is one 16-byte store; a
+// chunk the neighbouring tile shares is stored byte-exactly (disjoint bytes).
+template <uint32_t kNT, class Rows>
+__device__ __forceinline__ void tile_store_chunks(const CopyParams& P, const TileBlock& B,
+                                                  const TileExtent& X, const Rows& R,
+                                                  const uint8_t* gt, const uint4* stage,
+                                                  const TileOwned& O) {
+  const uint32_t nk = O.kx1 > O.kx0 ? ((O.kx1 + 15) >> 4) - (O.kx0 >> 4) : 0u;
+  for (uint32_t j = threadIdx.x; j < nk + O.nbnd; j += kNT) {
+    TileChunk c;
+    if (!tile_chunk(P, B, X, R, gt, stage, O, nk, j, c)) continue;
+    if (c.lo == 0 && c.hi == 16)
+      *reinterpret_cast<uint4*>(c.dst) = c.out;
+    else
+      store_partial(c.dst, c.out, c.lo, c.hi);
+  }
+}
+
+// The product form: the phases in order.
+template <uint32_t kT, uint32_t kNT, bool kXcd>
+__device__ __forceinline__ void tile_pass(const CopyParams& P, uint32_t tpb, uint32_t ntile) {
+  __shared__ TileRows<kT> R;
+  __shared__ uint8_t gt[kT / 64 + 8];  // row holding key byte max(64 g, range start), per 64-byte granule
+  __shared__ uint4 stage[(kT + kLineExt) / 16 + 4];
+  const uint32_t L = tile_index<kXcd>();
+  if (L >= ntile) return;
+  uint32_t rec, kl;
+  const TileBlock B = tile_block(P, L, tpb, rec, kl);
+  if (tile_idle<kT>(P, B)) {
+    block_outputs(P, B);
+    return;
+  }
+  const TileExtent X = tile_extent<kT>(B);
+  tile_dma<kNT>(P, B, X, stage);
+  if (threadIdx.x < 64) {
+    const TileLane W = tile_row_table(B, X, rec, kl, R);
+    if (!P.index_only) {
+      TileCuts C = tile_owned_ranges(W, X);
+      tile_line_cut(B, X, W, C);
+      tile_put_cuts(C, R);
+      tile_granules(X, W.live, W.kp, W.k, C.x[0], C.x[1], gt);
+      tile_value_units(B, X, W, C, R);
+    }
+    tile_index_rows(P, B, W);
+  }
+  if (P.index_only) {
+    block_outputs(P, B);
+    return;
+  }
+  tile_wait_stage();
+  tile_row_index(P, B, X, R);
+  const TileOwned O = tile_owned(R);
+  tile_store_runs<kNT>(P, B, R, stage, O.nunit);
+  tile_store_chunks<kNT>(P, B, X, R, gt, stage, O);
 }
 
 // 8 waves per SIMD (8 workgroups per CU: the LDS bound; registers capped at
@@ -2210,7 +2173,7 @@ TileGeo tile_geo(const okv_ctx* ctx, const Work& w, uint32_t nblk, bool index_on
 // consecutive tiles on one XCD (the grid padded to a multiple of 8).
 void launch_tile(okv_ctx* ctx, const CopyParams& P, const TileGeo& g) {
 #ifdef OKV_ABLATE
-  ablate_launch_tile(ctx, P, g);  // the OKV_TILE form (default: okv_tile_kernel_diag<.., 0>)
+  ablate_launch_tile(ctx, P, g);  // the OKV_TILE form (default: the product form)
 #else
   const uint32_t ntile = P.nblk * g.tpb;
   hipLaunchKernelGGL((okv_tile_kernel<kTileBytes, 256, true>), dim3((ntile + 7u) & ~7u),

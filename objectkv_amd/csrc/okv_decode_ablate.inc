@@ -2,10 +2,60 @@
 // compiled into libokv_sst_ablate.so only (okv_decode.hip includes this file
 // under -DOKV_ABLATE): the per-block global-window gather, the round-2 row
 // pass + value sweep, the wave-staged per-block gather, and the source-tile
-// pass with its diagnostic arms (tile sizes, widths, phase probes, no-DMA /
-// no-store / per-chunk / direct-load forms: tile_pass_diag, a copy of the
-// product tile_pass with the arms in).  The product library (libokv_sst.so)
-// contains none of them.
+// pass's measured forms (tile sizes, widths, phase probes, no-DMA / no-store /
+// per-chunk / direct-load / sector forms, omitted output classes), each a
+// composition of the product's phases (okv_decode.hip, tile_pass) and the
+// phases it alters.  The product library (libokv_sst.so) contains none of them.
+
+// The value sweep runs when every row's index is written by the per-block
+// pass 3 and the value arena is gap-free: no big block (okv_copy_kernel's
+// rows) and no capacity failure.  Every workgroup of both kernels reads the
+// same scalars, so they agree.
+constexpr uint32_t kSwTile = 4096;  // value-arena bytes per sweep tile
+__device__ __forceinline__ bool sweep_safe(const Totals& T, uint32_t nbig, uint64_t row_cap,
+                                           uint64_t key_cap, uint64_t val_cap) {
+  return nbig == 0 && T.rows <= row_cap && T.kb <= key_cap && T.vb <= val_cap;
+}
+
+// Value-sweep hand-off (lane r = row r): each row's value source, the row
+// owning each value-arena tile that starts inside its value, and the row's
+// boundary chunk.  A 16-byte chunk holding the end of row r's value (end not
+// 16-aligned) mixes rows (or the block's zero padding); the lane of the row
+// owning its first byte assembles it from the block's row table into
+// bchunk[row], and the sweep stores it with its tile (whole lines).  The
+// loads are issued first (with the key loads in flight: see okv_rows_kernel).
+__device__ __forceinline__ uint4 boundary_chunk(const CopyParams& P, const GatherSmem& sm,
+                                                const BlockMeta& m, int rows) {
+  const uint32_t t = threadIdx.x;
+  uint4 out = make_uint4(0, 0, 0, 0);
+  if (int(t) >= rows) return out;
+  const uint32_t v0 = sm.vpre[t], e = sm.vpre[t + 1];
+  const uint32_t C = e & ~15u;
+  if (e == v0 || (e & 15) == 0 || v0 > C) return out;  // no chunk of mine to assemble
+  out = merge_bytes(out, window16(P.seg, P.seg_bytes, int64_t(m.off + sm.vsb[t] + C)), 0,
+                    int32_t(e - C));
+  for (uint32_t j = t + 1; int(j) < rows && sm.vpre[j] < C + 16; ++j) {
+    const uint32_t q0 = sm.vpre[j], q1 = sm.vpre[j + 1];
+    if (q1 == q0) continue;
+    const uint4 w = window16(P.seg, P.seg_bytes, int64_t(m.off + sm.vsb[j] + C));
+    out = merge_bytes(out, w, int32_t(q0 - C), int32_t(min(q1, C + 16) - C));
+  }
+  return out;
+}
+__device__ __forceinline__ void sweep_handoff(const CopyParams& P, const GatherSmem& sm,
+                                              const BlockMeta& m, int rows, const uint4& bc) {
+  const uint32_t t = threadIdx.x;
+  if (int(t) >= rows) return;
+  const uint64_t g = m.B.row0 + t;
+  const uint32_t kl = sm.kpre[t + 1] - sm.kpre[t];
+  const uint32_t v0 = sm.vpre[t], e = sm.vpre[t + 1];
+  P.vsrc[g] = m.off + sm.rec[t] + 6 + kl;
+  P.bchunk[g] = bc;
+  for (uint64_t x = (m.B.vb0 + v0 + kSwTile - 1) & ~uint64_t(kSwTile - 1); x < m.B.vb0 + e;
+       x += kSwTile)
+    P.vtile[x / kSwTile] = uint32_t(g);
+}
+
 // Pass 3: one workgroup per block reads the block straight from HBM.  NT = 64
 // (one wave per block) for small blocks, where a block has only a few 1 KiB
 // tiles and more blocks in flight hide the row-table -> gather latency chain;
@@ -405,330 +455,49 @@ __global__ __launch_bounds__(256) void okv_value_sweep_kernel(SweepParams S) {
 
 
 // ---------------------------------------------------------------------------
-// The source-tile pass with its diagnostic arms.
+// The source-tile pass's measured forms.  Each is the product's sequence of
+// phases (okv_decode.hip, tile_pass) with the phases it alters, which live
+// here; the product's phases carry no flag for them.
 // ---------------------------------------------------------------------------
-template <uint32_t kT, uint32_t kNT, bool kXcd, int kDiag>
-__device__ __forceinline__ void tile_pass_diag(const CopyParams& P, uint32_t tpb, uint32_t ntile) {
-  // kDiag: 0 the product form (value runs); ablation arms: 1 no chunk pass,
-  // 2 no DMA, 3 phase probe of the per-chunk form, 4 (+ no stores), 5 (+ no
-  // data reads), 6 direct unaligned global loads, 7 phase probe of the product
-  // form, 8 the per-chunk form (every chunk looked up per lane); 9 (a launch
-  // choice) the product form without the 8-waves register cap
-  constexpr bool kDirect = kDiag == 6;  // no LDS stage: one unaligned global load per chunk
-  constexpr bool kChunk = (kDiag >= 3 && kDiag <= 5) || kDiag == 8;
-  constexpr bool kRuns = !kChunk && !kDirect;
-  constexpr bool kProbe = (kDiag >= 3 && kDiag <= 5) || kDiag == 7;
-  constexpr uint32_t kG = kT / 64 + 8;  // 64-byte destination granules per region table
-  __shared__ TileRows<kT> R;
-  __shared__ uint8_t gt[2][kG];         // row holding byte max(64 g, range start)
-  __shared__ uint4 stage[kT / 16 + 4];
-  uint32_t L = blockIdx.x;
-  if constexpr (kXcd) L = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  if (L >= ntile) return;
-  uint64_t T[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kProbe: phase timestamps (sampled workgroups)
-  if constexpr (kProbe) T[0] = __builtin_amdgcn_s_memrealtime();
-  // uniform block index (an SGPR: the loads below are scalar, all in one trip)
-  const uint32_t b = __builtin_amdgcn_readfirstlane(L / tpb);
-  const uint32_t t = L - b * tpb;
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  // one trip: the block's scalars and (wave 0) its record table
-  uint32_t rec = 0, kl = 0;
-  if (tid < 64) {
-    rec = P.rt_pos[rec_index(P.nblk, b, lane)];
-    kl = P.rt_kl[rec_index(P.nblk, b, lane)];
-  }
-  const uint64_t off = P.descs[b].offset;
-  const BlockCount c = P.cnt[b];
-  const Prefix lpre = P.lp[b], tpre = P.tile_pre[b / kTile];
-  // consume every scalar here: the scheduler otherwise sinks each load to its
-  // first use, one dependent trip after another
-  asm volatile("" ::"s"(off), "s"(c.rows), "s"(c.kbytes), "s"(c.vbytes), "s"(c.pend),
-               "s"(c.status), "s"(lpre.rows), "s"(lpre.kb), "s"(lpre.vb), "s"(tpre.rows),
-               "s"(tpre.kb), "s"(tpre.vb));
-  if constexpr (kProbe) T[1] = __builtin_amdgcn_s_memrealtime();
-  const uint64_t row0 = tpre.rows + lpre.rows, kb0 = tpre.kb + lpre.kb, vb0 = tpre.vb + lpre.vb;
-  const bool fits = row0 + c.rows <= P.row_cap &&
-                    (P.index_only ||
-                     (kb0 + round16(c.kbytes) <= P.key_cap && vb0 + round16(c.vbytes) <= P.val_cap));
-  const int32_t st = (c.status == OKV_BLK_OK && !fits) ? int32_t(OKV_BLK_CAPACITY) : c.status;
-  // Tile 0 writes the block outputs and the SoA row index.  Stores wait
-  // until the LDS tables are built: the compiler makes wave 0's LDS writes
-  // wait for the wave's outstanding memory operations (it cannot tell them
-  // from the DMA's LDS target).
-  auto block_outputs = [&]() {
-    if (t == 0 && tid == 0) {
-      P.row_start[b] = row0;
-      if (P.key_base) P.key_base[b] = kb0;
-      if (P.val_base) P.val_base[b] = vb0;
-      P.blk_status[b] = st;
-    }
-  };
-  const uint64_t pend = c.pend;
-  const uint32_t P0 = t * kT;
-  // big blocks are okv_copy_kernel's (the same test as okv_count_kernel's)
-  if (st != OKV_BLK_OK || c.rows == 0 || c.rows > uint64_t(kRCap) || pend > P.span_cap ||
-      pend >= (uint64_t(1) << 32) || P0 >= pend) {
-    block_outputs();
-    return;
-  }
-  const uint32_t rows = uint32_t(c.rows), lastr = rows - 1;
-  const uint32_t P1 = uint32_t(min<uint64_t>(uint64_t(P0) + kT, pend));
-  const bool last_tile = P1 == pend;
-  // stage = segment lines [A, E): the line before the one holding the tile's
-  // first byte (a chunk's window begins up to 15 bytes before its first owned
-  // byte) through the line after the one holding its last byte + 15
-  const int64_t A = int64_t((off + P0) & ~uint64_t(15)) - 16;
-  const int64_t E = int64_t((off + P1 + 15) & ~uint64_t(15)) + 16;
-  const uint32_t np = uint32_t((E - A) >> 4);
-  // Waves 1.. issue the DMA; wave 0 builds the row table meanwhile.  (With a
-  // share of the DMA in flight, wave 0's LDS row-table writes would wait for
-  // it: the compiler cannot tell them apart from the DMA's LDS target.)
-  if (!P.index_only && kDiag != 2 && !kDirect && tid >= 64) {
-    const int64_t lim = int64_t(round16(P.seg_bytes));
-    const uint32_t u = tid - 64;
-    for (uint32_t k0 = 0; k0 < np; k0 += kNT - 64) {
-      const uint32_t i = k0 + u;
-      if (i < np) {
-        int64_t a = A + (int64_t(i) << 4);
-        if (a < 0 || a + 16 > lim) a = int64_t(off) & ~int64_t(15);  // bytes never used
-        __builtin_amdgcn_global_load_lds(P.seg + a, OKV_LDS_PTR(stage + k0 + (u & ~63u)), 16,
-                                         0, 0);
-      }
-    }
-  }
-  if constexpr (kProbe) T[2] = __builtin_amdgcn_s_memrealtime();
-  // row table (wave 0, lane r = row r) while the tile is in flight
-  if (tid < 64) {
-    const bool live = lane < rows;
-    uint32_t nxt = __builtin_amdgcn_update_dpp(0u, rec, 0x130, 0xf, 0xf, false);  // rec[lane + 1]
-    if (lane == lastr) nxt = uint32_t(pend);
-    const uint32_t k = live ? kl : 0u, v = live ? nxt - rec - 6 - kl : 0u;
-    const uint32_t ki = wave_scan_dpp(k), vi = wave_scan_dpp(v);
-    const uint32_t kp = ki - k, vp = vi - v;
-    const uint32_t ks = rec + 6, vs = rec + 6 + k;  // block positions of the key / value
-    if (live) {
-      R.pre[0][lane] = kp;
-      R.pre[1][lane] = vp;
-      R.sb[0][lane] = ks - kp;
-      R.sb[1][lane] = vs - vp;
-      if (lane == lastr) {
-        R.pre[0][rows] = ki;
-        R.pre[1][rows] = vi;
-      }
-    }
-    if (!P.index_only) {
-      // the owned ranges: [first byte whose source is >= P0, same for P1); the
-      // last tile also owns the 16-byte padding after the region
-      const uint32_t KT = __builtin_amdgcn_readlane(ki, lastr);
-      const uint32_t VT = __builtin_amdgcn_readlane(vi, lastr);
-      // (row: the lane holding that byte; lastr when none does)
-      auto first_at = [&](uint32_t len, uint32_t src, uint32_t pr, uint32_t tot, uint32_t Q,
-                          uint32_t& row) {
-        const uint64_t mk = __ballot(live && len && src + len > Q);
-        row = lastr;
-        if (!mk) return tot;
-        const uint32_t j = uint32_t(__ffsll(static_cast<unsigned long long>(mk)) - 1);
-        row = j;
-        const uint32_t s0 = __builtin_amdgcn_readlane(src, j), p0 = __builtin_amdgcn_readlane(pr, j);
-        return Q > s0 ? p0 + (Q - s0) : p0;
-      };
-      uint32_t X[4], jx, jv;
-      X[0] = first_at(k, ks, kp, KT, P0, jx);
-      X[1] = last_tile ? uint32_t(round16(KT)) : first_at(k, ks, kp, KT, P1, jx);
-      X[2] = first_at(v, vs, vp, VT, P0, jv);
-      X[3] = last_tile ? uint32_t(round16(VT)) : first_at(v, vs, vp, VT, P1, jx);
-      if (lane == 0) {
-        R.x[0] = X[0];
-        R.x[1] = X[1];
-        R.x[2] = X[2];
-        R.x[3] = X[3];
-      }
-      // granule tables: gt[reg][g - (X0 >> 6)] = row holding byte max(64 g, X0);
-      // granules past the last row's bytes (padding) keep the preset lastr.
-      // The value-run form needs the key table only (its boundary chunks carry
-      // their row): a 4 KiB value is 64 granules, a serial per-lane loop.
-#pragma unroll
-      for (uint32_t reg = 0; reg < (kRuns ? 1u : 2u); ++reg) {
-        const uint32_t X0 = X[2 * reg], X1 = X[2 * reg + 1];
-        if (X1 <= X0) continue;
-        const uint32_t g0 = X0 >> 6, gl = (X1 - 1) >> 6;
-        for (uint32_t g = g0 + lane; g <= gl; g += 64) gt[reg][g - g0] = uint8_t(lastr);
-        const uint32_t pr = reg ? vp : kp, ln = reg ? v : k;
-        if (live && ln) {
-          const uint32_t e = pr + ln;
-          if (pr <= X0 && X0 < e) gt[reg][0] = uint8_t(lane);
-          const uint32_t gs = max(g0 + 1, (pr + 63) >> 6), ge = min(gl, ((e + 63) >> 6) - 1);
-          for (uint32_t g = gs; g <= ge; ++g) gt[reg][g - g0] = uint8_t(lane);
-        }
-      }
-      if constexpr (kRuns) {
-        // row pieces of the owned value range: [a, e) = row r's bytes in [X2, X3)
-        const uint32_t X2 = X[2], X3 = X[3];
-        const uint32_t a = max(vp, X2), e = min(vp + v, X3);
-        const bool piece = live && v && a < e;
-        const uint32_t cs = piece ? (a + 15) >> 4 : 0u, ce = piece ? e >> 4 : 0u;
-        const uint32_t wc = ce > cs ? ce - cs : 0u;
-        const uint32_t nu = (wc + 63) >> 6;
-        const uint32_t ui = wave_scan_dpp(nu);
-        const uint32_t sbias0 = uint32_t(int64_t(off) - A);
-        for (uint32_t q = 0; q < nu; ++q) {
-          const uint32_t u = ui - nu + q;
-          R.unit[0][u] = cs + 64 * q;
-          R.unit[1][u] = vs - vp + 16 * (cs + 64 * q) + sbias0;
-          R.unit[2][u] = min(64u, wc - 64 * q);
-        }
-        // boundary chunks: where a piece ends inside a chunk, and the range's
-        // first chunk when it starts inside one (in order; equal neighbours
-        // skipped), as chunk << 8 | the row holding the chunk's first owned
-        // byte: the lowest row whose piece ends in the chunk (a row before it
-        // holding that byte would end in the chunk too), or for the head chunk
-        // the row holding X2
-        const bool eb = piece && (e & 15);
-        const uint64_t m = __ballot(eb);
-        const uint32_t head = (X2 < X3 && (X2 & 15)) ? 1u : 0u;
-        const uint32_t idx = head + uint32_t(__builtin_amdgcn_mbcnt_hi(
-                                        uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u)));
-        if (eb) R.bnd[idx] = ((e >> 4) << 8) | lane;
-        // read lane 63 with the whole wave active (inside the lane-0 branch the
-        // compiler may compute ui for lane 0 only)
-        const uint32_t nunit = __builtin_amdgcn_readlane(ui, 63);
-        if (lane == 0) {
-          if (head) R.bnd[0] = ((X2 >> 4) << 8) | jv;
-          R.nbnd = head + uint32_t(__builtin_popcountll(m));
-          R.nunit = nunit;
-        }
-      }
-    }
-    if (P.index_only && t == 0 && live) {  // the SoA row index (spans into seg)
-      const uint64_t g = row0 + lane;
-      P.key_len[g] = uint16_t(k);
-      P.val_len[g] = v;
-      P.key_off[g] = off + ks;
-      P.val_off[g] = off + vs;
-    }
-  }
-  if constexpr (kProbe) T[3] = __builtin_amdgcn_s_memrealtime();
-  if (P.index_only) {
-    block_outputs();
-    return;
-  }
-  // the DMA waves wait for their loads (wave 0 has none: its SoA stores drain
-  // on their own)
-  if (tid >= 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if constexpr (kProbe) T[4] = __builtin_amdgcn_s_memrealtime();
-  if (t == 0 && tid < 64) {  // the block outputs and SoA row index (from the LDS tables)
-    block_outputs();
-    if (lane < rows) {
-      const uint64_t g = row0 + lane;
-      const uint32_t kp = R.pre[0][lane], vp = R.pre[1][lane];
-      P.key_len[g] = uint16_t(R.pre[0][lane + 1] - kp);
-      P.val_len[g] = R.pre[1][lane + 1] - vp;
-      P.key_off[g] = kb0 + kp;
-      P.val_off[g] = vb0 + vp;
-    }
-  }
-  const uint32_t kx0 = R.x[0], kx1 = R.x[1], vx0 = R.x[2], vx1 = R.x[3];
-  const uint32_t nk = kx1 > kx0 ? ((kx1 + 15) >> 4) - (kx0 >> 4) : 0u;
-  const uint32_t nv = vx1 > vx0 ? ((vx1 + 15) >> 4) - (vx0 >> 4) : 0u;
-  const uint32_t sbias = uint32_t(int64_t(off) - A);  // stage byte of block position s: s + sbias
-  if (kDiag == 1) return;  // diagnostic: metadata + DMA + row table only
-  if constexpr (kRuns) {
-    // value runs: one unit of <= 64 whole chunks of one row per wave iteration
-    const uint32_t nunit = R.nunit, nbnd = R.nbnd;
-    uint8_t* const varena = P.val_arena + vb0;
-    for (uint32_t u = tid >> 6; u < nunit; u += kNT / 64) {
-      const uint32_t c0 = __builtin_amdgcn_readfirstlane(R.unit[0][u]);
-      const uint32_t sbyte = __builtin_amdgcn_readfirstlane(R.unit[1][u]);
-      const uint32_t cnt = __builtin_amdgcn_readfirstlane(R.unit[2][u]);
-      if (lane < cnt) {
-        const uint32_t line = (sbyte >> 4) + lane;
-        const uint4 w = funnel_u(stage[line], stage[line + 1], sbyte & 15);
-        *reinterpret_cast<uint4*>(varena + (uint64_t(c0 + lane) << 4)) = w;
-      }
-    }
-    // keys and the boundary value chunks: per-lane lookup
-    for (uint32_t j = tid; j < nk + nbnd; j += kNT) {
-      const uint32_t reg = j >= nk;
-      const uint32_t bv = reg ? R.bnd[j - nk] : 0u;
-      if (reg && j > nk && (bv >> 8) == (R.bnd[j - nk - 1] >> 8)) continue;
-      const uint32_t X0 = reg ? vx0 : kx0, X1 = reg ? vx1 : kx1;
-      const uint32_t x = reg ? (bv >> 8) << 4 : ((kx0 >> 4) + j) << 4;
-      const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
-      const uint32_t* pre = R.pre[reg];
-      const uint32_t* sb = R.sb[reg];
-      uint32_t r = reg ? (bv & 255u) : uint32_t(gt[0][(lo >> 6) - (X0 >> 6)]);
-      while (r < lastr && pre[r + 1] <= lo) ++r;
-      uint8_t* dst = (reg ? P.val_arena + vb0 : P.key_arena + kb0) + x;
-      const uint32_t dend = min(hi, pre[rows]);
-      uint4 out = make_uint4(0, 0, 0, 0);
-      for (uint32_t d = lo; d < dend; ++r) {
-        const uint32_t e = min(dend, pre[r + 1]);
-        if (e > d) {
-          out = merge_bytes(out, load16_lds_b128(stage, sb[r] + x + sbias), int32_t(d - x),
-                            int32_t(e - x));
-          d = e;
-        }
-      }
-      if (lo == x && hi == x + 16)
-        *reinterpret_cast<uint4*>(dst) = out;
-      else
-        store_partial(dst, out, lo - x, hi - x);
-    }
-  } else if constexpr (kDirect) {
-    constexpr uint32_t kU = (kT / 16 + 8 + kNT - 1) / kNT;  // chunk slots per lane
-    uint4 v[kU];
-    uint32_t xs[kU], los[kU], his[kU], regs[kU];
-    bool slow[kU];
-#pragma unroll
-    for (uint32_t u = 0; u < kU; ++u) {  // every load issued before any store
-      const uint32_t j = tid + u * kNT;
-      his[u] = 0;
-      los[u] = 0;
-      slow[u] = false;
-      v[u] = make_uint4(0, 0, 0, 0);
-      if (j >= nk + nv) continue;
-      const uint32_t reg = j >= nk;
-      const uint32_t X0 = reg ? vx0 : kx0, X1 = reg ? vx1 : kx1;
-      const uint32_t x = ((X0 >> 4) + (reg ? j - nk : j)) << 4;
-      const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
-      const uint32_t* pre = R.pre[reg];
-      uint32_t r = gt[reg][(lo >> 6) - (X0 >> 6)];
-      while (r < lastr && pre[r + 1] <= lo) ++r;
-      xs[u] = x;
-      los[u] = lo;
-      his[u] = hi;
-      regs[u] = reg | (r << 1);
-      if (lo == x && hi == x + 16 && pre[r + 1] >= x + 16)
-        v[u] = *reinterpret_cast<const uint4*>(P.seg + off + R.sb[reg][r] + x);
-      else
-        slow[u] = true;
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < kU; ++u)
-      if (slow[u])
-        v[u] = tile_chunk_pieces(P.seg, P.seg_bytes, off, R.pre[regs[u] & 1], R.sb[regs[u] & 1],
-                                 rows, regs[u] >> 1, xs[u], los[u], his[u]);
-#pragma unroll
-    for (uint32_t u = 0; u < kU; ++u) {
-      if (his[u] <= los[u]) continue;
-      uint8_t* dst = ((regs[u] & 1) ? P.val_arena + vb0 : P.key_arena + kb0) + xs[u];
-      if (los[u] == xs[u] && his[u] == xs[u] + 16)
-        *reinterpret_cast<uint4*>(dst) = v[u];
-      else
-        store_partial(dst, v[u], los[u] - xs[u], his[u] - xs[u]);
-    }
-  } else
-  for (uint32_t j = tid; j < nk + nv; j += kNT) {
+
+// A destination chunk of a tile whose owned bytes [lo, hi) span rows or
+// padding: each row's piece from a global window (rare; kept out of line).
+__device__ __noinline__ uint4 tile_chunk_pieces(const uint8_t* seg, uint64_t seg_bytes, uint64_t off,
+                                                const uint32_t* pre, const uint32_t* sb,
+                                                uint32_t rows, uint32_t r, uint32_t x,
+                                                uint32_t lo, uint32_t hi) {
+  return chunk_bytes(pre, sb, rows, r, x, lo, hi,
+                     [&](uint32_t s) { return window16(seg, seg_bytes, int64_t(off + s)); });
+}
+
+// The round-5 extent: no stage extension (every form without the line cut).
+template <uint32_t kT>
+__device__ __forceinline__ TileExtent tile_extent_r5(const TileBlock& B) {
+  TileExtent X = tile_extent<kT>(B);
+  if (!X.last_tile) X.np -= kLineExt / 16;
+  return X;
+}
+
+// The per-chunk store (d3-d5, d8): every key and value chunk looked up per
+// lane through the two granule tables.  kDiag 4: no stores; 5: no data reads.
+template <uint32_t kNT, int kDiag, class Rows>
+__device__ __forceinline__ void chunk_store(const CopyParams& P, const TileBlock& B,
+                                            const TileExtent& X, const Rows& R,
+                                            const uint8_t* gtk, const uint8_t* gtv,
+                                            const uint4* stage, const TileOwned& O) {
+  const uint32_t nk = O.kx1 > O.kx0 ? ((O.kx1 + 15) >> 4) - (O.kx0 >> 4) : 0u;
+  const uint32_t nv = O.vx1 > O.vx0 ? ((O.vx1 + 15) >> 4) - (O.vx0 >> 4) : 0u;
+  const uint32_t sbias = uint32_t(int64_t(B.off) - X.A);
+  for (uint32_t j = threadIdx.x; j < nk + nv; j += kNT) {
     const uint32_t reg = j >= nk;
-    const uint32_t X0 = reg ? vx0 : kx0, X1 = reg ? vx1 : kx1;
+    const uint32_t X0 = reg ? O.vx0 : O.kx0, X1 = reg ? O.vx1 : O.kx1;
     const uint32_t x = ((X0 >> 4) + (reg ? j - nk : j)) << 4;
     const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
     const uint32_t* pre = R.pre[reg];
     const uint32_t* sb = R.sb[reg];
-    uint32_t r = gt[reg][(lo >> 6) - (X0 >> 6)];
-    while (r < lastr && pre[r + 1] <= lo) ++r;
-    uint8_t* dst = (reg ? P.val_arena + vb0 : P.key_arena + kb0) + x;
+    uint32_t r = (reg ? gtv : gtk)[(lo >> 6) - (X0 >> 6)];
+    while (r < X.lastr && pre[r + 1] <= lo) ++r;
+    uint8_t* dst = (reg ? P.val_arena + B.vb0 : P.key_arena + B.kb0) + x;
     if (lo == x && hi == x + 16 && pre[r + 1] >= x + 16) {  // the common chunk: inside row r
       if constexpr (kDiag == 5) {  // diagnostic: the lookup, no data read
         *reinterpret_cast<uint4*>(dst) = make_uint4(r, x, 0, 0);
@@ -742,50 +511,315 @@ __device__ __forceinline__ void tile_pass_diag(const CopyParams& P, uint32_t tpb
       *reinterpret_cast<uint4*>(dst) = w;
       continue;
     }
-    const uint32_t dend = min(hi, pre[rows]);
-    uint4 out = make_uint4(0, 0, 0, 0);
-    for (uint32_t d = lo; d < dend; ++r) {
-      const uint32_t e = min(dend, pre[r + 1]);
-      if (e > d) {  // bytes [d, e) of the chunk from row r
-        out = merge_bytes(out, load16_lds_b128(stage, sb[r] + x + sbias), int32_t(d - x),
-                          int32_t(e - x));
-        d = e;
-      }
-    }
+    const uint4 out = chunk_bytes(pre, sb, X.rows, r, x, lo, hi, [&](uint32_t s) {
+      return load16_lds_b128(stage, s + sbias);
+    });
     if (lo == x && hi == x + 16)
       *reinterpret_cast<uint4*>(dst) = out;
     else
       store_partial(dst, out, lo - x, hi - x);
   }
-  if constexpr (kProbe) {
+}
+
+// The direct store (d6): no LDS stage, one unaligned global load per chunk,
+// every load issued before any store.
+template <uint32_t kT, uint32_t kNT, class Rows>
+__device__ __forceinline__ void direct_store(const CopyParams& P, const TileBlock& B,
+                                             const TileExtent& X, const Rows& R,
+                                             const uint8_t* gtk, const uint8_t* gtv,
+                                             const TileOwned& O) {
+  constexpr uint32_t kU = (kT / 16 + 8 + kNT - 1) / kNT;  // chunk slots per lane
+  const uint32_t nk = O.kx1 > O.kx0 ? ((O.kx1 + 15) >> 4) - (O.kx0 >> 4) : 0u;
+  const uint32_t nv = O.vx1 > O.vx0 ? ((O.vx1 + 15) >> 4) - (O.vx0 >> 4) : 0u;
+  uint4 v[kU];
+  uint32_t xs[kU], los[kU], his[kU], regs[kU];
+  bool slow[kU];
+#pragma unroll
+  for (uint32_t u = 0; u < kU; ++u) {
+    const uint32_t j = threadIdx.x + u * kNT;
+    his[u] = 0;
+    los[u] = 0;
+    slow[u] = false;
+    v[u] = make_uint4(0, 0, 0, 0);
+    if (j >= nk + nv) continue;
+    const uint32_t reg = j >= nk;
+    const uint32_t X0 = reg ? O.vx0 : O.kx0, X1 = reg ? O.vx1 : O.kx1;
+    const uint32_t x = ((X0 >> 4) + (reg ? j - nk : j)) << 4;
+    const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
+    const uint32_t* pre = R.pre[reg];
+    uint32_t r = (reg ? gtv : gtk)[(lo >> 6) - (X0 >> 6)];
+    while (r < X.lastr && pre[r + 1] <= lo) ++r;
+    xs[u] = x;
+    los[u] = lo;
+    his[u] = hi;
+    regs[u] = reg | (r << 1);
+    if (lo == x && hi == x + 16 && pre[r + 1] >= x + 16)
+      v[u] = *reinterpret_cast<const uint4*>(P.seg + B.off + R.sb[reg][r] + x);
+    else
+      slow[u] = true;
+  }
+#pragma unroll
+  for (uint32_t u = 0; u < kU; ++u)
+    if (slow[u])
+      v[u] = tile_chunk_pieces(P.seg, P.seg_bytes, B.off, R.pre[regs[u] & 1], R.sb[regs[u] & 1],
+                               X.rows, regs[u] >> 1, xs[u], los[u], his[u]);
+#pragma unroll
+  for (uint32_t u = 0; u < kU; ++u) {
+    if (his[u] <= los[u]) continue;
+    uint8_t* dst = ((regs[u] & 1) ? P.val_arena + B.vb0 : P.key_arena + B.kb0) + xs[u];
+    if (los[u] == xs[u] && his[u] == xs[u] + 16)
+      *reinterpret_cast<uint4*>(dst) = v[u];
+    else
+      store_partial(dst, v[u], los[u] - xs[u], his[u] - xs[u]);
+  }
+}
+
+// Every cut between two tiles of a block moves up to a 64-byte sector of the
+// arena, so no destination sector is shared by two tiles; the few bytes this
+// adds to the tile before the cut come from global windows when they lie past
+// its stage.  (kKeyRound false: key cuts left as they are.)
+template <bool kKeyRound>
+__device__ __forceinline__ void sector_cuts(const TileBlock& B, const TileExtent& X, TileCuts& C) {
+  auto sector_up = [](uint32_t Y, uint64_t base, uint32_t tot) -> uint32_t {
+    const uint32_t end = uint32_t(round16(tot));
+    const uint32_t Ys = uint32_t(((base + Y + 63) & ~uint64_t(63)) - base);
+    return Ys > end ? end : Ys;
+  };
+  if (B.t != 0) {
+    if (kKeyRound) C.x[0] = sector_up(C.x[0], B.kb0, C.KT);
+    C.x[2] = sector_up(C.x[2], B.vb0, C.VT);
+  }
+  if (!X.last_tile) {
+    if (kKeyRound) C.x[1] = sector_up(C.x[1], B.kb0, C.KT);
+    C.x[3] = sector_up(C.x[3], B.vb0, C.VT);
+  }
+  C.x[0] = min(C.x[0], C.x[1]);
+  C.x[2] = min(C.x[2], C.x[3]);
+}
+
+// Row pieces of the owned value range: [a, e) = row r's bytes in [X2, X3).
+// Runs: the whole 64-byte sectors inside a piece (and before Yv1, the
+// unrounded value cut at P1: value bytes before it have their sources in this
+// tile's stage), in units of <= 64 chunks -- one wave store writes whole
+// sectors.  Every other sector a piece touches is a mixed sector: its four
+// chunks are assembled by four adjacent lanes and stored by one instruction.
+template <class Rows>
+__device__ __forceinline__ void sector_value_units(const TileBlock& B, const TileExtent& X,
+                                                   const TileLane& W, const TileCuts& C,
+                                                   uint32_t Yv1, Rows& R) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t vb0 = B.vb0;
+  const uint32_t a = max(W.vp, C.x[2]), e = min(W.vp + W.v, C.x[3]);
+  const bool piece = W.live && W.v && a < e;
+  const uint64_t va = vb0 + a, ve = vb0 + min(e, Yv1);
+  const uint64_t s0 = (va + 63) & ~uint64_t(63), s1 = ve & ~uint64_t(63);
+  const bool run = piece && s1 > s0;
+  const uint32_t cs = run ? uint32_t((s0 - vb0) >> 4) : 0u;
+  const uint32_t wc = run ? uint32_t((s1 - s0) >> 4) : 0u;
+  const uint32_t nu = (wc + 63) >> 6;
+  const uint32_t ui = wave_scan_dpp(nu);
+  const uint32_t sbias0 = uint32_t(int64_t(B.off) - X.A);
+  for (uint32_t q = 0; q < nu; ++q) {
+    const uint32_t u = ui - nu + q;
+    R.unit[0][u] = cs + 64 * q;
+    R.unit[1][u] = W.vs - W.vp + 16 * (cs + 64 * q) + sbias0;
+    R.unit[2][u] = min(64u, wc - 64 * q);
+  }
+  // mixed sectors, as (sector - the region's first sector) << 8 | the
+  // lowest row with bytes in it (rows in order, head before tail; equal
+  // neighbours skipped by the consumer)
+  const uint64_t vs0 = vb0 >> 6;
+  const uint32_t hsec = uint32_t(((vb0 + a) >> 6) - vs0);
+  const uint32_t tsec = uint32_t(((vb0 + e - 1) >> 6) - vs0);
+  const bool need_h = piece && (!run || s0 > va);
+  const bool need_t = piece && (run ? s1 < vb0 + e : tsec != hsec);
+  const uint32_t nme = uint32_t(need_h) + uint32_t(need_t);
+  const uint32_t mi = wave_scan_dpp(nme) - nme;
+  if (need_h) R.bnd[mi] = (hsec << 8) | lane;
+  if (need_t) R.bnd[mi + uint32_t(need_h)] = (tsec << 8) | lane;
+  const uint32_t nunit = __builtin_amdgcn_readlane(ui, 63);
+  const uint32_t nmix = __builtin_amdgcn_readlane(mi + nme, 63);
+  if (lane == 0) {
+    R.nbnd = nmix;
+    R.nunit = nunit;
+  }
+}
+
+// Keys (from the first chunk of the range's first sector, so each wave store
+// covers whole sectors) and the mixed value sectors, four lanes each: per-lane
+// lookup; sources past the stage from global windows.
+template <uint32_t kNT, bool kNoKeys, class Rows>
+__device__ __forceinline__ void sector_store(const CopyParams& P, const TileBlock& B,
+                                             const TileExtent& X, const Rows& R,
+                                             const uint8_t* gt, const uint4* stage,
+                                             const TileOwned& O) {
+  const uint32_t nk = O.kx1 > O.kx0 ? ((O.kx1 + 15) >> 4) - (O.kx0 >> 4) : 0u;
+  const uint32_t sbias = uint32_t(int64_t(B.off) - X.A);
+  const uint32_t kc0 = O.kx0 >> 4;
+  const uint32_t kph = uint32_t(((B.kb0 >> 4) + kc0) & 3u);
+  const uint32_t nk4 = nk ? (kph + nk + 3) & ~3u : 0u;
+  const uint32_t vph = uint32_t(B.vb0 & 63);
+  for (uint32_t j = threadIdx.x; j < nk4 + 4 * O.nbnd; j += kNT) {
+    const uint32_t reg = j >= nk4;
+    if (kNoKeys && !reg) continue;
+    uint32_t r;
+    int32_t xs;
+    if (reg) {
+      const uint32_t ei = (j - nk4) >> 2;
+      const uint32_t bv = R.bnd[ei];
+      if (ei && (bv >> 8) == (R.bnd[ei - 1] >> 8)) continue;
+      xs = int32_t((bv >> 8) * 64u) - int32_t(vph) + int32_t(16 * ((j - nk4) & 3u));
+      r = bv & 255u;
+    } else {
+      xs = int32_t(16 * (kc0 + j)) - int32_t(16 * kph);
+      r = 0;
+    }
+    const uint32_t X0 = reg ? O.vx0 : O.kx0, X1 = reg ? O.vx1 : O.kx1;
+    if (xs + 16 <= int32_t(X0) || xs >= int32_t(X1)) continue;
+    const uint32_t x = uint32_t(xs);
+    const uint32_t lo = max(x, X0), hi = min(x + 16, X1);
+    const uint32_t* pre = R.pre[reg];
+    const uint32_t* sb = R.sb[reg];
+    if (!reg) r = uint32_t(gt[(lo >> 6) - (X0 >> 6)]);
+    while (r < X.lastr && pre[r + 1] <= lo) ++r;
+    uint8_t* dst = (reg ? P.val_arena + B.vb0 : P.key_arena + B.kb0) + x;
+    const uint4 out = chunk_bytes(pre, sb, X.rows, r, x, lo, hi, [&](uint32_t s) {
+      return (((s + sbias) >> 4) + 1 < X.np) ? load16_lds_b128(stage, s + sbias)
+                                             : window16(P.seg, P.seg_bytes, int64_t(B.off) + s);
+    });
+    if (lo == x && hi == x + 16)
+      *reinterpret_cast<uint4*>(dst) = out;
+    else
+      store_partial(dst, out, lo - x, hi - x);
+  }
+}
+
+// The product's key and boundary-chunk store with output classes left out:
+// 4 key chunks, 8 boundary value chunks, 16 partial chunks.
+template <uint32_t kNT, uint32_t kSkip, class Rows>
+__device__ __forceinline__ void skip_store_chunks(const CopyParams& P, const TileBlock& B,
+                                                  const TileExtent& X, const Rows& R,
+                                                  const uint8_t* gt, const uint4* stage,
+                                                  const TileOwned& O) {
+  const uint32_t nk = O.kx1 > O.kx0 ? ((O.kx1 + 15) >> 4) - (O.kx0 >> 4) : 0u;
+  for (uint32_t j = threadIdx.x; j < nk + O.nbnd; j += kNT) {
+    if ((kSkip & 4) && j < nk) continue;
+    if ((kSkip & 8) && j >= nk) continue;
+    TileChunk c;
+    if (!tile_chunk(P, B, X, R, gt, stage, O, nk, j, c)) continue;
+    if (c.lo == 0 && c.hi == 16)
+      *reinterpret_cast<uint4*>(c.dst) = c.out;
+    else if (!(kSkip & 16))
+      store_partial(c.dst, c.out, c.lo, c.hi);
+  }
+}
+
+// Every form but d0 and d9 (the product's tile_pass): the product's sequence
+// with the phases the form alters.
+// Forms d32 + kSkip -- output classes left unwritten, to attribute the pass's
+// HBM write traffic: 1 the SoA row index, 2 value runs, 4 key chunks, 8
+// boundary value chunks, 16 partial chunks; other cuts: 64 the round-5 cuts
+// (no line cut, no stage extension); 128 whole 64-byte sectors per store
+// (+ 256 key cuts unrounded, + 512 the stage extension).  d32 is the product's
+// sequence.
+// Forms d1-d8, all on the round-5 cuts: 1 no chunk pass, 2 no DMA, 3 phase
+// probe of the per-chunk form, 4 (+ no stores), 5 (+ no data reads), 6 direct
+// unaligned global loads, 7 phase probe of the value-run form, 8 the per-chunk
+// form (every chunk looked up per lane).
+template <uint32_t kT, uint32_t kNT, bool kXcd, uint32_t kDiag>
+__device__ __forceinline__ void tile_pass_diag(const CopyParams& P, uint32_t tpb, uint32_t ntile) {
+  constexpr uint32_t kSkip = kDiag >= 32 ? kDiag - 32 : 64u;
+  constexpr bool kDirect = kDiag == 6;  // no LDS stage
+  constexpr bool kChunk = (kDiag >= 3 && kDiag <= 5) || kDiag == 8;
+  constexpr bool kRuns = !kChunk && !kDirect;
+  constexpr bool kProbe = (kDiag >= 3 && kDiag <= 5) || kDiag == 7;
+  constexpr bool kSector = (kSkip & 128) != 0;
+  constexpr bool kLineCut = !(kSkip & 64) && !kSector;
+  constexpr bool kExt = kLineCut || (kSkip & 512);
+  __shared__ TileRows<kT> R;
+  __shared__ uint8_t gt[kRuns ? 1 : 2][kT / 64 + 8];  // [key, value] granule tables
+  __shared__ uint4 stage[(kT + (kExt ? kLineExt : 0)) / 16 + 4];
+  const uint32_t L = tile_index<kXcd>();
+  if (L >= ntile) return;
+  uint64_t T[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kProbe: phase timestamps
+  if constexpr (kProbe) T[0] = __builtin_amdgcn_s_memrealtime();
+  uint32_t rec, kl;
+  const TileBlock B = tile_block(P, L, tpb, rec, kl);
+  if constexpr (kProbe) T[1] = __builtin_amdgcn_s_memrealtime();
+  if (tile_idle<kT>(P, B)) {
+    block_outputs(P, B);
+    return;
+  }
+  const TileExtent X = kExt ? tile_extent<kT>(B) : tile_extent_r5<kT>(B);
+  if constexpr (kDiag != 2 && !kDirect) tile_dma<kNT>(P, B, X, stage);
+  if constexpr (kProbe) T[2] = __builtin_amdgcn_s_memrealtime();
+  if (threadIdx.x < 64) {
+    const TileLane W = tile_row_table(B, X, rec, kl, R);
+    if (!P.index_only) {
+      TileCuts C = tile_owned_ranges(W, X);
+      if constexpr (kLineCut) tile_line_cut(B, X, W, C);
+      const uint32_t Yv1 = C.x[3];
+      if constexpr (kSector) sector_cuts<!(kSkip & 256)>(B, X, C);
+      tile_put_cuts(C, R);
+      tile_granules(X, W.live, W.kp, W.k, C.x[0], C.x[1], gt[0]);
+      // the value-run forms need the key table only (a 4 KiB value is 64
+      // granules, a serial per-lane loop)
+      if constexpr (kSector)
+        sector_value_units(B, X, W, C, Yv1, R);
+      else if constexpr (kRuns)
+        tile_value_units(B, X, W, C, R);
+      else
+        tile_granules(X, W.live, W.vp, W.v, C.x[2], C.x[3], gt[1]);
+    }
+    tile_index_rows(P, B, W);
+  }
+  if constexpr (kProbe) T[3] = __builtin_amdgcn_s_memrealtime();
+  if (P.index_only) {
+    block_outputs(P, B);
+    return;
+  }
+  tile_wait_stage();
+  if constexpr (kProbe) T[4] = __builtin_amdgcn_s_memrealtime();
+  if constexpr ((kSkip & 1) != 0)
+    block_outputs(P, B);
+  else
+    tile_row_index(P, B, X, R);
+  if (kDiag == 1) return;  // diagnostic: metadata + DMA + row table only
+  const TileOwned O = tile_owned(R);
+  if constexpr (kRuns && !(kSkip & 2)) tile_store_runs<kNT>(P, B, R, stage, O.nunit);
+  if constexpr (kSector)
+    sector_store<kNT, (kSkip & 4) != 0>(P, B, X, R, gt[0], stage, O);
+  else if constexpr (kRuns)
+    skip_store_chunks<kNT, kSkip>(P, B, X, R, gt[0], stage, O);
+  else if constexpr (kDirect)
+    direct_store<kT, kNT>(P, B, X, R, gt[0], gt[1], O);
+  else
+    chunk_store<kNT, kDiag>(P, B, X, R, gt[0], gt[1], stage, O);
+  if constexpr (kProbe) {  // the last three timestamps; sampled workgroups hand theirs over
     T[5] = __builtin_amdgcn_s_memrealtime();
     __syncthreads();
     T[6] = __builtin_amdgcn_s_memrealtime();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     T[7] = __builtin_amdgcn_s_memrealtime();
-    if ((L & 255) == 0 && tid == 0)
+    if ((L & 255) == 0 && threadIdx.x == 0)
       for (int k = 0; k < 8; ++k) P.vsrc[(L >> 8) * 8 + k] = T[k];
   }
 }
 
-// The tile pass with its diagnostic arms (kDiag), 8 waves per SIMD as the
-// product; arm d9 is the uncapped form (70 registers, 7 waves per SIMD).
-template <uint32_t kT, uint32_t kNT, bool kXcd, int kDiag>
+// 8 waves per SIMD as the product.
+template <uint32_t kT, uint32_t kNT, bool kXcd, uint32_t kDiag>
 __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(kT <= 16384 || kNT == 1024 ? 8 : 4))) void okv_tile_kernel_diag(
     CopyParams P, uint32_t tpb, uint32_t ntile) {
   tile_pass_diag<kT, kNT, kXcd, kDiag>(P, tpb, ntile);
 }
-// The product tile pass with output classes left unwritten (kSkip, see
-// tile_pass): HBM write attribution by PMC, forms d32 + kSkip.
 template <uint32_t kT, uint32_t kNT, bool kXcd, uint32_t kSkip>
 __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8))) void okv_tile_kernel_skip(
     CopyParams P, uint32_t tpb, uint32_t ntile) {
-  tile_pass<kT, kNT, kXcd, kSkip>(P, tpb, ntile);
+  tile_pass_diag<kT, kNT, kXcd, kSkip + 32>(P, tpb, ntile);
 }
+// Form d9: the product's tile_pass without the 8-waves register cap.
 template <uint32_t kT, uint32_t kNT, bool kXcd>
 __global__ __launch_bounds__(kNT) void okv_tile_kernel_w7(CopyParams P, uint32_t tpb,
                                                           uint32_t ntile) {
-  tile_pass_diag<kT, kNT, kXcd, 0>(P, tpb, ntile);
+  tile_pass<kT, kNT, kXcd>(P, tpb, ntile);
 }
-
-

@@ -112,7 +112,10 @@ int ensure_group(okv_ctx* ctx, uint32_t ngroups) {
 template <uint32_t kT, uint32_t kNT, bool kXcd, int kDiag>
 void launch_tile_t(hipStream_t s, const CopyParams& P, uint32_t tpb, uint32_t ntile) {
   const uint32_t grid = kXcd ? ((ntile + 7u) & ~7u) : ntile;
-  if constexpr (kDiag == 9) {
+  if constexpr (kDiag == 0) {  // the product's kernel, at this geometry
+    hipLaunchKernelGGL((okv_tile_kernel<kT, kNT, kXcd>), dim3(grid), dim3(kNT), 0, s, P, tpb,
+                       ntile);
+  } else if constexpr (kDiag == 9) {  // the same without the register cap
     hipLaunchKernelGGL((okv_tile_kernel_w7<kT, kNT, kXcd>), dim3(grid), dim3(kNT), 0, s, P, tpb,
                        ntile);
   } else if constexpr (kDiag >= 32) {
@@ -141,7 +144,7 @@ const TileForm kTileForms[] = {
     // write attribution (okv_tile_kernel_skip): d32 + kSkip
     F(16, 256, 32), F(16, 256, 33), F(16, 256, 34), F(16, 256, 36), F(16, 256, 40),
     F(16, 256, 48), F(16, 256, 63),
-    // value cuts on 128-byte lines (tile_pass kSkip 64); whole 64-byte sectors per store (128)
+    // the round-5 cuts, no line cut (tile_pass_skip kSkip 64); whole 64-byte sectors per store (128)
     F(16, 256, 96), F(16, 256, 160), F(16, 256, 672), F(16, 256, 928)};
 #undef F
 const TileForm* tile_form(uint32_t kib, uint32_t threads, uint32_t diag) {
@@ -151,7 +154,7 @@ const TileForm* tile_form(uint32_t kib, uint32_t threads, uint32_t diag) {
 }
 
 // launch_tile's hook: the form the knobs name (ablate_open has checked that it
-// exists); with none set, the product's geometry through okv_tile_kernel_diag<.., 0>.
+// exists); with none set, the product form (okv_tile_kernel at the product's geometry).
 void ablate_launch_tile(okv_ctx* ctx, const CopyParams& P, const TileGeo& g) {
   const AblateState& A = ctx->ab;
   const TileForm* f = tile_form(A.tile_kib, A.tile_threads, A.tile_diag);

@@ -145,6 +145,31 @@ def test_pack_kernels_are_the_product_form_only():
     assert m.group(0).strip("\n").count("\n") + 1 <= 25
 
 
+def test_tile_pass_is_a_sequence_of_phases():
+    """The product tile pass carries no ablation arm: tile_pass is a short
+    sequence of phase calls with no loop of its own, the helpers only the
+    measured forms use live in okv_decode_ablate.inc, and those forms call the
+    product's phases instead of repeating them (the scalar trip is stated once)."""
+    csrc = os.path.join(ROOT, "objectkv_amd", "csrc")
+    dec = _strip_comments(open(os.path.join(csrc, "okv_decode.hip")).read())
+    for word in ("kSkip", "kSector", "kKeyRound", "kDiag"):
+        assert word not in dec, word
+    for name in ("boundary_chunk", "sweep_handoff", "sweep_safe", "tile_chunk_pieces"):
+        assert not re.search(r"\b" + name + r"\s*\([^;]*\)\s*\{", dec), name
+    m = re.search(r"\n[^\n;{}]*\btile_pass\s*\([^)]*\)\s*\{.*?\n\}", dec, flags=re.S)
+    assert m and "__device__" in m.group(0)
+    assert m.group(0).strip("\n").count("\n") + 1 <= 60
+    assert "for (" not in m.group(0) and "while (" not in m.group(0)
+    trips = {}
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if os.path.isfile(path):
+            n = open(path, errors="replace").read().count('asm volatile("" ::"s"(off)')
+            if n:
+                trips[name] = n
+    assert trips == {"okv_decode.hip": 1}, trips
+
+
 def test_staged_block_machinery_is_stated_once():
     """A block staged in LDS has one byte source (okv_kernels.hpp's Staged), and one
     speculative header walk, walk_staged_to; okv_point_kernel is a short sequence of

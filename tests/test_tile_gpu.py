@@ -47,10 +47,7 @@ def _fill_to(target, kl, rng):
     return shape
 
 
-def test_tile_boundaries(decoder):
-    """Records whose header, key or value straddles a 16 KiB tile edge, and
-    values / whole blocks ending exactly on one (the last tile then owns only
-    the 16-byte padding of its regions)."""
+def _boundary_segment():
     rng = np.random.default_rng(1)
     blocks = []
     for edge in (TILE, 2 * TILE, 3 * TILE):
@@ -60,16 +57,10 @@ def test_tile_boundaries(decoder):
             blocks.append(head + [(20, 1000)] + [(33, 777)] * 3)
     for k in (1, 2, 3, 4):  # blocks ending exactly on a tile edge
         blocks.append(_fill_to(k * TILE, 16, rng))
-    seg, d = _segment(blocks, 2)
-    got = decoder.decode(seg, d)
-    _assert_same_as_oracle(got, seg, d, 0, False)
-    assert (got.status == 0).all()
+    return _segment(blocks, 2)
 
 
-def test_long_keys_and_tiny_values(decoder):
-    """A 60 000-byte key spanning four tiles; 64-row blocks of 0-3 byte
-    values and 0-8 byte keys (many rows per destination chunk and per 64-byte
-    granule of the row lookup); empty keys; a block of empty values only."""
+def _long_key_segment():
     rng = np.random.default_rng(3)
     blocks = [[(60000, 100), (5, 4000)],
               [(65535 - 10, 0)],
@@ -79,7 +70,88 @@ def test_long_keys_and_tiny_values(decoder):
               [(7, 1)] * 64]
     blocks += [[(int(rng.integers(0, 9)), int(rng.integers(0, 4))) for _ in range(64)]
                for _ in range(40)]
-    seg, d = _segment(blocks, 4)
+    return _segment(blocks, 4)
+
+
+def _odd_offset_segments():
+    rng = np.random.default_rng(5)
+    blocks = [_fill_to(int(rng.integers(30000, 65000)), int(rng.integers(8, 200)), rng)
+              for _ in range(60)]
+    for gap in (1, 3, 5, 13):
+        seg, d = _segment(blocks, 6, pad_to=65536, gap=gap)
+        d[-1, 1] = len(seg) - d[-1, 0]  # ends exactly at the segment end
+        yield seg, d
+
+
+def _line_cut_segment():
+    """Blocks of 2-4 tiles whose interior 16 KiB edges meet the value-range
+    cut's cases (okv_decode.hip line_cut: a cut moves up to the next 128-byte
+    line of the value arena when the bytes it adds are staged by the tile
+    before it).  Returns the segment, its descs and the number of such edges."""
+    rng = np.random.default_rng(11)
+    blocks, nedge = [], 0
+    for b in range(192):
+        ntile = 2 + b % 3
+        shape, pos = [], 0
+
+        def fill(target, kl):  # records up to block byte `target`
+            nonlocal pos
+            shape.extend(_fill_to(target - pos, kl, rng))
+            pos = target
+
+        def put(*recs):
+            nonlocal pos
+            shape.extend(recs)
+            pos += sum(6 + kl + vl for kl, vl in recs)
+
+        for e in range(1, ntile):
+            edge, case = e * TILE, nedge % 5
+            nedge += 1
+            if b % 4 == 0 and e == ntile - 1:
+                # the value region ends before the next line: the clamp to round16(VT)
+                fill(edge - 20, 12)
+                put(*[(100, 3)] * 4)
+            elif case == 0:  # a value straight across the edge
+                fill(edge - 1500 - (6 + 16), 16)
+                put((16, 3000))
+            elif case == 1:
+                # a value ending d bytes after the edge, then a long key: the line
+                # lies in the next value, 6 + key + up to 127 bytes further on
+                d = (1, 9, 16, 40, 77, 120)[(nedge // 5) % 6]
+                fill(edge + d - (6 + 16 + 600), 16)
+                put((16, 600), (330 + 10 * ((nedge // 5) % 18), 300))
+            elif case == 2:  # many rows inside one line: the cut stays
+                fill(edge - 900, 16)
+                put(*[(100, int(rng.integers(0, 13))) for _ in range(16)])
+            elif case == 3:  # empty values exactly at the cut
+                fill(edge - 2 * (6 + 30), 16)
+                put((30, 0), (30, 0), (30, 0), (30, 0), (30, 200))
+            else:  # a value ending exactly at the edge, then empty values
+                fill(edge, 16)
+                put((30, 0), (30, 0), (30, 64))
+        if b % 4:
+            fill(int(rng.integers(pos + 600, ntile * TILE - 8)), 16)
+        assert (ntile - 1) * TILE < pos <= ntile * TILE and len(shape) <= 64, (b, pos, len(shape))
+        blocks.append(shape)
+    seg, d = _segment(blocks, 12)
+    return seg, d, nedge
+
+
+def test_tile_boundaries(decoder):
+    """Records whose header, key or value straddles a 16 KiB tile edge, and
+    values / whole blocks ending exactly on one (the last tile then owns only
+    the 16-byte padding of its regions)."""
+    seg, d = _boundary_segment()
+    got = decoder.decode(seg, d)
+    _assert_same_as_oracle(got, seg, d, 0, False)
+    assert (got.status == 0).all()
+
+
+def test_long_keys_and_tiny_values(decoder):
+    """A 60 000-byte key spanning four tiles; 64-row blocks of 0-3 byte
+    values and 0-8 byte keys (many rows per destination chunk and per 64-byte
+    granule of the row lookup); empty keys; a block of empty values only."""
+    seg, d = _long_key_segment()
     got = decoder.decode(seg, d)
     _assert_same_as_oracle(got, seg, d, 0, False)
 
@@ -88,14 +160,27 @@ def test_odd_offsets_and_segment_edges(decoder):
     """Blocks at unaligned offsets (the tile stage's lead-in line starts
     before the block; the first block's before the segment), and the last
     block ending at the segment's last byte."""
-    rng = np.random.default_rng(5)
-    blocks = [_fill_to(int(rng.integers(30000, 65000)), int(rng.integers(8, 200)), rng)
-              for _ in range(60)]
-    for gap in (1, 3, 5, 13):
-        seg, d = _segment(blocks, 6, pad_to=65536, gap=gap)
-        d[-1, 1] = len(seg) - d[-1, 0]  # ends exactly at the segment end
+    for seg, d in _odd_offset_segments():
         got = decoder.decode(seg, d)
         _assert_same_as_oracle(got, seg, d, 0, False)
+
+
+def test_value_cuts_on_arena_lines(decoder):
+    """The value-range cut between two tiles of a block (okv_decode.hip
+    tile_line_cut) at every kind of edge: a value straight across it (the cut
+    moves to the line), a value ending 1-120 bytes after it followed by a
+    330-500 byte key (the line's source on both sides of the staged
+    extension), runs of 0-12 byte values (many rows in one line), empty values
+    at the cut, and value regions ending before the next line; first, middle
+    and last tiles, every residue of the block's arena base in its line."""
+    import objectkv_amd as okv
+    seg, d, nedge = _line_cut_segment()
+    assert d.shape[0] <= 256 and (d[:, 1] == 65536).all() and nedge >= d.shape[0]
+    got = decoder.decode(seg, d)
+    assert decoder.last_path() & okv._lib.PATH_TILE, decoder.last_path()
+    _assert_same_as_oracle(got, seg, d, 0, False)
+    assert (got.status == 0).all()
+    assert {int(v) % 128 for v in got.val_base[:d.shape[0]]} == set(range(0, 128, 16))
 
 
 def test_blocks_past_the_tile_span_and_over_64_rows(decoder):

@@ -2,7 +2,8 @@
 knob set): the arm must be the path taken and its outputs equal the oracle's.
 usage: OKV_ABLATE=1 <knob>=1 python tools/ablate_check.py stream|pieces|small_pieces|onepass
        OKV_ABLATE=1 python tools/ablate_check.py block|block512
-       OKV_ABLATE=1 python tools/ablate_check.py enc_arms   (sets each encode knob itself)"""
+       OKV_ABLATE=1 python tools/ablate_check.py enc_arms   (sets each encode knob itself)
+       OKV_ABLATE=1 python tools/ablate_check.py tile_forms [form ...]  (sets each OKV_TILE form itself)"""
 import os
 import random
 import sys
@@ -105,4 +106,24 @@ elif arm == "enc_arms":
             del os.environ[knob]
         print("  " + " ".join(f"{k}={v}" for k, v in knobs.items()) + ": parity ok", flush=True)
     enc.close()
+elif arm == "tile_forms":
+    # every OKV_TILE form that writes the whole output (the forms that skip work,
+    # d1-d5 and d33-d63, and the probe d7 are not parity forms), on the tile
+    # tests' edge segments; stops at the first form that fails
+    from tests import test_tile_gpu as TT  # noqa: E402
+    cases = [TT._boundary_segment(), TT._long_key_segment(), *TT._odd_offset_segments(),
+             TT._line_cut_segment()[:2]]
+    for form in sys.argv[2:] or (
+            "16xd0", "8xd0", "32xd0", "16xw512d0", "32xw512d0", "4xd0", "64xw1024d0",
+            "64xw512d0", "16xd6", "16xd8", "8xd8", "32xw512d8", "16xd9", "16xd32",
+            "16xd96", "16xd160", "16xd672", "16xd928"):
+        os.environ["OKV_TILE"] = form
+        dec = okv.Decoder(0)
+        del os.environ["OKV_TILE"]
+        for seg, d in cases:
+            got = dec.decode(seg, d)
+            assert dec.last_path() & _lib.PATH_TILE, (form, dec.last_path())
+            TD._assert_same_as_oracle(got, seg, d, 0, False)
+        dec.close()
+        print(f"  OKV_TILE={form}: parity ok on {len(cases)} segments", flush=True)
 print(f"ablation arm {arm}: parity ok")
