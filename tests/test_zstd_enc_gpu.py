@@ -4,7 +4,11 @@ Every case runs at T=3584, D=4096 and at T=61440, D=65536, in host mode and in
 device-pointer mode (the two must give the same bytes), and is checked by three
 decoders -- libzstd on each frame, the device decoder and the C oracle on the file --
 and by a byte-exact rebuild of the file around the device's frames
-(oracle/zstd_ref.zstd_segment with frame_fn).
+(oracle/zstd_ref.zstd_segment with frame_fn).  Every frame must also equal, byte for byte,
+the frame a CPU model of the kernel's parse predicts (tests/zenc_model.py: the candidate
+search, the quarter parse, the list merge and the Raw / Compressed decision restated in
+numpy, the frame bytes written by tests/zenc_main.cpp without sanitizers), so a parse that
+merely round-trips does not pass.
 
 Frame census.  The encoder can emit: Raw_Blocks and Compressed_Blocks; the 1-, 2- and
 3-byte Raw_Literals_Block headers; the 1- and 2-byte Number_of_Sequences forms.  All of
@@ -32,11 +36,13 @@ from oracle import coracle as CO
 from oracle import pyoracle as P
 from oracle import zstd_ref as Z
 from tests import snapshot_cases as SC
+from tests import zenc_cases as ZC
+from tests import zenc_model as M
 
 pytestmark = pytest.mark.gpu
 
 UNIT = _lib.ZSTD_ENC_UNIT
-CONFIGS = [(3584, 4096), (61440, 65536)]
+CONFIGS = ZC.CONFIGS
 ZSTD = okv.sst.COMP_ZSTD
 CENSUS = {"block": set(), "lit": set(), "nseq": set(), "fcs": set()}
 
@@ -48,8 +54,9 @@ def enc():
     e.close()
 
 
-def _raw(rows):
-    return b"".join(struct.pack("<HI", len(k), len(v)) + k + v for k, v in rows)
+_raw = ZC.raw_of
+_text_rows, _random_rows, _closes = ZC.text_rows, ZC.random_rows, ZC.closes
+_periodic, _mixed, PERIODIC, EDGES = ZC.periodic, ZC.mixed, ZC.PERIODIC, ZC.EDGES
 
 
 def _tensors(r):
@@ -154,7 +161,7 @@ def check(enc, decoder, rows, T, D, strict_go=True, compressible=None):
     assert np.array_equal(plain.first_row, got.first_row)
     assert int(got.first_row[nb]) == len(rows)
     # 1a. libzstd on every frame; 3. census and the size bound
-    frames, kinds = [], []
+    frames, kinds, raws = [], [], []
     for b in range(nb):
         off, bs, orig, cs = (int(x) for x in got.descs[b])
         raw = _raw(rows[int(got.first_row[b]):int(got.first_row[b + 1])])
@@ -165,6 +172,10 @@ def check(enc, decoder, rows, T, D, strict_go=True, compressible=None):
         assert cs <= orig + 3 * -(-orig // UNIT) + 18
         kinds += _parse_frame(frame, orig)
         frames.append(frame)
+        raws.append(raw)
+    # 6. the frame is the one the parse means to write: the CPU model's, byte for byte
+    for b, (want_frame, _units) in enumerate(M.model_frames(raws)):
+        assert frames[b] == want_frame, (b, len(raws[b]))
     if compressible is True:
         assert 2 in kinds
     if compressible is False:
@@ -193,35 +204,6 @@ def check(enc, decoder, rows, T, D, strict_go=True, compressible=None):
     return got
 
 
-def _text_rows(n, vlen=59):
-    rows = []
-    for i in range(n):
-        v = ('{"id":%d,"name":"user%d","score":%d,"active":true' %
-             (100000 + 7 * i, 5000 + i, (i * 37) % 1000)).encode()
-        rows.append((b"key%09d" % (i * 3), v.ljust(vlen - 1) + b"}"))
-    return rows
-
-
-def _random_rows(seed, n, vmax):
-    rng = random.Random(seed)
-    return [(b"%08d" % i + rng.randbytes(rng.randint(0, 9)), rng.randbytes(rng.randint(0, vmax)))
-            for i in range(n)]
-
-
-def _closes(rows, T):
-    """strict_go for these rows: Go panics in Close when the last row closed a block."""
-    raw = 0
-    for k, v in rows:
-        raw = 0 if raw >= T else raw
-        raw += 6 + len(k) + len(v)
-    return raw >= T
-
-
-def _periodic(P_, N, seed=5):
-    pat = random.Random(seed * 1000 + P_).randbytes(P_)
-    return [(b"k", (pat * (N // P_ + 1))[:N - 7])]
-
-
 @pytest.mark.parametrize("T,D", CONFIGS)
 def test_text_rows_three_decoders_and_compression(enc, decoder, T, D):
     rows = _text_rows(46)
@@ -241,8 +223,7 @@ def test_random_input_is_raw_blocks(enc, decoder, T, D):
     """Random bytes with nothing to find: one row per block (so the only structured bytes
     of a block are one 6-byte record header), every zstd block a Raw_Block, the size bound
     of the interface met (check() asserts it for every block)."""
-    rng = random.Random(3)
-    rows = [(rng.randbytes(10), rng.randbytes(T + 50 + i)) for i in range(5)]
+    rows = ZC.random_raw(T)
     got = check(enc, decoder, rows, T, D, strict_go=False, compressible=False)
     assert got.n_blocks == 5
     for off, bs, orig, cs in got.descs:
@@ -256,10 +237,6 @@ def test_random_rows_mixed(enc, decoder, T, D):
     check(enc, decoder, rows, T, D, strict_go=not _closes(rows, T))
 
 
-PERIODIC = [(N, P_) for N in (3600, 65000, 200000) for P_ in (1, 7, 64, 222, 1000)] + \
-    [(65000, 30000)]
-
-
 @pytest.mark.parametrize("T,D", CONFIGS)
 @pytest.mark.parametrize("N,P_", PERIODIC)
 def test_periodic_value(enc, decoder, T, D, N, P_):
@@ -271,26 +248,6 @@ def test_periodic_value(enc, decoder, T, D, N, P_):
     print(f"periodic N={N} P={P_}: CompressedSize {cs}; libzstd-1 "
           f"{len(Z.compress(_raw(rows), 1))}, libzstd-3 {len(Z.compress(_raw(rows), 3))}")
     assert got.n_blocks == 1 and cs <= units * P_ + N // 8 + 64
-
-
-def _mixed(n, seed=9):
-    rng = random.Random(seed)
-    half = rng.randbytes((n - 7) // 2)
-    return [(b"k", (half + half + b"x")[:n - 7])]
-
-
-EDGES = {
-    "seven_raw_bytes": lambda: [(b"k", b"")],
-    "unit_minus_1": lambda: _mixed(UNIT - 1),
-    "unit": lambda: _mixed(UNIT),
-    "unit_plus_1": lambda: _mixed(UNIT + 1),
-    "value_200k_random": lambda: [(b"big", random.Random(1).randbytes(200 * 1024))],
-    "value_200k_text": lambda: [(b"a", b"x"), (b"big", _raw(_text_rows(2700))[:200 * 1024])],
-    "zeros_70000": lambda: [(b"z", bytes(70000))],
-    "empty_values": lambda: [(b"k%05d" % i, b"" if i % 3 else b"v%d" % i) for i in range(900)],
-    "small_then_large": lambda: [(b"a%03d" % i, b"ab" * i) for i in range(300)] +
-    [(b"b", bytes(range(256)) * 300)] + [(b"c%03d" % i, b"tail") for i in range(50)],
-}
 
 
 @pytest.mark.parametrize("T,D", CONFIGS)
@@ -311,8 +268,7 @@ def test_edges(enc, decoder, T, D, name):
 def test_block_counts(enc, decoder, T, D, nblocks):
     """One row per block (each row alone reaches the threshold), so the last row closes
     a block: Go panics in Close (strict_go, Q1), the footer is written otherwise."""
-    pat = bytes(range(251))
-    rows = [(b"r%05d" % i, (pat * (T // 251 + 1))[i % 7:i % 7 + T]) for i in range(nblocks)]
+    rows = ZC.block_pattern(T, nblocks)
     got = check(enc, decoder, rows, T, D, strict_go=False, compressible=True)
     assert got.n_blocks == nblocks
     if nblocks == 256:
@@ -455,6 +411,39 @@ def test_compact_zstd(enc, decoder):
     assert all(int(cs) <= int(orig) + 3 * -(-int(orig) // UNIT) + 18
                for _o, _bs, orig, cs in md.descs)
     assert int(md.descs[:, 3].sum()) < int(md.descs[:, 2].sum())  # (keys share prefixes)
+
+
+PARSE = {name: (rows, ok) for name, rows, ok in ZC.parse_fixtures()}
+
+
+@pytest.mark.parametrize("T,D", CONFIGS)
+@pytest.mark.parametrize("name", list(PARSE))
+def test_parse_fixtures(enc, decoder, T, D, name):
+    """The smallest shapes at which a phase of the unit kernel can go wrong (tests/zenc_cases.py);
+    check() holds every frame against the CPU model byte for byte.  That each fixture is the
+    shape it claims to be (which quarters parse, which hash groups form, where matches end,
+    the sequence counts, compressed size - n) is asserted from the model's census without a
+    GPU in tests/test_zstd_enc_model.py."""
+    rows, _ = PARSE[name]
+    check(enc, decoder, rows, T, D, strict_go=not _closes(rows, T))
+
+
+@pytest.mark.parametrize("name,T,D", [(n, T, D) for n, T, D, _ in ZC.writer_cases()])
+def test_writer_options(enc, decoder, name, T, D):
+    """The zstd path at block sizes that are no multiple of 16 (the place kernel's byte
+    stores, the bytewise meta kernel behind an unaligned data area), at tiny thresholds, with
+    multi-unit blocks at D % 16 != 0, and with long FirstKeys read through the row arrays
+    (the meta kernel's byte-store arm in one group of 256 blocks and not in its neighbour)."""
+    rows = {n: r for n, _T, _D, r in ZC.writer_cases()}[name]
+    got = check(enc, decoder, rows, T, D, strict_go=not _closes(rows, T))
+    if D in (1, 100):
+        assert got.data_bytes % 16 != 0, "the meta block is not 16-byte aligned"
+    if T == 70000:
+        assert int(got.descs[:, 2].max()) > 2 * UNIT
+    if name.startswith("long_first_keys"):
+        assert got.n_blocks == len(rows) >= 600
+        g = ZC.meta_group_bytes([rows[int(r)][0] for r in got.first_row[:-1]])
+        assert g[0] > ZC.META_IMAGE and g[1] + 30 <= ZC.META_IMAGE and g[2] > ZC.META_IMAGE
 
 
 def test_census_is_complete(enc, decoder):

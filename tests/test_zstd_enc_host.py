@@ -23,44 +23,15 @@ import pytest
 from oracle import pyoracle as P
 from oracle import zstd_ref as Z
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "objectkv_amd", "csrc")
+from tests.zenc_model import CSRC, LL, ML, build_zenc_main
+from tests.zenc_model import code as _code
+
 BLOCK_MAX = 128 * 1024
-
-# RFC 8878 3.1.1.3.2.1.1: (baseline, extra bits) per code
-LL = [(i, 0) for i in range(16)] + [(16, 1), (18, 1), (20, 1), (22, 1), (24, 2), (28, 2), (32, 3),
-                                    (40, 3), (48, 4), (64, 6), (128, 7), (256, 8), (512, 9),
-                                    (1024, 10), (2048, 11), (4096, 12), (8192, 13), (16384, 14),
-                                    (32768, 15), (65536, 16)]
-ML = [(i + 3, 0) for i in range(32)] + [(35, 1), (37, 1), (39, 1), (41, 1), (43, 2), (47, 2),
-                                        (51, 3), (59, 3), (67, 4), (83, 4), (99, 5), (131, 7),
-                                        (259, 8), (515, 9), (1027, 10), (2051, 11), (4099, 12),
-                                        (8195, 13), (16387, 14), (32771, 15), (65539, 16)]
-
-
-def _code(table, v):
-    return max(c for c, (base, _) in enumerate(table) if base <= v)
-
-
-def _clang():
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    for sub in ("llvm/bin/clang++", "lib/llvm/bin/clang++"):
-        path = os.path.join(rocm, sub)
-        if os.path.exists(path):
-            return path
-    raise AssertionError(f"no clang++ under {rocm}")
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("zenc") / "zenc_main")
-    build = subprocess.run(
-        [_clang(), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-         "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
-         "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "zenc_main.cpp"),
-         "-o", out], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
-    return out
+    return build_zenc_main(str(tmp_path_factory.mktemp("zenc") / "zenc_main"), sanitize=True)
 
 
 WARM = (8, 24, 8)  # gives every frame eight bytes to point back into
