@@ -721,6 +721,62 @@ typedef struct okv_gather_out {
 int okv_gather_rows(okv_ctx *ctx, const okv_merge_src *srcs, uint32_t nsrc, const uint32_t *src,
                     const uint64_t *row, uint64_t n, okv_gather_out *out, uint32_t flags);
 
+/* ======================================================================== *
+ * Batched GetRange merge: every page of a batch of range queries in one launch.
+ * A page is one OKV_MERGE_GETRANGE merge of at most OKV_PAGE_MAX_ROWS rows; one
+ * workgroup runs it in LDS and nothing goes to the host inside the call.
+ * DESIGN.md 24.
+ * ======================================================================== */
+#define OKV_PAGE_MAX_ROWS 2048  /* rows of all streams of one page */
+#define OKV_M_BIG 2             /* okv_pages_out.status: the page has more rows than
+                                   OKV_PAGE_MAX_ROWS; nothing was merged, use okv_merge_rows */
+#define OKV_M_CAPACITY 3        /* n_rows > out_cap: n_rows is set, no row is written */
+
+typedef struct okv_page {      /* one OKV_MERGE_GETRANGE merge; 48 bytes */
+  uint64_t limit;              /* > 0 */
+  uint64_t out_at;             /* first slot of this page in okv_pages_out.src / .row */
+  uint64_t out_cap;            /* slots it may write */
+  uint32_t src_at, nsrc;       /* its streams: srcs[src_at, src_at + nsrc), priority order, nsrc <= 64 */
+  uint32_t bound_at, bound_len;/* its bound in `bounds` (end ascending, start descending), <= 65535 */
+  uint32_t direction;          /* OKV_DIR_* */
+  uint32_t pad;
+} okv_page;
+
+typedef struct okv_pages_out {
+  uint32_t *src;      /* device: srcs index (src_at + stream), iteration order, from out_at */
+  uint64_t *row;      /* device */
+  uint32_t *n_rows;   /* [n_pages] rows returned (as okv_merge_out.n_rows) */
+  uint32_t *n_unique; /* [n_pages] */
+  int32_t  *status;   /* [n_pages] 0, OKV_M_EOF, OKV_M_BIG, OKV_M_CAPACITY */
+} okv_pages_out;
+
+/*
+ * Page i is okv_merge_rows in OKV_MERGE_GETRANGE mode over srcs[src_at, src_at + nsrc):
+ * the same n_rows, n_unique, status and rows, and everything that call relies on (rows
+ * strictly ascending within a stream, non-empty keys, an input with row_lo == row_hi
+ * ignored) carries over.  The rows go to src / row from slot out_at on; src holds the
+ * index into this call's srcs (src_at + stream), so okv_gather_rows over srcs takes the
+ * arrays of the whole batch as they are.  Every slot of [out_at, out_at + out_cap) that
+ * holds no row gets src = 0xffffffff (okv_gather_rows' empty row), its row is not
+ * written: the whole slice when status is OKV_M_EOF, OKV_M_BIG or OKV_M_CAPACITY.  Slots
+ * outside every slice are not touched.  The slices of two pages must not overlap (the
+ * caller's duty); pages may share streams.  A page whose streams hold more than
+ * OKV_PAGE_MAX_ROWS rows gets OKV_M_BIG and the call still returns OKV_OK.
+ * srcs, pages and bounds are host memory always (at most 65535 sources, fewer than 2^32
+ * pages; of a page's pad nothing is read); src and row are device memory always.
+ * flags: without OKV_F_DEVICE_PTRS n_rows, n_unique and status are host memory and the
+ * call synchronises once, at its end; with it they are device memory and, with
+ * OKV_F_ASYNC, the call only enqueues.  n_pages == 0 succeeds and launches nothing.
+ * OKV_E_ARG (nothing is launched): a NULL pointer where one is needed, a page with
+ * nsrc > 64, src_at + nsrc > nsrc of the call, limit == 0, a direction that is no
+ * OKV_DIR_*, bound_at + bound_len > bounds_len, bound_len > 65535, or a source with
+ * row_hi < row_lo.
+ */
+int okv_merge_pages(okv_ctx *ctx, const okv_merge_src *srcs, uint32_t nsrc,
+                    const okv_page *pages, uint32_t n_pages,
+                    const uint8_t *bounds, uint64_t bounds_len,
+                    okv_pages_out *out, uint32_t flags);
+
 /* Per-kernel timing with HIP events recorded on the context stream around
  * each stage of okv_decode_blocks.  okv_profile(ctx, 1) enables and resets;
  * okv_profile_read synchronises the stream and returns the summed

@@ -53,6 +53,9 @@ SYNTH_FIXED, SYNTH_ZIPF = 0, 1
 MERGE_GETRANGE, MERGE_ALL = 0, 1
 DIR_ASC, DIR_DESC = 0, 1
 M_EOF = 1
+# okv_merge_pages (include/okv_sst.h OKV_PAGE_MAX_ROWS, okv_pages_out.status)
+PAGE_MAX_ROWS = 2048
+M_BIG, M_CAPACITY = 2, 3
 
 # exported symbols declared by include/*.h (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -69,7 +72,7 @@ SYMBOLS = [
     "okv_bloom_write_to", "okv_bloom_last_path",
     "okv_index_new", "okv_index_free", "okv_index_info", "okv_get_rows", "okv_get_totals",
     "okv_snap_new", "okv_snap_free", "okv_snap_get_rows", "okv_snap_totals",
-    "okv_seek_rows", "okv_gather_rows",
+    "okv_seek_rows", "okv_gather_rows", "okv_merge_pages",
     "okv_writer_new", "okv_writer_write_row", "okv_writer_close", "okv_writer_data",
     "okv_writer_meta", "okv_writer_num_blocks", "okv_writer_block", "okv_writer_free",
     "okv_writer_set_bloom",
@@ -188,6 +191,19 @@ class GatherOut(C.Structure):
                 ("val_bytes", C.c_uint64)]
 
 
+class Page(C.Structure):
+    """okv_page (include/okv_sst.h)."""
+    _fields_ = [("limit", C.c_uint64), ("out_at", C.c_uint64), ("out_cap", C.c_uint64),
+                ("src_at", C.c_uint32), ("nsrc", C.c_uint32), ("bound_at", C.c_uint32),
+                ("bound_len", C.c_uint32), ("direction", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class PagesOut(C.Structure):
+    """okv_pages_out (include/okv_sst.h)."""
+    _fields_ = [("src", C.c_void_p), ("row", C.c_void_p), ("n_rows", C.c_void_p),
+                ("n_unique", C.c_void_p), ("status", C.c_void_p)]
+
+
 class MergeOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("direction", C.c_int), ("drop_tombstones", C.c_int),
                 ("pad", C.c_int), ("limit", C.c_uint64), ("bound", C.c_void_p),
@@ -288,6 +304,8 @@ def lib():
         "okv_seek_rows": (i32, [p, C.POINTER(SeekSrc), u32, C.POINTER(Rows), p, p, p, p, u32]),
         "okv_gather_rows": (i32, [p, C.POINTER(MergeSrc), u32, p, p, u64,
                                   C.POINTER(GatherOut), u32]),
+        "okv_merge_pages": (i32, [p, C.POINTER(MergeSrc), u32, C.POINTER(Page), u32, p, u64,
+                                  C.POINTER(PagesOut), u32]),
         "okv_writer_new": (p, [u64, u64, i32, i32]),
         "okv_writer_write_row": (i32, [p, p, C.c_size_t, p, C.c_size_t]),
         "okv_writer_close": (i32, [p, i32, C.POINTER(u64), C.POINTER(u64)]),

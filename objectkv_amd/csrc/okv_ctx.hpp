@@ -1,13 +1,14 @@
 // okv_ctx.hpp -- the per-GPU context shared by the decode (okv_decode.hip), encode
 // (okv_encode.hip), zstd (okv_zstd.hip), merge (okv_merge.hip) and batched GetRow
 // (okv_get.hip, okv_snap.hip) translation units, the zstd encoder (okv_zstd_enc.hip) and the
-// range seek and gather (okv_seek.hip).
+// range seek and gather (okv_seek.hip) and the batched GetRange merge (okv_pages.hip).
 // Internal header.
 // Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
 // its capacity and frees itself with its owner; kernels get raw pointers from data().  The
 // owners are okv_ctx (decode), AblateState (the decode ablation arms) and, each defined in its
 // own file behind a forward declaration here and released by okv_close: EncScratch,
-// zst::Scratch, mrg::Scratch, get::Scratch, snap::Scratch, zenc::Scratch and rng::Scratch.
+// zst::Scratch, mrg::Scratch, get::Scratch, snap::Scratch, zenc::Scratch, rng::Scratch and
+// pages::Scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #define OKV_BUF_HIP
@@ -40,6 +41,10 @@ namespace rng {
 struct Scratch;  // okv_seek.hip
 }
 void range_release(okv_ctx* ctx);
+namespace pages {
+struct Scratch;  // okv_pages.hip
+}
+void pages_release(okv_ctx* ctx);
 // okv_bloom.hip: what another translation unit's kernel needs to probe a device filter.
 struct BloomView {
   okv_ctx* ctx;
@@ -187,6 +192,7 @@ struct okv_ctx {
   okv::snap::Scratch* snap = nullptr;  // snapshot GetRows scratch (okv_snap.hip)
   okv::zenc::Scratch* zenc = nullptr;  // zstd encoder scratch (okv_zstd_enc.hip)
   okv::rng::Scratch* range = nullptr;  // seek and gather scratch (okv_seek.hip)
+  okv::pages::Scratch* pages = nullptr;  // batched GetRange merge scratch (okv_pages.hip)
 };
 
 namespace okv {

@@ -2802,6 +2802,7 @@ void okv_close(okv_ctx* ctx) {
   okv::get_release(ctx);
   okv::snap_release(ctx);
   okv::range_release(ctx);
+  okv::pages_release(ctx);
   const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;
   delete ctx;  // every scratch buffer releases itself
   if (owned) (void)hipStreamDestroy(owned);

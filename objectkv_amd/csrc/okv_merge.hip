@@ -28,43 +28,12 @@
 
 #include "okv_ctx.hpp"
 #include "okv_kernels.hpp"
+#include "okv_merge_kernels.hpp"
 #include "okv_sst.h"
 
 namespace okv {
 
 namespace mrg {
-
-struct Src {  // == okv_merge_src
-  const uint8_t* ka;
-  const uint64_t* ko;
-  const uint16_t* kl;
-  const uint8_t* va;
-  const uint64_t* vo;
-  const uint32_t* vl;
-  uint64_t lo, hi;
-  int32_t level;
-  int32_t pad;
-};
-static_assert(sizeof(Src) == sizeof(okv_merge_src), "okv_merge_src layout");
-
-constexpr uint32_t kMaxSrc = 64;
-
-// Go loop outcome per unique key
-enum : uint8_t {
-  kSkip = 0,       // L0 tombstone owner: rolled forward (:316-333)
-  kErr = 1,        // ... and a stream ran out on it: Next() returns io.EOF -> error
-  kBreak = 2,      // outside the range: break before it (:340-347)
-  kEmit = 3,       // appended (:350-354)
-  kEmitBreak = 4,  // appended; a stream ran out on it: the stale cursor ends the loop (:336-338)
-  kEmitErr = 5,    // appended; the stale cursor's owner is an L0 tombstone: io.EOF error
-};
-
-// The first 16 key bytes as two big-endian words, zero padded: with the length
-// as the tie-break, comparing these orders keys as bytes.Compare does, so keys
-// of <= 16 bytes never touch the arenas.
-struct Key16 {
-  uint64_t a, b;
-};
 
 struct Scratch {
   DevBuf<uint64_t> kaddr;   // [N] key address
@@ -85,60 +54,6 @@ struct Scratch {
   DevBuf<uint64_t> d_misc;  // [0] first termination, [1] its code, [2..] per-stream end key index
   PinBuf<uint64_t> h_misc;
 };
-
-__device__ __forceinline__ uint32_t find_src(const uint64_t* __restrict__ base, uint32_t k,
-                                             uint64_t g) {
-  uint32_t lo = 0, hi = k;  // largest i with base[i] <= g
-  while (hi - lo > 1) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (base[m] <= g)
-      lo = m;
-    else
-      hi = m;
-  }
-  return lo;
-}
-
-// Key bytes [off, off + 8) as a big-endian word, bytes past len read as 0;
-// the eight loads are independent (one memory round trip).
-__device__ __forceinline__ uint64_t be_word(const uint8_t* k, uint32_t len, uint32_t off) {
-  uint64_t p = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 8; ++i) p = (p << 8) | (off + i < len ? uint64_t(k[off + i]) : 0ull);
-  return p;
-}
-
-// The first 16 bytes from the aligned line(s) holding them (the second only
-// when the key runs into it: a line holding a valid byte never crosses the
-// allocation), bytes past len zeroed, then byte-swapped to big-endian words.
-__device__ __forceinline__ Key16 be_prefix(const uint8_t* k, uint32_t len) {
-  if (len == 0) return Key16{0, 0};
-  const uintptr_t a = reinterpret_cast<uintptr_t>(k);
-  const uint4* line = reinterpret_cast<const uint4*>(a & ~uintptr_t(15));
-  const uint32_t sh = uint32_t(a & 15), n = len < 16 ? len : 16;
-  const uint4 x = line[0];
-  const uint4 y = sh + n > 16 ? line[1] : make_uint4(0, 0, 0, 0);
-  uint4 v = funnel32(x, y, sh);
-  v.x &= byte_mask(0, int32_t(n), 0);
-  v.y &= byte_mask(0, int32_t(n), 1);
-  v.z &= byte_mask(0, int32_t(n), 2);
-  v.w &= byte_mask(0, int32_t(n), 3);
-  return Key16{__builtin_bswap64(uint64_t(v.x) | (uint64_t(v.y) << 32)),
-               __builtin_bswap64(uint64_t(v.z) | (uint64_t(v.w) << 32))};
-}
-
-// bytes.Compare of two keys given their prefixes, lengths and addresses.
-__device__ __forceinline__ int key_cmp(const Key16& pa, uint32_t la, const uint8_t* ka,
-                                       const Key16& pb, uint32_t lb, const uint8_t* kb) {
-  if (pa.a != pb.a) return pa.a < pb.a ? -1 : 1;
-  if (pa.b != pb.b) return pa.b < pb.b ? -1 : 1;
-  const uint32_t m = la < lb ? la : lb;
-  for (uint32_t i = 16; i < m; i += 8) {
-    const uint64_t x = be_word(ka, la, i), y = be_word(kb, lb, i);
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
 
 }  // namespace mrg
 
@@ -436,25 +351,21 @@ __global__ __launch_bounds__(256) void okv_merge_event_kernel(
         end_here = true;
         jmin = j < jmin ? j : jmin;
       }
-    if (tomb) {
-      e = end_here ? mrg::kErr : mrg::kSkip;
-    } else {
-      const uint8_t* kp = reinterpret_cast<const uint8_t*>(kaddr[g]);
-      const mrg::Key16 bp = mrg::be_prefix(bound, bound_len);
-      const int c = mrg::key_cmp(pfx[g], klen[g], kp, bp, bound_len, bound);
-      const bool out = dir == OKV_DIR_DESC ? c <= 0 : c >= 0;
-      if (out) {
-        e = mrg::kBreak;
-      } else if (!end_here) {
-        e = mrg::kEmit;
-      } else {
-        // the stale cursor of stream jmin sits on this key: its row is the
-        // stream's last in direction
-        const mrg::Src t = src[jmin];
-        const uint64_t rj = dir == OKV_DIR_DESC ? t.lo : t.hi - 1;
-        e = (t.level == 0 && t.vl[rj] == 0) ? mrg::kEmitErr : mrg::kEmitBreak;
-      }
-    }
+    e = mrg::go_outcome(
+        tomb, end_here,
+        [&] {
+          const uint8_t* kp = reinterpret_cast<const uint8_t*>(kaddr[g]);
+          const mrg::Key16 bp = mrg::be_prefix(bound, bound_len);
+          const int c = mrg::key_cmp(pfx[g], klen[g], kp, bp, bound_len, bound);
+          return dir == OKV_DIR_DESC ? c <= 0 : c >= 0;
+        },
+        [&] {
+          // the stale cursor of stream jmin sits on this key: its row is the
+          // stream's last in direction
+          const mrg::Src t = src[jmin];
+          const uint64_t rj = dir == OKV_DIR_DESC ? t.lo : t.hi - 1;
+          return t.level == 0 && t.vl[rj] == 0;
+        });
   }
   ev[d] = e;
   emit[d] = e >= mrg::kEmit ? 1u : 0u;
@@ -473,18 +384,9 @@ __global__ __launch_bounds__(256) void okv_merge_term_kernel(uint64_t nu,
   const uint64_t d = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (d >= nu) return;
   const uint8_t e = ev[d];
-  unsigned long long key = ~0ull;
-  if (e == mrg::kErr) {
-    key = (unsigned long long)(d) << 3 | 5;
-  } else if (e == mrg::kBreak) {
-    key = (unsigned long long)(d) << 3 | 6;
-  } else if (e >= mrg::kEmit) {
-    const uint64_t cnt = uint64_t(escan[d]) + 1;  // emits through d
-    if (cnt == limit || e == mrg::kEmitBreak)
-      key = (unsigned long long)(d + 1) << 3 | 1;
-    else if (e == mrg::kEmitErr)
-      key = (unsigned long long)(d + 1) << 3 | 2;
-  }
+  // (escan[d] + 1: emits through d, read for an emit only)
+  const unsigned long long key =
+      mrg::term_key(e, d, e >= mrg::kEmit ? uint64_t(escan[d]) + 1 : 0, limit);
   if (key != ~0ull) atomicMin(misc, key);
 }
 
@@ -646,12 +548,7 @@ int okv_merge_rows(okv_ctx* ctx, const okv_merge_src* srcs, uint32_t nsrc,
                        opts->limit, reinterpret_cast<unsigned long long*>(m->d_misc.data()));
     OKV_HIP(hipMemcpyAsync(m->h_misc.data(), m->d_misc.data(), 8, hipMemcpyDeviceToHost, s));
     OKV_HIP(hipStreamSynchronize(s));
-    const uint64_t t = m->h_misc.data()[0];
-    if (t != ~0ull) {
-      stop = t >> 3;
-      const uint32_t code = uint32_t(t & 7);
-      if (code == 2 || code == 5) status = OKV_M_EOF;
-    }
+    mrg::term_decode(m->h_misc.data()[0], nu, stop, status);
   }
   // rows emitted before stop = escan[stop]
   OKV_HIP(hipMemcpyAsync(m->h_misc.data(), m->escan.data() + stop, 4, hipMemcpyDeviceToHost, s));

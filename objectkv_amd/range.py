@@ -8,7 +8,8 @@ val_off, val_len: offsets into the segment), for a zstd segment the decode's are
 range each iterator yields, which is an ``okv_merge_rows`` input.  ``gather_rows`` packs
 the rows a merge picked (its ``src`` / ``row`` outputs, still on the device) into two
 arenas.  Key and output arrays are numpy arrays (host mode, staged) or torch tensors on
-the device, as for ``get_rows``.
+the device, as for ``get_rows``.  ``pack_pages`` lays the merges of a batch out as the pages
+of one ``okv_merge_pages`` call (``Decoder.merge_pages_device``).
 """
 from __future__ import annotations
 
@@ -127,6 +128,35 @@ def merge_srcs(sources):
     return arr, len(sources)
 
 
+PAGE_MAX_STREAMS = 64  # okv_page.nsrc
+
+
+def pack_pages(jobs, first_slot=0):
+    """The okv_merge_pages arguments of one batch of GetRange merges (no GPU).
+
+    jobs: dicts with ``ranges`` [(row_lo, row_hi)] per stream, ``lim`` (> 0), ``direction``,
+    ``bound`` (bytes), ``base`` (the index of the job's first stream in the call's srcs: its
+    gather base) and ``cap`` (slots of its slice).  The slices lie one after the other from
+    ``first_slot`` on, every job's (the old path's too) at the sum of the earlier caps.
+    -> (pages: a _lib.Page array, bounds: the bounds back to back, at: each job's slice
+    start, old: the indices of the jobs that are no page -- more than PAGE_MAX_ROWS rows
+    or more than 64 streams -- and stay with okv_merge_rows)."""
+    at, old, fit, blob = [], [], [], bytearray()
+    slot = int(first_slot)
+    for i, j in enumerate(jobs):
+        at.append(slot)
+        slot += int(j["cap"])
+        rows = sum(int(b) - int(a) for a, b in j["ranges"])
+        if rows > _lib.PAGE_MAX_ROWS or len(j["ranges"]) > PAGE_MAX_STREAMS:
+            old.append(i)
+            continue
+        bound = bytes(j["bound"])
+        fit.append(_lib.Page(int(j["lim"]), at[i], int(j["cap"]), int(j["base"]),
+                             len(j["ranges"]), len(blob), len(bound), int(j["direction"]), 0))
+        blob += bound
+    return (_lib.Page * len(fit))(*fit), bytes(blob), at, old
+
+
 class GatherResult:
     """The arrays of okv_gather_out and its totals."""
 
@@ -203,4 +233,5 @@ def gather_rows(owner, sources, src, row, n=None, out=None, arenas=True, key_cap
     return res
 
 
-__all__ = ["ARENA_SPARE", "GatherResult", "ResidentRows", "gather_rows", "merge_srcs", "seek_rows"]
+__all__ = ["ARENA_SPARE", "GatherResult", "PAGE_MAX_STREAMS", "ResidentRows", "gather_rows",
+           "merge_srcs", "pack_pages", "seek_rows"]

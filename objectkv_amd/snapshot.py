@@ -29,7 +29,7 @@ from .sst import COMP_NONE, Decoder, Encoder, OkvError, fetch_metadata
 
 DirectionAscending, DirectionDescending = 0, 1  # segment_row_iter.go:22-25
 _RANGE_STATS = ("seeks", "seek_calls", "gather_calls", "rows_merged", "windows_accepted",
-                "reruns", "rows_gathered")
+                "reruns", "rows_gathered", "merge_calls", "pages_merged")
 _GATHER_SOURCES = 60000  # streams of one okv_gather_rows call (it takes 65535 sources)
 UnboundStart = None  # segment_reader.go:60
 UnboundEnd = b"\xff"  # :62
@@ -516,15 +516,17 @@ class Reader:
         """GetRange for every (start, end, limit, direction) of queries: per query the list
         of KVPair, None (no candidate segment), or the SnapshotError / SnapshotPanic Go's
         GetRange would give (returned, not raised).  One okv_seek_rows call positions every
-        (query, candidate) stream; each query's merge (okv_merge_rows) runs over windows
-        of window_size(limit) rows and is run again over the whole streams only when
-        accept_window refuses its result; one okv_gather_rows packs the rows of the whole
+        (query, candidate) stream; each query's merge runs over windows of
+        window_size(limit) rows -- every page of the batch in one okv_merge_pages call, a
+        merge of more than PAGE_MAX_ROWS rows by okv_merge_rows -- and is run again over
+        the whole streams only when accept_window refuses its result; one okv_gather_rows packs the rows of the whole
         batch on the device and they come back once per batch (the row arrays, the key arena,
         the value arena), not per row.  More than 64 candidates of one query is the merge's
         OKV_E_ARG, as in GetRange.  range_stats counts the call:
         seeks (triples), seek_calls, gather_calls, rows_merged (rows given to merges),
         windows_accepted (queries with a cut stream whose windowed result stood), reruns,
-        rows_gathered.  With range_profile set it also holds seek_ms, merge_ms and gather_ms:
+        rows_gathered, merge_calls (okv_merge_pages and okv_merge_rows calls), pages_merged
+        (merges that went through okv_merge_pages).  With range_profile set it also holds seek_ms, merge_ms and gather_ms:
         device events on the decoder's stream around the three steps."""
         from . import range as RG
         st = self.range_stats = dict.fromkeys(_RANGE_STATS, 0)
@@ -595,23 +597,32 @@ class Reader:
             self._merge_group(group, sources, queries, results, windowed)
 
     def _merge_group(self, jobs, sources, queries, results, windowed):
-        """One merge per job into slices of one device src / row array, then one gather
-        and one copy back.  The gather's sources are the jobs' streams one after the other,
-        so a merge's stream numbers need only the job's base added.  windowed: over the
-        jobs' windows, with the frontier rows added to the gather list; a refused result
-        marks the job for the rerun."""
+        """The jobs' merges into slices of one device src / row array, then one gather and
+        one copy back.  Every job that fits a page (range.pack_pages) is merged by one
+        okv_merge_pages call; the others (more than PAGE_MAX_ROWS rows: usually the whole
+        streams of the rerun) by one okv_merge_rows each.  The gather's sources are the
+        jobs' streams one after the other: a page's src already counts in them, a single
+        merge's needs the job's base added.  A job's slice is its cap slots at a fixed
+        place, the slots it leaves unused are empty rows of the gather.  windowed: over
+        the jobs' windows, with the frontier rows added to the gather list; a refused
+        result marks the job for the rerun."""
         import torch
+        from . import range as RG
         st = self.range_stats
         dev = torch.device("cuda", self.decoder.device)
         extra, gsrc = [], []  # the frontier rows, in front of the merges' rows
         for j in jobs:
+            start, end, _l, j["direction"] = queries[j["qi"]]
+            j["bound"] = _b(end if j["direction"] == DirectionAscending else start)
             j["ranges"] = j["windows"] if windowed else j["streams"]
             j["base"], j["fr_at"] = len(gsrc), len(extra)
             gsrc += [sources[s] for s in j["src"]]
             if windowed:
                 extra += [(j["base"] + i, r) for i, r in enumerate(j["frontier"]) if r is not None]
             j["cap"] = min(sum(b - a for a, b in j["ranges"]), j["lim"])
+            st["rows_merged"] += sum(b - a for a, b in j["ranges"])
         ne = len(extra)
+        pages, bounds, ats, old = RG.pack_pages(jobs, ne)
         total = ne + sum(j["cap"] for j in jobs)
         d_src = torch.full((max(total, 1),), -1, dtype=torch.int32, device=dev)
         d_row = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
@@ -622,26 +633,44 @@ class Reader:
             d_row[:ne] = up[ne:]
         # torch filled the arrays on its stream; the decoder's kernels run on another
         torch.cuda.current_stream(dev).synchronize()
-        pos = ne
         t0 = self._mark()
-        for j in jobs:
-            start, end, _l, direction = queries[j["qi"]]
-            bound = _b(end if direction == DirectionAscending else start)
+        for j, at in zip(jobs, ats):
+            j["at"] = at
+        gsrcs = RG.merge_srcs(gsrc)  # the pages' sources and the gather's
+        if len(pages):
+            srcs = gsrcs[0]
+            for j in jobs:
+                for i, (rec, (a, b)) in enumerate(zip(j["segs"], j["ranges"])):
+                    m = srcs[j["base"] + i]
+                    m.row_lo, m.row_hi, m.level = a, b, rec.Level
+            n_rows, _nu, status = self.decoder.merge_pages_device(
+                gsrcs, pages, bounds, {"src": d_src, "row": d_row})
+            st["merge_calls"] += 1
+            st["pages_merged"] += len(pages)
+            skip = set(old)
+            paged = [j for i, j in enumerate(jobs) if i not in skip]
+            for j, n, s in zip(paged, n_rows.tolist(), status.tolist()):
+                if s not in (0, _lib.M_EOF):  # a page fits by pack_pages, its rows by cap
+                    raise OkvError(_lib.OKV_E_ARG, f"okv_merge_pages: page status {s}")
+                j["eof"] = s == _lib.M_EOF
+                j["n"] = 0 if j["eof"] else n
+        for i in old:
+            j = jobs[i]
             srcs = [(sources[s].t, a, b, rec.Level)
                     for s, rec, (a, b) in zip(j["src"], j["segs"], j["ranges"])]
-            st["rows_merged"] += sum(b - a for a, b in j["ranges"])
-            out = {"src": d_src[pos:pos + j["cap"]], "row": d_row[pos:pos + j["cap"]]}
-            mo = self.decoder.merge_device(srcs, _lib.MERGE_GETRANGE, direction, j["lim"], bound,
-                                           out=out, row_cap=j["cap"])
+            at = j["at"]
+            out = {"src": d_src[at:at + j["cap"]], "row": d_row[at:at + j["cap"]]}
+            mo = self.decoder.merge_device(srcs, _lib.MERGE_GETRANGE, j["direction"], j["lim"],
+                                           j["bound"], out=out, row_cap=j["cap"])
+            st["merge_calls"] += 1
             j["eof"] = mo.status == _lib.M_EOF
             j["n"] = 0 if j["eof"] else int(mo.n_rows)
-            j["at"] = pos
             if j["n"] and j["base"]:  # the merge counts its inputs from 0
-                d_src[pos:pos + j["n"]] += j["base"]
-            pos += j["n"]
+                d_src[at:at + j["n"]] += j["base"]
         torch.cuda.current_stream(dev).synchronize()
         t1 = self._span("merge_ms", t0)
-        g = self._gather(gsrc, d_src, d_row, pos)
+        pos = ne + sum(j["n"] for j in jobs)  # real rows; the gather also sees the empty slots
+        g = self._gather(gsrcs, d_src, d_row, total)
         self._span("gather_ms", t1)
         st["gather_calls"] += 1
         st["rows_gathered"] += pos
@@ -683,8 +712,8 @@ class Reader:
             self.range_stats[name] += since.elapsed_time(e)
         return e
 
-    def _gather(self, sources, d_src, d_row, n):
-        """okv_gather_rows of rows (d_src, d_row)[:n] into the reader's device arenas (grown
+    def _gather(self, srcs, d_src, d_row, n):
+        """okv_gather_rows (sources srcs: range.merge_srcs) of rows (d_src, d_row)[:n] into the reader's device arenas (grown
         when the call reports OKV_E_CAPACITY), copied back -> range.GatherResult on the host.
         The four per-row arrays are one device buffer: one copy brings them back."""
         import torch
@@ -695,7 +724,6 @@ class Reader:
         out = {"key_pos": buf[:8 * m].view(torch.int64), "val_pos": buf[8 * m:16 * m].view(torch.int64),
                "val_len": buf[16 * m:20 * m].view(torch.int32),
                "key_len": buf[20 * m:22 * m].view(torch.int16)}
-        srcs = RG.merge_srcs(sources)
         if self._garena is None:
             self._garena = (torch.empty(1 << 16, dtype=torch.uint8, device=dev),
                             torch.empty(1 << 20, dtype=torch.uint8, device=dev))

@@ -385,6 +385,43 @@ class Decoder:
             raise err
         return mo
 
+    def merge_pages_device(self, srcs, pages, bounds, out: dict, sync=True):
+        """okv_merge_pages: every page an OKV_MERGE_GETRANGE merge, all in one launch.
+
+        srcs: merge_device's [(soa dict, row_lo, row_hi, level)] or a (_lib.MergeSrc
+        array, count) pair; pages: _lib.Page entries (a ctypes array or a list) whose
+        src_at / nsrc index srcs and whose bound_at / bound_len index ``bounds`` (bytes);
+        out: device tensors src (int32) and row (int64), the pages' slices.  Returns
+        (n_rows, n_unique, status) per page as numpy arrays.  With device tensors
+        n_rows / n_unique / status (int32) in ``out`` the call runs in device mode and
+        returns those; sync=False then only enqueues (OKV_F_ASYNC)."""
+        if isinstance(srcs, tuple):
+            arr, nsrc = srcs
+        else:
+            nsrc = len(srcs)
+            arr = (_lib.MergeSrc * max(1, nsrc))()
+            for i, (t, lo, hi, level) in enumerate(srcs):
+                arr[i] = _lib.MergeSrc(_ptr(t["key_arena"]), _ptr(t["key_off"]),
+                                       _ptr(t["key_len"]), _ptr(t["val_arena"]),
+                                       _ptr(t["val_off"]), _ptr(t["val_len"]), int(lo), int(hi),
+                                       int(level), 0)
+        n = len(pages)
+        if isinstance(pages, (list, tuple)):
+            pages = (_lib.Page * max(1, n))(*pages)
+        b = np.frombuffer(bytes(bounds), np.uint8)
+        if "status" in out:
+            per = [out["n_rows"], out["n_unique"], out["status"]]
+            flags = F_DEVICE_PTRS | (0 if sync else F_ASYNC)
+        else:
+            per = [np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32),
+                   np.zeros(max(n, 1), np.int32)]
+            flags = 0
+        po = _lib.PagesOut(_ptr(out.get("src")), _ptr(out.get("row")), *[_ptr(a) for a in per])
+        self._check(lib().okv_merge_pages(self._ctx, arr, nsrc, pages, n,
+                                          _ptr(b) if b.size else None, int(b.size),
+                                          C.byref(po), flags), "okv_merge_pages")
+        return tuple(per) if flags else tuple(a[:n] for a in per)
+
     def plan_device(self, seg_t, seg_bytes, descs_t, nblk, compression=COMP_NONE,
                     index_only=False):
         r, k, v = C.c_uint64(), C.c_uint64(), C.c_uint64()
