@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "okv_bloom_hash.hpp"
+#include "okv_stage.hpp"
 
 struct okv_bloom {
   okv_ctx* ctx = nullptr;
@@ -42,13 +43,6 @@ constexpr uint64_t kMaxK = 4096;            // documented divergence: Go has no 
 // 16 384 rows, 33.0 against 29.2 at 32 768, 82.4 against 47.1 at 100 000; the difference
 // changes sign near 23 000 rows = 4.7e5 locations
 constexpr uint64_t kLdsMinLocations = 1ull << 19;
-
-struct KeyRows {
-  const uint8_t* ka;
-  const uint64_t* ko;
-  const uint16_t* kl;
-  uint64_t n;
-};
 
 // Add, LDS-sliced form.  Workgroup b accumulates slice b % S of the bit array
 // (2^20 bits) in LDS over the rows of group b / S, then ORs its non-zero words into
@@ -141,11 +135,7 @@ int make_filter(okv_ctx* ctx, uint64_t m, uint64_t k, uint64_t length, okv_bloom
   f->ctx = ctx;
   f->m = m, f->k = k, f->length = length;
   f->words = words_needed(length);
-  int ncu = 0;
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) !=
-          hipSuccess || ncu <= 0)
-    ncu = 256;
-  f->n_cu = uint32_t(ncu);
+  f->n_cu = cu_count(ctx);
   if (f->words > (uint64_t(1) << 40)) {  // 8 TiB of words: not a device allocation
     delete f;
     return set_err(ctx, OKV_E_NOMEM, "bloom: filter too large");
@@ -155,38 +145,6 @@ int make_filter(okv_ctx* ctx, uint64_t m, uint64_t k, uint64_t length, okv_bloom
     return rc;
   }
   *out = f;
-  return OKV_OK;
-}
-
-// The key arrays of `rows` as device pointers: the caller's (device mode), or staged
-// into the filter's scratch (host mode; `extra` more bytes follow, at *extra_at).
-int key_rows(okv_ctx* ctx, const okv_bloom* f, const okv_rows* rows, bool dev, size_t extra,
-             KeyRows* R, uint8_t** extra_at) {
-  const uint64_t n = rows->n_rows;
-  if (!rows->key_off || !rows->key_len || (!rows->key_arena && rows->key_arena_bytes))
-    return set_err(ctx, OKV_E_ARG, "bloom: rows");
-  R->n = n;
-  if (dev) {
-    R->ka = rows->key_arena, R->ko = rows->key_off, R->kl = rows->key_len;
-    return OKV_OK;
-  }
-  for (uint64_t i = 0; i < n; ++i)  // (host arrays: a row outside the arena is caught here)
-    if (rows->key_off[i] > rows->key_arena_bytes ||
-        rows->key_len[i] > rows->key_arena_bytes - rows->key_off[i])
-      return set_err(ctx, OKV_E_ARG, "bloom: a key lies outside key_arena_bytes");
-  const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t oko = al(rows->key_arena_bytes), okl = oko + al(n * 8), oex = okl + al(n * 2);
-  if (int rc = reserve(ctx, f->stage, oex + al(extra))) return rc;
-  uint8_t* b = f->stage.data();
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice;
-  if (rows->key_arena_bytes)
-    OKV_HIP(hipMemcpyAsync(b, rows->key_arena, rows->key_arena_bytes, h2d, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(b + oko, rows->key_off, n * 8, h2d, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(b + okl, rows->key_len, n * 2, h2d, ctx->stream));
-  R->ka = b;
-  R->ko = reinterpret_cast<const uint64_t*>(b + oko);
-  R->kl = reinterpret_cast<const uint16_t*>(b + okl);
-  if (extra_at) *extra_at = b + oex;
   return OKV_OK;
 }
 
@@ -301,7 +259,7 @@ int okv_bloom_add_rows(okv_ctx* ctx, okv_bloom* f, const okv_rows* rows, uint32_
   OKV_HIP(hipSetDevice(ctx->device));
   const bool dev = flags & OKV_F_DEVICE_PTRS;
   KeyRows R;
-  if (int rc = key_rows(ctx, f, rows, dev, 0, &R, nullptr)) return rc;
+  if (int rc = stage_keys(ctx, f->stage, rows, dev, "bloom", "rows", nullptr, 0, &R)) return rc;
   const bool lds = (flags & OKV_BLOOM_FORCE_LDS) ||
                    (!(flags & OKV_BLOOM_FORCE_GLOBAL) && lds_fits && n * f->k >= kLdsMinLocations);
   const bloom::Modulus mod = bloom::modulus(f->m);
@@ -340,12 +298,14 @@ int okv_bloom_test_rows(okv_ctx* ctx, const okv_bloom* f, const okv_rows* rows, 
       memset(maybe, 1, n);
   } else {
     KeyRows R;
-    uint8_t* d_maybe = maybe;
-    if (int rc = key_rows(ctx, f, rows, dev, n, &R, dev ? nullptr : &d_maybe)) return rc;
+    stage::Col m{maybe, 1, false, true};
+    if (int rc = stage_keys(ctx, f->stage, rows, dev, "bloom", "rows", &m, 1, &R)) return rc;
     hipLaunchKernelGGL(okv_bloom_test_kernel, dim3(grid_for(f, n)), dim3(kThreads), 0, ctx->stream,
-                       R, f->bits.data(), bloom::modulus(f->m), uint32_t(f->k), f->length, d_maybe);
+                       R, f->bits.data(), bloom::modulus(f->m), uint32_t(f->k), f->length,
+                       m.as<uint8_t>());
     OKV_HIP(hipGetLastError());
-    if (!dev) OKV_HIP(hipMemcpyAsync(maybe, d_maybe, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev)
+      if (int rc = stage_out(ctx, &m, 1, n)) return rc;
   }
   if (!dev || !(flags & OKV_F_ASYNC)) OKV_HIP(hipStreamSynchronize(ctx->stream));
   return OKV_OK;

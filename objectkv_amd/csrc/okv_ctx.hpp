@@ -2,7 +2,9 @@
 // (okv_encode.hip), zstd (okv_zstd.hip), merge (okv_merge.hip) and batched GetRow
 // (okv_get.hip, okv_snap.hip) translation units, the zstd encoder (okv_zstd_enc.hip) and the
 // range seek and gather (okv_seek.hip) and the batched GetRange merge (okv_pages.hip).
-// Internal header.
+// Internal header.  Host mode of the batched calls -- the key check of an okv_rows, the layout
+// of a staging buffer and the copies in and out of it -- is okv_stage.hpp, which a file
+// includes after this one.
 // Ownership: every device or pinned allocation is one DevBuf / PinBuf (okv_buf.hpp) that knows
 // its capacity and frees itself with its owner; kernels get raw pointers from data().  The
 // owners are okv_ctx (decode), AblateState (the decode ablation arms) and, each defined in its
@@ -225,6 +227,15 @@ inline int set_err(okv_ctx* c, int code, const char* what, hipError_t e = hipSuc
     hipError_t e_ = (call);                                       \
     if (e_ != hipSuccess) return set_err(ctx, OKV_E_HIP, #call, e_); \
   } while (0)
+
+// The CUs of the context's device, what the grids are capped by (256 when the query fails).
+inline uint32_t cu_count(okv_ctx* ctx) {
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) !=
+          hipSuccess || ncu <= 0)
+    ncu = 256;
+  return uint32_t(ncu);
+}
 
 // Room for n elements of scratch on the context's stream (Buf::reserve): a
 // compare when there is room already; a failure is OKV_E_HIP with HIP's text.

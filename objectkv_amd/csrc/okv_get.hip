@@ -206,22 +206,11 @@ int run(okv_ctx* ctx, Scratch* s, const okv_index* ix, Params& P, uint64_t* val_
   const uint32_t gk = std::max(1u, std::min(ceil_div(n, kThreads), cap));
   hipLaunchKernelGGL(okv_get_locate_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
-  if (nt) {
-    if (int rc = scan(ctx, s->tsum_in, s->tsum, CntLoad{P.cnt}, nt, P.gscan, nullptr)) return rc;
-    const uint32_t gs = std::max(1u, std::min(ceil_div(std::max(n, nt), kThreads), cap));
-    hipLaunchKernelGGL(okv_get_scatter_kernel, dim3(gs), dim3(kThreads), 0, ctx->stream, P);
-    const uint64_t most = std::min(n, nt);  // touched blocks at most
-    if (ix->max_block <= kSmallCap) {
-      const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(ix->n_cu) * 8));
-      hipLaunchKernelGGL(okv_get_search_kernel<kSmallCap>, dim3(g), dim3(kSearchThreads), 0,
-                         ctx->stream, P);
-    } else {
-      const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(ix->n_cu) * 2));
-      hipLaunchKernelGGL(okv_get_search_kernel<uint32_t(kStage)>, dim3(g), dim3(kSearchThreads), 0,
-                         ctx->stream, P);
-    }
-    OKV_HIP(hipGetLastError());
-  }
+  if (nt)
+    if (int rc = group_and_search(ctx, s, P, n, nt, ix->max_block, ix->n_cu, okv_get_scatter_kernel,
+                                  okv_get_search_kernel<kSmallCap>,
+                                  okv_get_search_kernel<uint32_t(kStage)>))
+      return rc;
   if (int rc = scan(ctx, s->tsum_in, s->tsum, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos)) return rc;
   hipLaunchKernelGGL(okv_get_count_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
@@ -275,11 +264,7 @@ int okv_index_new(okv_ctx* ctx, const okv_block_desc* descs, const uint8_t* fk_a
   ix->ctx = ctx;
   ix->nt = im.descs.size(), ix->nf = n;
   for (const okv_block_desc& d : im.descs) ix->max_block = std::max(ix->max_block, d.block_size);
-  int ncu = 0;
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) !=
-          hipSuccess || ncu <= 0)
-    ncu = 256;
-  ix->n_cu = uint32_t(ncu);
+  ix->n_cu = cu_count(ctx);
   const size_t nt = size_t(ix->nt);
   if (reserve(ctx, ix->descs, nt) || reserve(ctx, ix->file_index, nt) ||
       reserve(ctx, ix->arena, im.arena.size()) || reserve(ctx, ix->off, nt) ||
@@ -329,17 +314,9 @@ int okv_get_rows(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv
   ctx->last_path = 0;
   out->n_found = out->n_fallback = out->val_bytes = out->blocks_searched = 0;
   Scratch* s = scratch(ctx);
-  s->last_arena = out->val_arena != nullptr;
-  s->last_cap = out->val_cap;
-  if (n == 0) {
-    if (s->d_tot.data()) {  // (okv_get_totals reads this call's totals: none)
-      OKV_HIP(hipSetDevice(ctx->device));
-      OKV_HIP(hipMemsetAsync(s->d_tot.data(), 0, sizeof(GetTotals), ctx->stream));
-    }
-    return OKV_OK;
-  }
-  if (!keys->key_off || !keys->key_len || (!keys->key_arena && keys->key_arena_bytes))
-    return set_err(ctx, OKV_E_ARG, "get: keys");
+  if (int rc = open_call(ctx, s, out, n)) return rc;
+  if (n == 0) return OKV_OK;
+  if (int rc = key_err(ctx, stage::check_keys(keys, false), "get", "keys")) return rc;
   if (!out->state || !out->blk_status || !out->entry || !out->val_off || !out->val_len)
     return set_err(ctx, OKV_E_ARG, "get: a NULL output array");
   if (!seg && seg_bytes) return set_err(ctx, OKV_E_ARG, "get: seg");
@@ -362,75 +339,27 @@ int okv_get_rows(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv
   P.val_cap = out->val_cap;
   ctx->last_path = OKV_PATH_GET;
 
-  if (dev) {
-    P.ka = keys->key_arena, P.ko = keys->key_off, P.kl = keys->key_len;
-    P.state = out->state, P.blk_status = out->blk_status, P.entry = out->entry;
-    P.val_off = out->val_off, P.val_len = out->val_len, P.val_arena = out->val_arena;
-    if (int rc = run(ctx, s, ix, P, out->val_pos)) return rc;
-    if (out->val_arena)
-      if (int rc = launch_values(ctx, ix, P)) return rc;
-    if (flags & OKV_F_ASYNC) return OKV_OK;
-    if (int rc = read_totals(ctx, s, out)) return rc;
-    if (out->val_arena && out->val_bytes > out->val_cap)
-      return set_err(ctx, OKV_E_CAPACITY, "get: val_cap too small");
-    return OKV_OK;
-  }
-
-  // host mode: the key arrays in, the per-key arrays out, through one staging buffer
-  for (uint64_t i = 0; i < n; ++i)
-    if (keys->key_off[i] > keys->key_arena_bytes ||
-        keys->key_len[i] > keys->key_arena_bytes - keys->key_off[i])
-      return set_err(ctx, OKV_E_ARG, "get: a key lies outside key_arena_bytes");
-  const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t oko = al(keys->key_arena_bytes), okl = oko + al(n * 8), ost = okl + al(n * 2),
-               obs = ost + al(n * 4), oen = obs + al(n * 4), ovo = oen + al(n * 4),
-               ovl = ovo + al(n * 8), ovp = ovl + al(n * 4), end = ovp + al(n * 8);
-  if (int rc = reserve(ctx, s->stage, end)) return rc;
-  uint8_t* b = s->stage.data();
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  if (keys->key_arena_bytes)
-    OKV_HIP(hipMemcpyAsync(b, keys->key_arena, keys->key_arena_bytes, h2d, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(b + oko, keys->key_off, n * 8, h2d, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(b + okl, keys->key_len, n * 2, h2d, ctx->stream));
-  P.ka = b;
-  P.ko = reinterpret_cast<const uint64_t*>(b + oko);
-  P.kl = reinterpret_cast<const uint16_t*>(b + okl);
-  P.state = reinterpret_cast<int32_t*>(b + ost);
-  P.blk_status = reinterpret_cast<int32_t*>(b + obs);
-  P.entry = reinterpret_cast<uint32_t*>(b + oen);
-  P.val_off = reinterpret_cast<uint64_t*>(b + ovo);
-  P.val_len = reinterpret_cast<uint32_t*>(b + ovl);
-  if (int rc = run(ctx, s, ix, P, reinterpret_cast<uint64_t*>(b + ovp))) return rc;
-  OKV_HIP(hipMemcpyAsync(out->state, b + ost, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->blk_status, b + obs, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->entry, b + oen, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->val_off, b + ovo, n * 8, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->val_len, b + ovl, n * 4, d2h, ctx->stream));
-  if (out->val_pos) OKV_HIP(hipMemcpyAsync(out->val_pos, b + ovp, n * 8, d2h, ctx->stream));
-  if (int rc = read_totals(ctx, s, out)) return rc;  // (synchronises)
-  if (!out->val_arena) return OKV_OK;
-  if (out->val_bytes > out->val_cap) return set_err(ctx, OKV_E_CAPACITY, "get: val_cap too small");
-  if (out->val_bytes == 0) return OKV_OK;
-  if (int rc = reserve(ctx, s->d_val, size_t(out->val_bytes))) return rc;
-  P.val_arena = s->d_val.data();
-  P.val_cap = out->val_bytes;
-  if (int rc = launch_values(ctx, ix, P)) return rc;
-  OKV_HIP(hipMemcpyAsync(out->val_arena, P.val_arena, out->val_bytes, d2h, ctx->stream));
-  OKV_HIP(hipStreamSynchronize(ctx->stream));
-  return OKV_OK;
+  // the per-key arrays: the caller's, or (host mode) staged behind the key arrays
+  stage::Col cols[] = {{out->state, 4, false, true},   {out->blk_status, 4, false, true},
+                       {out->entry, 4, false, true},   {out->val_off, 8, false, true},
+                       {out->val_len, 4, false, true}, {out->val_pos, 8, false, true}};
+  KeyRows R;
+  if (int rc = stage_keys(ctx, s->stage, keys, dev, "get", "keys", cols, 6, &R)) return rc;
+  P.ka = R.ka, P.ko = R.ko, P.kl = R.kl;
+  P.state = cols[0].as<int32_t>(), P.blk_status = cols[1].as<int32_t>();
+  P.entry = cols[2].as<uint32_t>(), P.val_off = cols[3].as<uint64_t>();
+  P.val_len = cols[4].as<uint32_t>();
+  if (dev) P.val_arena = out->val_arena;
+  if (int rc = run(ctx, s, ix, P, cols[5].as<uint64_t>())) return rc;
+  return finish_values(ctx, s, P, out, flags, cols, 6, "get: val_cap too small", read_totals,
+                       [&](const Params& p) { return launch_values(ctx, ix, p); });
 }
 
 int okv_get_totals(okv_ctx* ctx, okv_get_out* out) {
   if (!ctx || !out) return OKV_E_ARG;
   Scratch* s = ctx->get;
   out->n_found = out->n_fallback = out->val_bytes = out->blocks_searched = 0;
-  if (!s || !s->d_tot.data()) return OKV_OK;  // no call has launched anything
-  OKV_HIP(hipSetDevice(ctx->device));
-  if (int rc = reserve(ctx, s->h_tot, 1)) return rc;
-  if (int rc = read_totals(ctx, s, out)) return rc;
-  if (s->last_arena && out->val_bytes > s->last_cap)
-    return set_err(ctx, OKV_E_CAPACITY, "get: val_cap too small");
-  return OKV_OK;
+  return last_totals(ctx, s, out, "get: val_cap too small", read_totals);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // okv_get_kernels.hpp -- the device pieces the batched GetRow of one segment
 // (okv_get.hip) and of a snapshot (okv_snap.hip) are both made of: the three-launch
 // exclusive scan, the grouping of items by block, the search of a staged block and the
-// copy of a value.  An "item" is what lands on a block: a key (okv_get.hip) or a
+// copy of a value; and the host steps both entry points share: the grouping and search
+// launches, the totals, and the values tail of device and host mode (the end of this
+// file).  An "item" is what lands on a block: a key (okv_get.hip) or a
 // (key, segment) pair (okv_snap.hip).  Internal header of those two files; everything
 // has internal linkage, so each file's code object holds its own kernels.
 #pragma once
@@ -9,6 +11,7 @@
 
 #include "okv_bloom_hash.hpp"
 #include "okv_index.hpp"
+#include "okv_stage.hpp"
 
 struct okv_index {
   okv_ctx* ctx = nullptr;
@@ -281,6 +284,79 @@ __device__ __forceinline__ void copy_value(const uint8_t* seg, uint64_t seg_byte
     const int32_t nb = int32_t(min(16u, vl - 16 * c));
     dst[c] = merge_bytes(make_uint4(0, 0, 0, 0), v, 0, nb);
   }
+}
+
+// ---- host: what okv_get_rows and okv_snap_get_rows do alike.  S is the file's Scratch, P
+// its Params, Out its okv_*_out; read is its read_totals (it synchronises). -----------
+// The grouping and the search enqueued (nb > 0): cnt scanned over the nb blocks, the n
+// items scattered into per-block lists, one workgroup per touched block with the stage
+// max_block asks for.
+template <class S, class P>
+int group_and_search(okv_ctx* ctx, S* s, const P& p, uint64_t n, uint64_t nb, uint64_t max_block,
+                     uint32_t n_cu, void (*scatter)(P), void (*search_small)(P),
+                     void (*search_large)(P)) {
+  if (int rc = scan(ctx, s->tsum_in, s->tsum, CntLoad{p.cnt}, nb, p.gscan, nullptr)) return rc;
+  const uint32_t gs = std::max(1u, std::min(ceil_div(std::max(n, nb), kThreads), n_cu * 8));
+  hipLaunchKernelGGL(scatter, dim3(gs), dim3(kThreads), 0, ctx->stream, p);
+  const bool small = max_block <= kSmallCap;
+  const uint64_t most = std::min(n, nb);  // touched blocks at most
+  const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(n_cu) * (small ? 8 : 2)));
+  hipLaunchKernelGGL(small ? search_small : search_large, dim3(g), dim3(kSearchThreads), 0,
+                     ctx->stream, p);
+  OKV_HIP(hipGetLastError());
+  return OKV_OK;
+}
+
+// What a call does first: the arena and capacity okv_*_totals judges by and, for an
+// empty call (n == 0: nothing is launched), this call's totals: none.
+template <class S, class Out>
+int open_call(okv_ctx* ctx, S* s, const Out* out, uint64_t n) {
+  s->last_arena = out->val_arena != nullptr;
+  s->last_cap = out->val_cap;
+  if (n || !s->d_tot.data()) return OKV_OK;
+  OKV_HIP(hipSetDevice(ctx->device));
+  OKV_HIP(hipMemsetAsync(s->d_tot.data(), 0, sizeof(*s->d_tot.data()), ctx->stream));
+  return OKV_OK;
+}
+
+// okv_*_totals after the caller zeroed *out: the last call's totals and its capacity error.
+template <class S, class Out, class Read>
+int last_totals(okv_ctx* ctx, S* s, Out* out, const char* cap_msg, Read read) {
+  if (!s || !s->d_tot.data()) return OKV_OK;  // no call has launched anything
+  OKV_HIP(hipSetDevice(ctx->device));
+  if (int rc = reserve(ctx, s->h_tot, 1)) return rc;
+  if (int rc = read(ctx, s, out)) return rc;
+  if (s->last_arena && out->val_bytes > s->last_cap) return set_err(ctx, OKV_E_CAPACITY, cap_msg);
+  return OKV_OK;
+}
+
+// After run(): the values and the totals.  Device mode: the values kernel behind run()
+// (it writes nothing when they do not fit), then, unless OKV_F_ASYNC, the totals.  Host
+// mode: the columns back, the totals, and when the values fit a device arena of exactly
+// val_bytes, the values kernel and the copy out.  values(p) launches the values kernel.
+template <class S, class P, class Out, class Read, class Values>
+int finish_values(okv_ctx* ctx, S* s, P& p, Out* out, uint32_t flags, const stage::Col* cols,
+                  size_t ncols, const char* cap_msg, Read read, Values values) {
+  const bool dev = flags & OKV_F_DEVICE_PTRS;
+  if (dev) {
+    if (out->val_arena)
+      if (int rc = values(p)) return rc;
+    if (flags & OKV_F_ASYNC) return OKV_OK;
+  } else if (int rc = stage_out(ctx, cols, ncols, p.n)) {
+    return rc;
+  }
+  if (int rc = read(ctx, s, out)) return rc;
+  if (!out->val_arena) return OKV_OK;
+  if (out->val_bytes > out->val_cap) return set_err(ctx, OKV_E_CAPACITY, cap_msg);
+  if (dev || out->val_bytes == 0) return OKV_OK;
+  if (int rc = reserve(ctx, s->d_val, size_t(out->val_bytes))) return rc;
+  p.val_arena = s->d_val.data();
+  p.val_cap = out->val_bytes;
+  if (int rc = values(p)) return rc;
+  OKV_HIP(hipMemcpyAsync(out->val_arena, p.val_arena, out->val_bytes, hipMemcpyDeviceToHost,
+                         ctx->stream));
+  OKV_HIP(hipStreamSynchronize(ctx->stream));
+  return OKV_OK;
 }
 
 }  // namespace

@@ -148,8 +148,6 @@ Scratch* scratch(okv_ctx* ctx) {
   return ctx->range;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
 }  // namespace
 }  // namespace rng
 
@@ -174,8 +172,7 @@ int okv_seek_rows(okv_ctx* ctx, const okv_seek_src* srcs, uint32_t nsrc, const o
   const uint64_t n = keys->n_rows;
   if (n >= get::kNone) return set_err(ctx, OKV_E_ARG, "seek: 2^32 - 1 triples or more");
   if (n == 0) return OKV_OK;
-  if (!keys->key_off || !keys->key_len || (!keys->key_arena && keys->key_arena_bytes))
-    return set_err(ctx, OKV_E_ARG, "seek: keys");
+  if (int rc = key_err(ctx, stage::check_keys(keys, false), "seek", "keys")) return rc;
   if (!src_of || !direction || !row_lo || !row_hi)
     return set_err(ctx, OKV_E_ARG, "seek: a NULL array");
   for (uint32_t s = 0; s < nsrc; ++s)
@@ -203,41 +200,41 @@ int okv_seek_rows(okv_ctx* ctx, const okv_seek_src* srcs, uint32_t nsrc, const o
     if (!(flags & OKV_F_ASYNC)) OKV_HIP(hipStreamSynchronize(st));
     return OKV_OK;
   }
-  for (uint64_t i = 0; i < n; ++i) {
-    if (keys->key_off[i] > keys->key_arena_bytes ||
-        keys->key_len[i] > keys->key_arena_bytes - keys->key_off[i])
-      return set_err(ctx, OKV_E_ARG, "seek: a key lies outside key_arena_bytes");
+  if (int rc = key_err(ctx, stage::check_keys(keys, true), "seek", "keys")) return rc;
+  for (uint64_t i = 0; i < n; ++i)
     if (src_of[i] >= nsrc) return set_err(ctx, OKV_E_ARG, "seek: src_of names no source");
-  }
-  // host mode: every input through one pinned image and one copy, both outputs back in one
-  const size_t osr = al256(keys->key_arena_bytes), oko = osr + al256(sizeof(seek::Source) * nsrc),
-               okl = oko + al256(n * 8), oso = okl + al256(n * 2), odi = oso + al256(n * 4),
-               olo = odi + al256(n), ohi = olo + n * 8, end = ohi + n * 8;
+  // host mode: every input through one pinned image and one copy, both outputs (one
+  // column of pairs) back in one.  head: the two arrays not sized by n, one element each
+  stage::Col head[] = {{keys->key_arena, keys->key_arena_bytes, true, false},
+                       {srcs, sizeof(seek::Source) * nsrc, true, false}};
+  stage::Col cols[] = {{keys->key_off, 8, true, false}, {keys->key_len, 2, true, false},
+                       {src_of, 4, true, false},        {direction, 1, true, false},
+                       {row_lo, 16, false, true}};
+  stage::Layout L;
+  stage::place(L, head, 2, 1);
+  stage::place(L, cols, 5, n);
   int rc;
-  if ((rc = reserve(ctx, sc->stage, end)) || (rc = reserve(ctx, sc->h_stage, end))) return rc;
-  uint8_t* b = sc->stage.data();
+  if ((rc = reserve(ctx, sc->stage, L.end())) || (rc = reserve(ctx, sc->h_stage, L.end())))
+    return rc;
+  stage::bind(sc->stage.data(), head, 2);
+  stage::bind(sc->stage.data(), cols, 5);
   uint8_t* h = sc->h_stage.data();
-  if (keys->key_arena_bytes) memcpy(h, keys->key_arena, keys->key_arena_bytes);
-  if (nsrc) memcpy(h + osr, srcs, sizeof(seek::Source) * nsrc);
-  memcpy(h + oko, keys->key_off, n * 8);
-  memcpy(h + okl, keys->key_len, n * 2);
-  memcpy(h + oso, src_of, n * 4);
-  memcpy(h + odi, direction, n);
-  OKV_HIP(hipMemcpyAsync(b, h, olo, h2d, st));
-  P.srcs = reinterpret_cast<const seek::Source*>(b + osr);
-  P.ka = b;
-  P.ko = reinterpret_cast<const uint64_t*>(b + oko);
-  P.kl = reinterpret_cast<const uint16_t*>(b + okl);
-  P.src_of = reinterpret_cast<const uint32_t*>(b + oso);
-  P.direction = b + odi;
-  P.row_lo = reinterpret_cast<uint64_t*>(b + olo);
-  P.row_hi = reinterpret_cast<uint64_t*>(b + ohi);
+  for (const stage::Col& c : head)
+    if (c.elem) memcpy(h + c.off, c.host, c.elem);
+  for (const stage::Col& c : cols)
+    if (c.in) memcpy(h + c.off, c.host, c.elem * n);
+  const size_t olo = cols[4].off;
+  OKV_HIP(hipMemcpyAsync(sc->stage.data(), h, olo, h2d, st));
+  P.ka = head[0].as<const uint8_t>(), P.srcs = head[1].as<const seek::Source>();
+  P.ko = cols[0].as<const uint64_t>(), P.kl = cols[1].as<const uint16_t>();
+  P.src_of = cols[2].as<const uint32_t>(), P.direction = cols[3].as<const uint8_t>();
+  P.row_lo = cols[4].as<uint64_t>(), P.row_hi = P.row_lo + n;
   hipLaunchKernelGGL(okv_seek_kernel, grid, block, 0, st, P);
   OKV_HIP(hipGetLastError());
-  OKV_HIP(hipMemcpyAsync(h + olo, b + olo, n * 16, d2h, st));
+  OKV_HIP(hipMemcpyAsync(h + olo, P.row_lo, n * 16, d2h, st));
   OKV_HIP(hipStreamSynchronize(st));
   memcpy(row_lo, h + olo, n * 8);
-  memcpy(row_hi, h + ohi, n * 8);
+  memcpy(row_hi, h + olo + n * 8, n * 8);
   return OKV_OK;
 }
 
@@ -281,21 +278,18 @@ int okv_gather_rows(okv_ctx* ctx, const okv_merge_src* srcs, uint32_t nsrc, cons
   P.srcs = sc->d_src.data(), P.nsrc = nsrc, P.n = uint32_t(n);
   P.src = src, P.row = row;
   P.kscan = sc->kscan.data(), P.vscan = sc->vscan.data();
-  uint64_t *kpos, *vpos;
-  const size_t okl = al256(n * 8), ovp = okl + al256(n * 2), ovl = ovp + al256(n * 8),
-               end = ovl + al256(n * 4);
-  uint8_t* b = nullptr;
+  stage::Col cols[] = {{out->key_pos, 8, false, true}, {out->key_len, 2, false, true},
+                       {out->val_pos, 8, false, true}, {out->val_len, 4, false, true}};
   if (dev) {
-    P.key_len = out->key_len, P.val_len = out->val_len;
-    kpos = out->key_pos, vpos = out->val_pos;
+    stage::direct(cols, 4);
   } else {
-    if ((rc = reserve(ctx, sc->stage, end))) return rc;
-    b = sc->stage.data();
-    kpos = reinterpret_cast<uint64_t*>(b);
-    P.key_len = reinterpret_cast<uint16_t*>(b + okl);
-    vpos = reinterpret_cast<uint64_t*>(b + ovp);
-    P.val_len = reinterpret_cast<uint32_t*>(b + ovl);
+    stage::Layout L;
+    stage::place(L, cols, 4, n);
+    if ((rc = reserve(ctx, sc->stage, L.end()))) return rc;
+    stage::bind(sc->stage.data(), cols, 4);
   }
+  uint64_t *kpos = cols[0].as<uint64_t>(), *vpos = cols[2].as<uint64_t>();
+  P.key_len = cols[1].as<uint16_t>(), P.val_len = cols[3].as<uint32_t>();
   hipLaunchKernelGGL(okv_gather_index_kernel, dim3(ceil_div(n, kThreads)), dim3(kThreads), 0, st, P);
   OKV_HIP(hipGetLastError());
   if ((rc = get::scan(ctx, sc->tsum_in, sc->tsum, KeyRoom{P.key_len}, n, sc->kscan.data(), kpos)))
@@ -319,10 +313,7 @@ int okv_gather_rows(okv_ctx* ctx, const okv_merge_src* srcs, uint32_t nsrc, cons
       return set_err(ctx, OKV_E_CAPACITY, "gather: key_cap or val_cap too small");
     return OKV_OK;
   }
-  OKV_HIP(hipMemcpyAsync(out->key_pos, b, n * 8, d2h, st));
-  OKV_HIP(hipMemcpyAsync(out->key_len, b + okl, n * 2, d2h, st));
-  OKV_HIP(hipMemcpyAsync(out->val_pos, b + ovp, n * 8, d2h, st));
-  OKV_HIP(hipMemcpyAsync(out->val_len, b + ovl, n * 4, d2h, st));
+  if ((rc = stage_out(ctx, cols, 4, n))) return rc;
   OKV_HIP(hipStreamSynchronize(st));
   out->key_bytes = sc->h_tot.data()[0], out->val_bytes = sc->h_tot.data()[1];
   if (!arenas) return OKV_OK;

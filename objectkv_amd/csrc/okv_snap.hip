@@ -348,22 +348,11 @@ int run(okv_ctx* ctx, Scratch* s, const okv_snap* sn, Params& P, uint64_t* val_p
     hipLaunchKernelGGL(okv_snap_locate_kernel, dim3(gp), dim3(kThreads), 0, ctx->stream, P);
     OKV_HIP(hipGetLastError());
   }
-  if (nb) {
-    if (int rc = scan(ctx, s->tsum_in, s->tsum, CntLoad{P.cnt}, nb, P.gscan, nullptr)) return rc;
-    const uint32_t gs = std::max(1u, std::min(ceil_div(std::max(np_max, nb), kThreads), cap));
-    hipLaunchKernelGGL(okv_snap_scatter_kernel, dim3(gs), dim3(kThreads), 0, ctx->stream, P);
-    const uint64_t most = std::min(np_max, nb);  // touched blocks at most
-    if (sn->max_block <= kSmallCap) {
-      const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(sn->n_cu) * 8));
-      hipLaunchKernelGGL(okv_snap_search_kernel<kSmallCap>, dim3(g), dim3(kSearchThreads), 0,
-                         ctx->stream, P);
-    } else {
-      const uint32_t g = uint32_t(std::min<uint64_t>(most, uint64_t(sn->n_cu) * 2));
-      hipLaunchKernelGGL(okv_snap_search_kernel<uint32_t(kStage)>, dim3(g), dim3(kSearchThreads),
-                         0, ctx->stream, P);
-    }
-    OKV_HIP(hipGetLastError());
-  }
+  if (nb)
+    if (int rc = group_and_search(ctx, s, P, np_max, nb, sn->max_block, sn->n_cu,
+                                  okv_snap_scatter_kernel, okv_snap_search_kernel<kSmallCap>,
+                                  okv_snap_search_kernel<uint32_t(kStage)>))
+      return rc;
   hipLaunchKernelGGL(okv_snap_resolve_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
   if (int rc = scan(ctx, s->tsum_in, s->tsum, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos))
@@ -475,11 +464,7 @@ int okv_snap_new(okv_ctx* ctx, const okv_snap_seg* segs, uint32_t n_segs, okv_sn
   std::unique_ptr<okv_snap> sn(new okv_snap());
   sn->ctx = ctx;
   sn->ns = n_segs, sn->nb = uint32_t(nb), sn->max_block = max_block;
-  int ncu = 0;
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) !=
-          hipSuccess || ncu <= 0)
-    ncu = 256;
-  sn->n_cu = uint32_t(ncu);
+  sn->n_cu = cu_count(ctx);
   if (upload(ctx, sn->segs, sd) || upload(ctx, sn->by_prio, by_prio) ||
       upload(ctx, sn->blk_seg, blk_seg) || upload(ctx, sn->arena, im.arena) ||
       upload(ctx, sn->first_off, im.first_off) || upload(ctx, sn->last_off, im.last_off) ||
@@ -506,17 +491,9 @@ int okv_snap_get_rows(okv_ctx* ctx, const okv_snap* sn, const okv_rows* keys, ok
   ctx->last_path = 0;
   zero_totals(out);
   snap::Scratch* s = scratch(ctx);
-  s->last_arena = out->val_arena != nullptr;
-  s->last_cap = out->val_cap;
-  if (n == 0) {
-    if (s->d_tot.data()) {  // (okv_snap_totals reads this call's totals: none)
-      OKV_HIP(hipSetDevice(ctx->device));
-      OKV_HIP(hipMemsetAsync(s->d_tot.data(), 0, sizeof(SnapTotals), ctx->stream));
-    }
-    return OKV_OK;
-  }
-  if (!keys->key_off || !keys->key_len || (!keys->key_arena && keys->key_arena_bytes))
-    return set_err(ctx, OKV_E_ARG, "snap get: keys");
+  if (int rc = open_call(ctx, s, out, n)) return rc;
+  if (n == 0) return OKV_OK;
+  if (int rc = key_err(ctx, stage::check_keys(keys, false), "snap get", "keys")) return rc;
   if (!out->state || !out->seg || !out->blk_status || !out->entry || !out->val_off || !out->val_len)
     return set_err(ctx, OKV_E_ARG, "snap get: a NULL output array");
   const bool dev = flags & OKV_F_DEVICE_PTRS;
@@ -534,79 +511,28 @@ int okv_snap_get_rows(okv_ctx* ctx, const okv_snap* sn, const okv_rows* keys, ok
   P.val_cap = out->val_cap;
   ctx->last_path = OKV_PATH_SNAP_GET;
 
-  if (dev) {
-    P.ka = keys->key_arena, P.ko = keys->key_off, P.kl = keys->key_len;
-    P.state = out->state, P.seg = out->seg, P.blk_status = out->blk_status, P.entry = out->entry;
-    P.val_off = out->val_off, P.val_len = out->val_len, P.val_arena = out->val_arena;
-    if (int rc = run(ctx, s, sn, P, out->val_pos)) return rc;
-    if (out->val_arena)
-      if (int rc = launch_values(ctx, sn, P)) return rc;
-    if (flags & OKV_F_ASYNC) return OKV_OK;
-    if (int rc = read_totals(ctx, s, out)) return rc;
-    if (out->val_arena && out->val_bytes > out->val_cap)
-      return set_err(ctx, OKV_E_CAPACITY, "snap get: val_cap too small");
-    return OKV_OK;
-  }
-
-  // host mode: the key arrays in, the per-key arrays out, through one staging buffer
-  for (uint64_t i = 0; i < n; ++i)
-    if (keys->key_off[i] > keys->key_arena_bytes ||
-        keys->key_len[i] > keys->key_arena_bytes - keys->key_off[i])
-      return set_err(ctx, OKV_E_ARG, "snap get: a key lies outside key_arena_bytes");
-  const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t oko = al(keys->key_arena_bytes), okl = oko + al(n * 8), ost = okl + al(n * 2),
-               osg = ost + al(n * 4), obs = osg + al(n * 4), oen = obs + al(n * 4),
-               ovo = oen + al(n * 4), ovl = ovo + al(n * 8), ovp = ovl + al(n * 4),
-               end = ovp + al(n * 8);
-  if (int rc = reserve(ctx, s->stage, end)) return rc;
-  uint8_t* b = s->stage.data();
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  if (keys->key_arena_bytes)
-    OKV_HIP(hipMemcpyAsync(b, keys->key_arena, keys->key_arena_bytes, h2d, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(b + oko, keys->key_off, n * 8, h2d, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(b + okl, keys->key_len, n * 2, h2d, ctx->stream));
-  P.ka = b;
-  P.ko = reinterpret_cast<const uint64_t*>(b + oko);
-  P.kl = reinterpret_cast<const uint16_t*>(b + okl);
-  P.state = reinterpret_cast<int32_t*>(b + ost);
-  P.seg = reinterpret_cast<uint32_t*>(b + osg);
-  P.blk_status = reinterpret_cast<int32_t*>(b + obs);
-  P.entry = reinterpret_cast<uint32_t*>(b + oen);
-  P.val_off = reinterpret_cast<uint64_t*>(b + ovo);
-  P.val_len = reinterpret_cast<uint32_t*>(b + ovl);
-  if (int rc = run(ctx, s, sn, P, reinterpret_cast<uint64_t*>(b + ovp))) return rc;
-  OKV_HIP(hipMemcpyAsync(out->state, b + ost, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->seg, b + osg, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->blk_status, b + obs, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->entry, b + oen, n * 4, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->val_off, b + ovo, n * 8, d2h, ctx->stream));
-  OKV_HIP(hipMemcpyAsync(out->val_len, b + ovl, n * 4, d2h, ctx->stream));
-  if (out->val_pos) OKV_HIP(hipMemcpyAsync(out->val_pos, b + ovp, n * 8, d2h, ctx->stream));
-  if (int rc = read_totals(ctx, s, out)) return rc;  // (synchronises)
-  if (!out->val_arena) return OKV_OK;
-  if (out->val_bytes > out->val_cap)
-    return set_err(ctx, OKV_E_CAPACITY, "snap get: val_cap too small");
-  if (out->val_bytes == 0) return OKV_OK;
-  if (int rc = reserve(ctx, s->d_val, size_t(out->val_bytes))) return rc;
-  P.val_arena = s->d_val.data();
-  P.val_cap = out->val_bytes;
-  if (int rc = launch_values(ctx, sn, P)) return rc;
-  OKV_HIP(hipMemcpyAsync(out->val_arena, P.val_arena, out->val_bytes, d2h, ctx->stream));
-  OKV_HIP(hipStreamSynchronize(ctx->stream));
-  return OKV_OK;
+  // the per-key arrays: the caller's, or (host mode) staged behind the key arrays
+  stage::Col cols[] = {{out->state, 4, false, true},      {out->seg, 4, false, true},
+                       {out->blk_status, 4, false, true}, {out->entry, 4, false, true},
+                       {out->val_off, 8, false, true},    {out->val_len, 4, false, true},
+                       {out->val_pos, 8, false, true}};
+  KeyRows R;
+  if (int rc = stage_keys(ctx, s->stage, keys, dev, "snap get", "keys", cols, 7, &R)) return rc;
+  P.ka = R.ka, P.ko = R.ko, P.kl = R.kl;
+  P.state = cols[0].as<int32_t>(), P.seg = cols[1].as<uint32_t>();
+  P.blk_status = cols[2].as<int32_t>(), P.entry = cols[3].as<uint32_t>();
+  P.val_off = cols[4].as<uint64_t>(), P.val_len = cols[5].as<uint32_t>();
+  if (dev) P.val_arena = out->val_arena;
+  if (int rc = run(ctx, s, sn, P, cols[6].as<uint64_t>())) return rc;
+  return finish_values(ctx, s, P, out, flags, cols, 7, "snap get: val_cap too small", read_totals,
+                       [&](const Params& p) { return launch_values(ctx, sn, p); });
 }
 
 int okv_snap_totals(okv_ctx* ctx, okv_snap_out* out) {
   if (!ctx || !out) return OKV_E_ARG;
   snap::Scratch* s = ctx->snap;
   zero_totals(out);
-  if (!s || !s->d_tot.data()) return OKV_OK;  // no call has launched anything
-  OKV_HIP(hipSetDevice(ctx->device));
-  if (int rc = reserve(ctx, s->h_tot, 1)) return rc;
-  if (int rc = read_totals(ctx, s, out)) return rc;
-  if (s->last_arena && out->val_bytes > s->last_cap)
-    return set_err(ctx, OKV_E_CAPACITY, "snap get: val_cap too small");
-  return OKV_OK;
+  return last_totals(ctx, s, out, "snap get: val_cap too small", read_totals);
 }
 
 }  // extern "C"

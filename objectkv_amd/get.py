@@ -17,8 +17,8 @@ import numpy as np
 from . import _lib
 from ._lib import (F_ASYNC, F_DEVICE_PTRS, GET_BLOCK_ERROR, GET_BLOOM_NEGATIVE,  # noqa: F401
                    GET_FALLBACK, GET_FOUND, GET_NO_BLOCK, GET_NOT_IN_BLOCK, lib)
-from .bloom import DeviceBloom, key_rows, pack_keys
-from .sst import OkvError, _ptr
+from .bloom import DeviceBloom, Values, pack_keys, rows_call
+from .sst import _ptr
 
 _OUT = (("state", np.int32), ("blk_status", np.int32), ("entry", np.uint32),
         ("val_off", np.uint64), ("val_len", np.uint32), ("val_pos", np.uint64))
@@ -63,7 +63,7 @@ class DeviceIndex:
     __del__ = close
 
 
-class GetResult:
+class GetResult(Values):
     """The arrays of okv_get_out and its totals."""
 
     def __init__(self, arrays, val_arena, o):
@@ -71,14 +71,6 @@ class GetResult:
         self.val_arena = val_arena
         self.n_found, self.n_fallback = int(o.n_found), int(o.n_fallback)
         self.val_bytes, self.blocks_searched = int(o.val_bytes), int(o.blocks_searched)
-
-    def value(self, i):
-        """FOUND key i's value from val_arena (host arrays): bytes, or None for Go's nil."""
-        n = int(self.val_len[i])
-        if not n:
-            return None
-        p = int(self.val_pos[i])
-        return self.val_arena[p:p + n].tobytes()
 
 
 def get_rows(owner, seg, seg_bytes, index: DeviceIndex, keys, bloom: DeviceBloom = None,
@@ -92,40 +84,16 @@ def get_rows(owner, seg, seg_bytes, index: DeviceIndex, keys, bloom: DeviceBloom
     Host mode: values=False is the index-only call; val_cap defaults to room for every
     value (two calls: the first sizes the arena).  Raises OkvError (OKV_E_CAPACITY with
     .result holding the totals)."""
-    R, dev, keep = key_rows(keys, n_rows, key_arena_bytes)
-    n = int(R.n_rows)
     segp = seg if isinstance(seg, int) or seg is None else _ptr(seg)
     bh = bloom._h if bloom is not None else None
-    L = lib()
 
-    def call(arrays, arena, cap, flags):
-        o = _lib.GetOut(*[_ptr(arrays.get(k)) for k, _ in _OUT], _ptr(arena), cap, 0, 0, 0, 0)
-        rc = L.okv_get_rows(owner._ctx, segp, seg_bytes, index._h, bh, C.byref(R), compression,
-                            C.byref(o), flags)
-        return rc, o
+    def call(R, ptrs, arena, cap, flags):
+        o = _lib.GetOut(*ptrs, arena, cap, 0, 0, 0, 0)
+        return lib().okv_get_rows(owner._ctx, segp, seg_bytes, index._h, bh, C.byref(R),
+                                  compression, C.byref(o), flags), o
 
-    if dev:
-        arena = out.get("val_arena")
-        cap = int(arena.numel()) if arena is not None and val_cap is None else int(val_cap or 0)
-        rc, o = call(out, arena, cap, F_DEVICE_PTRS | (0 if sync else F_ASYNC))
-        arrays = {k: out.get(k) for k, _ in _OUT}
-    else:
-        arrays = {k: np.zeros(n, t) for k, t in _OUT}
-        arena, cap = None, 0
-        if values:
-            if val_cap is None:  # size query: index only, then the arena
-                rc, o = call(arrays, None, 0, 0)
-                owner._check(rc, "okv_get_rows")
-                val_cap = int(o.val_bytes)
-            cap = int(val_cap)
-            arena = np.zeros(max(cap, 1), np.uint8)
-        rc, o = call(arrays, arena, cap, 0)
-    res = GetResult(arrays, arena, o)
-    if rc:
-        e = OkvError(rc, f"okv_get_rows: {owner.error()}")
-        e.result = res
-        raise e
-    return res
+    return rows_call(owner, "okv_get_rows", _OUT, call, GetResult, keys, n_rows, key_arena_bytes,
+                     values, val_cap, out, sync)
 
 
 def totals(owner) -> dict:

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import F_ASYNC, F_DEVICE_PTRS, lib
-from .bloom import key_rows
+from .bloom import Values, key_rows
 from .sst import COMP_NONE, OkvError, _ptr
 
 _GATHER = (("key_pos", np.uint64), ("key_len", np.uint16), ("val_pos", np.uint64),
@@ -157,7 +157,7 @@ def pack_pages(jobs, first_slot=0):
     return (_lib.Page * len(fit))(*fit), bytes(blob), at, old
 
 
-class GatherResult:
+class GatherResult(Values):
     """The arrays of okv_gather_out and its totals."""
 
     def __init__(self, arrays, key_arena, val_arena, o):
@@ -180,14 +180,6 @@ class GatherResult:
         """Row i's key (host arrays)."""
         p = int(self.key_pos[i])
         return self.key_arena[p:p + int(self.key_len[i])].tobytes()
-
-    def value(self, i):
-        """Row i's value (host arrays): bytes, or None for Go's nil."""
-        n = int(self.val_len[i])
-        if not n:
-            return None
-        p = int(self.val_pos[i])
-        return self.val_arena[p:p + n].tobytes()
 
 
 def gather_rows(owner, sources, src, row, n=None, out=None, arenas=True, key_cap=None,

@@ -19,8 +19,8 @@ import numpy as np
 from . import _lib
 from ._lib import (F_ASYNC, F_DEVICE_PTRS, SNAP_DELETED, SNAP_FALLBACK, SNAP_FOUND,  # noqa: F401
                    SNAP_NO_ROWS, SNAP_SEG_ERROR, lib)
-from .bloom import key_rows
-from .sst import OkvError, _ptr
+from .bloom import Values, rows_call
+from .sst import _ptr
 
 _OUT = (("state", np.int32), ("seg", np.uint32), ("blk_status", np.int32), ("entry", np.uint32),
         ("val_off", np.uint64), ("val_len", np.uint32), ("val_pos", np.uint64))
@@ -95,7 +95,7 @@ class DeviceSnapshot:
     __del__ = close
 
 
-class SnapResult:
+class SnapResult(Values):
     """The arrays of okv_snap_out and its totals."""
 
     def __init__(self, arrays, val_arena, o):
@@ -103,14 +103,6 @@ class SnapResult:
         self.val_arena = val_arena
         for k in _TOTALS:
             setattr(self, k, int(getattr(o, k)))
-
-    def value(self, i):
-        """FOUND key i's value from val_arena (host arrays): bytes, or None for Go's nil."""
-        n = int(self.val_len[i])
-        if not n:
-            return None
-        p = int(self.val_pos[i])
-        return self.val_arena[p:p + n].tobytes()
 
 
 def snap_get_rows(owner, snap: DeviceSnapshot, keys, values=True, val_cap=None, out=None,
@@ -122,37 +114,12 @@ def snap_get_rows(owner, snap: DeviceSnapshot, keys, values=True, val_cap=None, 
     Host mode: values=False is the index-only call; val_cap defaults to room for every
     value (two calls: the first sizes the arena).  Raises OkvError (OKV_E_CAPACITY with
     .result holding the totals)."""
-    R, dev, keep = key_rows(keys, n_rows, key_arena_bytes)
-    n = int(R.n_rows)
-    L = lib()
+    def call(R, ptrs, arena, cap, flags):
+        o = _lib.SnapOut(*ptrs, arena, cap, 0, 0, 0, 0, 0, 0)
+        return lib().okv_snap_get_rows(owner._ctx, snap._h, C.byref(R), C.byref(o), flags), o
 
-    def call(arrays, arena, cap, flags):
-        o = _lib.SnapOut(*[_ptr(arrays.get(k)) for k, _ in _OUT], _ptr(arena), cap, 0, 0, 0, 0, 0, 0)
-        rc = L.okv_snap_get_rows(owner._ctx, snap._h, C.byref(R), C.byref(o), flags)
-        return rc, o
-
-    if dev:
-        arena = out.get("val_arena")
-        cap = int(arena.numel()) if arena is not None and val_cap is None else int(val_cap or 0)
-        rc, o = call(out, arena, cap, F_DEVICE_PTRS | (0 if sync else F_ASYNC))
-        arrays = {k: out.get(k) for k, _ in _OUT}
-    else:
-        arrays = {k: np.zeros(n, t) for k, t in _OUT}
-        arena, cap = None, 0
-        if values:
-            if val_cap is None:  # size query: index only, then the arena
-                rc, o = call(arrays, None, 0, 0)
-                owner._check(rc, "okv_snap_get_rows")
-                val_cap = int(o.val_bytes)
-            cap = int(val_cap)
-            arena = np.zeros(max(cap, 1), np.uint8)
-        rc, o = call(arrays, arena, cap, 0)
-    res = SnapResult(arrays, arena, o)
-    if rc:
-        e = OkvError(rc, f"okv_snap_get_rows: {owner.error()}")
-        e.result = res
-        raise e
-    return res
+    return rows_call(owner, "okv_snap_get_rows", _OUT, call, SnapResult, keys, n_rows,
+                     key_arena_bytes, values, val_cap, out, sync)
 
 
 def totals(owner) -> dict:

@@ -196,6 +196,26 @@ def test_staged_block_machinery_is_stated_once():
     assert "while (" not in m.group(0)
 
 
+def test_host_mode_staging_is_stated_once():
+    """The batched calls' host mode is okv_stage.hpp's: one key check, one 256-byte
+    rounding, one KeyRows; the CU count is okv_ctx.hpp's cu_count."""
+    csrc = os.path.join(ROOT, "objectkv_amd", "csrc")
+    code = {name: _strip_comments(open(os.path.join(csrc, name), errors="replace").read())
+            for name in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, name))}
+    callers = ("okv_bloom.hip", "okv_get.hip", "okv_snap.hip", "okv_seek.hip")
+    assert {n: c.count("lies outside key_arena_bytes") for n, c in code.items()
+            if "lies outside key_arena_bytes" in c} == {"okv_stage.hpp": 1}
+    assert {n: len(re.findall(r"\bstruct KeyRows\b", c)) for n, c in code.items()
+            if re.search(r"\bstruct KeyRows\b", c)} == {"okv_stage.hpp": 1}
+    for name in callers:
+        assert "+ 255) & ~" not in code[name], name
+        assert not re.search(r"\bal(256)?\s*(=|\()", code[name]), name
+        assert "hipDeviceAttributeMultiprocessorCount" not in code[name], name
+        assert "okv_stage.hpp" in code[name] or "okv_get_kernels.hpp" in code[name], name
+    assert code["okv_stage.hpp"].count("+ 255) & ~") == 1
+    assert code["okv_ctx.hpp"].count("hipDeviceAttributeMultiprocessorCount") == 1
+
+
 def test_zstd_stage_owns_its_scratch_and_diagnostics_are_out_of_line():
     """okv_zstd.hip's host part (everything after its last kernel) is the
     product sequence: the knobs, the profiling and the reports live in
