@@ -131,9 +131,11 @@ int okv_reader_get_row(okv_reader *r, const uint8_t *key, size_t klen, okv_row *
  * filter once (kept until okv_reader_close: bytes_staged grows by the storage length
  * once, calls by one per batched call).  Keys on blocks the batched kernel does not take
  * (BlockSize > 64 KiB), keys longer than 65535 bytes, every key when the filter is one the
- * device probe refuses (m == 0 with k > 0, k > 4096), every key of a zstd segment (for which
- * nothing is uploaded) and every key of a reader without a context go through
- * okv_reader_get_row.  Returns OKV_OK; the metadata error; or OKV_R_GPU when the upload or the
+ * device probe refuses (m == 0 with k > 0, k > 4096) and every key of a reader without a
+ * context go through okv_reader_get_row.  A zstd segment goes through OKV_F_GET_ZSTD: its
+ * touched blocks are inflated on the device and the values come back in an arena the reader
+ * keeps (one call when the last batch's arena suffices, else two: calls counts both); only
+ * keys on a block that inflates past OKV_GET_INFLATED_MAX take the single-key path.  Returns OKV_OK; the metadata error; or OKV_R_GPU when the upload or the
  * batched call itself fails (okv_last_error; nothing stays on the device after a failed
  * upload).  A non-zero return is also in every rcs[i]. */
 int okv_reader_get_rows(okv_reader *r, const uint8_t *const *keys, const size_t *klens,

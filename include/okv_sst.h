@@ -45,7 +45,9 @@ extern "C" {
                                 still 6 with the device zstd encoder (OKV_F_ZSTD_NATIVE,
                                 OKV_PATH_ZSTD_ENC): one new flag bit and one path bit;
                                 still 6 with the snapshot GetRows (okv_snap_*,
-                                OKV_PATH_SNAP_GET): new symbols and one path bit */
+                                OKV_PATH_SNAP_GET): new symbols and one path bit;
+                                still 6 with GetRows on zstd segments (OKV_F_GET_ZSTD,
+                                OKV_GET_INFLATED_MAX): one new flag bit */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -111,6 +113,27 @@ extern "C" {
  * OKV_E_CAPACITY; a call with seg_cap >= that file_bytes and blk_cap >= n_blocks succeeds
  * and sets the actual sizes (never above the bound). */
 #define OKV_F_ZSTD_NATIVE 64u
+/* okv_get_rows / okv_snap_get_rows: take the floor blocks of OKV_COMP_ZSTD segments too
+ * (DESIGN.md 25).  Without the flag such a block is OKV_GET_FALLBACK / OKV_SNAP_FALLBACK.
+ * With it, for a segment whose compression is OKV_COMP_ZSTD (any other segment: no change):
+ *  - the floor block is taken whatever its BlockSize.  Its status before any read is Go's
+ *    in Go's order: :303-316 (EOF / PANIC / SHORT), then CompressedSize > BlockSize ->
+ *    OKV_BLK_PANIC (the slice of :321);
+ *  - every touched block is inflated once per call by the device decoder, its
+ *    CompressedSize bytes only; a frame set the decoder rejects fails the block's keys with
+ *    BLOCK_ERROR (SEG_ERROR) and blk_status = OKV_BLK_ZSTD_ERROR;
+ *  - the record walk (:338-352, bounded by OriginalSize) runs over the whole inflated
+ *    length, as Go inflates every frame before it; a failed walk is OKV_BLK_PANIC;
+ *  - a block that inflates to more than OKV_GET_INFLATED_MAX bytes is FALLBACK for its
+ *    keys (decided after the inflate);
+ *  - FOUND: val_off is the value's offset INSIDE THE INFLATED BLOCK entry[i] names (there is
+ *    no offset into seg); val_len and the bytes in val_arena are as ever.
+ * The call synchronises with the host inside the call (the touched count and the zstd
+ * stage's own round trips, as a zstd okv_decode_blocks does); OKV_F_ASYNC still defers only
+ * the totals.  okv_last_path gains OKV_PATH_ZSTD when blocks were inflated, and
+ * OKV_PATH_ZSTD_REGROW when some outgrew their first region. */
+#define OKV_F_GET_ZSTD 128u
+#define OKV_GET_INFLATED_MAX (1u << 24)
 /* The most source bytes the encoder puts into one zstd block of a frame, so
  * CompressedSize <= OriginalSize + 3 * ceil(OriginalSize / OKV_ZSTD_ENC_UNIT) + 18. */
 #define OKV_ZSTD_ENC_UNIT 32768
@@ -452,15 +475,18 @@ int okv_index_info(const okv_index *ix, uint64_t *n_tree, uint64_t *n_file);
 #define OKV_GET_BLOOM_NEGATIVE 1 /* ErrNoRows, "did not find row in bloom filter" (:371-378) */
 #define OKV_GET_NO_BLOCK 2       /* ErrNoRows, no index entry <= key (:387-389) */
 #define OKV_GET_NOT_IN_BLOCK 3   /* ErrNoRows, "did not find row in block" (:403) */
-#define OKV_GET_BLOCK_ERROR 4    /* blk_status[i] = OKV_BLK_EOF / _SHORT / _PANIC */
-#define OKV_GET_FALLBACK 5       /* not a block this path takes (zstd, BlockSize > 64 KiB):
-                                    use okv_decode_blocks */
+#define OKV_GET_BLOCK_ERROR 4    /* blk_status[i] = OKV_BLK_EOF / _SHORT / _PANIC (with
+                                    OKV_F_GET_ZSTD also OKV_BLK_ZSTD_ERROR) */
+#define OKV_GET_FALLBACK 5       /* not a block this path takes (zstd without OKV_F_GET_ZSTD or
+                                    inflating past OKV_GET_INFLATED_MAX; uncompressed
+                                    BlockSize > 64 KiB): use okv_decode_blocks */
 
 typedef struct okv_get_out {
   int32_t *state;      /* [n] OKV_GET_* */
   int32_t *blk_status; /* [n] OKV_BLK_* of the floor block (OKV_BLK_OK when none was read) */
   uint32_t *entry;     /* [n] file index of the floor block, UINT32_MAX when none */
-  uint64_t *val_off;   /* [n] FOUND: byte offset of the value in seg (else 0) */
+  uint64_t *val_off;   /* [n] FOUND: byte offset of the value in seg (else 0); in a zstd
+                          segment (OKV_F_GET_ZSTD): inside the inflated block entry[i] */
   uint32_t *val_len;   /* [n] FOUND: its length, 0 <=> nil (else 0) */
   uint64_t *val_pos;   /* [n] or NULL: offset of the value in val_arena, 16-byte aligned;
                           keys that are not FOUND take no room */
@@ -480,7 +506,8 @@ typedef struct okv_get_out {
  * flags: without OKV_F_DEVICE_PTRS the key arrays and every output are host memory
  * (staged; the call synchronises); with it, optionally OKV_F_ASYNC, everything stays
  * in stream order (totals then by okv_get_totals after okv_sync).  n_rows == 0
- * succeeds and launches nothing.  Returns OKV_OK, OKV_E_CAPACITY (val_bytes > val_cap:
+ * succeeds and launches nothing.  OKV_F_GET_ZSTD: see the flag.
+ * Returns OKV_OK, OKV_E_CAPACITY (val_bytes > val_cap:
  * totals and the per-key arrays are set, val_arena is not written), or an error.
  */
 int okv_get_rows(okv_ctx *ctx, const uint8_t *seg, uint64_t seg_bytes, const okv_index *ix,
@@ -532,10 +559,12 @@ void okv_snap_free(okv_snap *snap);
 #define OKV_SNAP_FOUND 0     /* val_off / val_len (0 <=> nil) in segment `seg` */
 #define OKV_SNAP_NO_ROWS 1   /* ErrNoRows: no candidate has the row */
 #define OKV_SNAP_DELETED 2   /* ErrNoRows too: an empty value found at level 0 (:136-141) */
-#define OKV_SNAP_SEG_ERROR 3 /* blk_status[i] = OKV_BLK_EOF / _SHORT / _PANIC of segment `seg` */
+#define OKV_SNAP_SEG_ERROR 3 /* blk_status[i] = OKV_BLK_EOF / _SHORT / _PANIC of segment `seg`
+                                (with OKV_F_GET_ZSTD also OKV_BLK_ZSTD_ERROR) */
 #define OKV_SNAP_FALLBACK 4  /* the resolution reached, before any answer, a candidate this path
-                                does not take (zstd, BlockSize > 64 KiB): send the whole key
-                                through the single-key path */
+                                does not take (zstd without OKV_F_GET_ZSTD or inflating past
+                                OKV_GET_INFLATED_MAX; uncompressed BlockSize > 64 KiB): send the
+                                whole key through the single-key path */
 
 typedef struct okv_snap_out {
   int32_t *state;      /* [n] OKV_SNAP_* */
@@ -543,7 +572,8 @@ typedef struct okv_snap_out {
                           segment's position in segs as given; UINT32_MAX when none */
   int32_t *blk_status; /* [n] OKV_BLK_* of that segment's floor block (OKV_BLK_OK otherwise) */
   uint32_t *entry;     /* [n] file index of that floor block, UINT32_MAX when none */
-  uint64_t *val_off;   /* [n] FOUND: byte offset of the value in that segment (else 0) */
+  uint64_t *val_off;   /* [n] FOUND: byte offset of the value in that segment (else 0); in a
+                          zstd segment (OKV_F_GET_ZSTD): inside the inflated block entry[i] */
   uint32_t *val_len;   /* [n] FOUND: its length, 0 <=> nil (else 0) */
   uint64_t *val_pos;   /* [n] or NULL: offset of the value in val_arena, 16-byte aligned;
                           keys that are not FOUND take no room */
@@ -557,7 +587,8 @@ typedef struct okv_snap_out {
 } okv_snap_out;
 
 /*
- * keys, flags, n_rows == 0 and OKV_E_CAPACITY as okv_get_rows.  Fewer than 2^32 keys,
+ * keys, flags (OKV_F_GET_ZSTD included: a snapshot may mix segment kinds), n_rows == 0 and
+ * OKV_E_CAPACITY as okv_get_rows.  Fewer than 2^32 keys,
  * and n_rows * n_segs < 2^32 (the pair scratch is sized for every key meeting every
  * segment; more: OKV_E_ARG).  There is no cap on the candidates of one key.
  */

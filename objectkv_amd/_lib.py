@@ -25,10 +25,13 @@ if os.environ.get("OKV_LIB"):
 # ---- constants (include/okv_sst.h) -------------------------------------------
 OKV_OK, OKV_E_ARG, OKV_E_HIP, OKV_E_CAPACITY, OKV_E_NOMEM, OKV_E_NODEV = 0, -1, -2, -3, -4, -5
 BLK_OK, BLK_EOF, BLK_SHORT, BLK_PANIC, BLK_UNSUPPORTED, BLK_CAPACITY = 0, 1, 2, 3, 4, 5
+BLK_ZSTD_ERROR = 6
 COMP_NONE, COMP_ZSTD, COMP_LZ4 = 0, 1, 2
 F_DEVICE_PTRS, F_INDEX_ONLY, F_ASYNC, F_NO_CLOSE = 1, 2, 4, 8
 F_BLOOM_DEVICE = 16
 F_ZSTD_NATIVE = 64  # okv_encode_rows with COMP_ZSTD: the device zstd encoder (opt-in)
+F_GET_ZSTD = 128  # okv_get_rows / okv_snap_get_rows: zstd floor blocks inflated on the device
+GET_INFLATED_MAX = 1 << 24  # OKV_GET_INFLATED_MAX: a longer inflated block is FALLBACK
 ZSTD_ENC_UNIT = 32768  # OKV_ZSTD_ENC_UNIT: most source bytes in one zstd block of a frame
 BLOOM_FORCE_LDS, BLOOM_FORCE_GLOBAL = 32, 64
 BLOOM_PATH_LDS, BLOOM_PATH_GLOBAL = 1, 2

@@ -63,12 +63,12 @@ class Values:
 
 
 def rows_call(owner, name, cols, call, result, keys, n_rows, key_arena_bytes, values, val_cap,
-              out, sync):
+              out, sync, flags=0):
     """What get_rows and snap_get_rows share.  cols: the (name, dtype) per-key arrays of the
     out struct; call(R, [pointer per column], arena pointer, cap, flags) -> (rc, out struct);
     result(arrays, arena, out struct) -> the result.  Device mode takes the tensors of
     ``out``; host mode makes the arrays, sizes the arena by an index-only call when val_cap
-    is None, and raises OkvError with .result."""
+    is None, and raises OkvError with .result.  flags: further OKV_F_* bits of every call."""
     R, dev, keep = key_rows(keys, n_rows, key_arena_bytes)
 
     def go(arrays, arena, cap, flags):
@@ -77,19 +77,19 @@ def rows_call(owner, name, cols, call, result, keys, n_rows, key_arena_bytes, va
     if dev:
         arena = out.get("val_arena")
         cap = int(arena.numel()) if arena is not None and val_cap is None else int(val_cap or 0)
-        rc, o = go(out, arena, cap, F_DEVICE_PTRS | (0 if sync else F_ASYNC))
+        rc, o = go(out, arena, cap, flags | F_DEVICE_PTRS | (0 if sync else F_ASYNC))
         arrays = {k: out.get(k) for k, _ in cols}
     else:
         arrays = {k: np.zeros(int(R.n_rows), t) for k, t in cols}
         arena, cap = None, 0
         if values:
             if val_cap is None:  # size query: index only, then the arena
-                rc, o = go(arrays, None, 0, 0)
+                rc, o = go(arrays, None, 0, flags)
                 owner._check(rc, name)
                 val_cap = int(o.val_bytes)
             cap = int(val_cap)
             arena = np.zeros(max(cap, 1), np.uint8)
-        rc, o = go(arrays, arena, cap, 0)
+        rc, o = go(arrays, arena, cap, flags)
     res = result(arrays, arena, o)
     if rc:
         e = OkvError(rc, f"{name}: {owner.error()}")

@@ -16,6 +16,10 @@
 //   scan + okv_get_values_kernel
 //                           round16(val_len) of the found keys scanned in key order, the
 //                           values copied out with 16-byte stores
+// A zstd segment under OKV_F_GET_ZSTD: between the scatter and the values, the inflate arms
+// of okv_get_kernels.hpp instead of the search (okv_get_zplan_kernel, okv_get_zpack_kernel,
+// the zstd stage, okv_get_zsearch_kernel, okv_get_zglobal_kernel), then okv_get_zfix_kernel:
+// val_off inside the inflated block.  DESIGN.md 25.
 //
 // The bodies of the locate, scan, scatter, search and value steps are in
 // okv_get_kernels.hpp, which okv_snap.hip (the same batch against a whole snapshot) shares.
@@ -50,6 +54,7 @@ struct Scratch {
   PinBuf<GetTotals> h_tot;
   DevBuf<uint8_t> stage;    // host mode: key arrays and per-key outputs
   DevBuf<uint8_t> d_val;    // host mode: the value arena
+  ZScratch z;               // the inflate arms (OKV_F_GET_ZSTD)
   bool last_arena = false;  // the last call's arena and capacity (okv_get_totals)
   uint64_t last_cap = 0;
 };
@@ -83,6 +88,7 @@ struct Params {
   uint32_t* list;
   uint64_t* vscan;
   GetTotals* tot;
+  ZView z;  // the inflate arms (z.on: OKV_F_GET_ZSTD on a zstd segment)
 };
 
 namespace {
@@ -96,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void okv_get_locate_kernel(Params P) {
     int32_t state, bst;
     uint32_t entry, t;
     locate_key(key, kl, Filter{P.words, P.mod, P.k, P.length}, P.ix, P.descs, P.file_index,
-               P.seg_bytes, P.comp, state, bst, entry, t);
+               P.seg_bytes, P.comp, P.z.on != 0, state, bst, entry, t);
     if (t != kNone) atomicAdd(&P.cnt[t], 1u);
     P.state[i] = state;
     P.blk_status[i] = bst;
@@ -120,12 +126,14 @@ struct GetSrc {  // search_blocks over one segment: an item is a key
   uint64_t* val_off;
   uint32_t* val_len;
   __device__ __forceinline__ uint32_t touched() const { return uint32_t(P.gscan[P.ix.nt] >> 32); }
-  __device__ __forceinline__ void block(uint32_t w, const uint8_t*& seg, int& comp, Desc& d,
+  __device__ __forceinline__ bool block(uint32_t w, const uint8_t*& seg, int& comp, Desc& d,
                                         uint32_t& k0, uint32_t& k1) const {
     const uint32_t t = P.work[w];
     seg = P.seg, comp = P.comp, d = P.descs[t];
     k0 = uint32_t(P.gscan[t]), k1 = uint32_t(P.gscan[t + 1]);
+    return comp != OKV_COMP_ZSTD;
   }
+  __device__ __forceinline__ uint32_t slot(uint32_t w) const { return P.work[w]; }
   __device__ __forceinline__ uint32_t item(uint32_t j) const { return P.list[j]; }
   __device__ __forceinline__ void key(uint32_t i, const uint8_t*& key, uint32_t& kl) const {
     key = P.ka + P.ko[i], kl = P.kl[i];
@@ -138,6 +146,34 @@ __global__ __launch_bounds__(kSearchThreads) void okv_get_search_kernel(Params P
   __shared__ int32_t s_st;
   __shared__ uint32_t s_rows;
   search_blocks<kCap>(GetSrc{P, P.state, P.blk_status, P.val_off, P.val_len}, sm, s_st, s_rows);
+}
+
+// ---- the inflate arms (OKV_F_GET_ZSTD) ---------------------------------------------
+__global__ __launch_bounds__(kThreads) void okv_get_zplan_kernel(Params P) {
+  zplan_blocks(GetSrc{P, P.state, P.blk_status, P.val_off, P.val_len}, P.z);
+}
+__global__ __launch_bounds__(kThreads) void okv_get_zpack_kernel(Params P) {
+  zpack_blocks(GetSrc{P, P.state, P.blk_status, P.val_off, P.val_len}, P.z);
+}
+template <uint32_t kCap>
+__global__ __launch_bounds__(kSearchThreads) void okv_get_zsearch_kernel(Params P) {
+  __shared__ SearchSmem<kCap> sm;
+  __shared__ int32_t s_st;
+  __shared__ uint32_t s_rows;
+  const GetSrc src{P, P.state, P.blk_status, P.val_off, P.val_len};
+  search_blocks<kCap>(ZSrc<GetSrc>{src, P.z, P.state, P.blk_status, P.val_off, P.val_len}, sm,
+                      s_st, s_rows);
+}
+__global__ __launch_bounds__(kSearchThreads) void okv_get_zglobal_kernel(Params P) {
+  __shared__ int32_t s_st;
+  __shared__ uint32_t s_rows;
+  zglobal_blocks(GetSrc{P, P.state, P.blk_status, P.val_off, P.val_len}, P.z, s_st, s_rows);
+}
+// One lane per key: a found value's offset into the inflated block (zfix_value).
+__global__ __launch_bounds__(kThreads) void okv_get_zfix_kernel(Params P) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < P.n;
+       i += uint64_t(gridDim.x) * kThreads)
+    if (P.state[i] == OKV_GET_FOUND) zfix_value(P.z, i, P.tpos[i], P.val_off);
 }
 
 // ---- values ----------------------------------------------------------------------
@@ -162,8 +198,8 @@ __global__ __launch_bounds__(kThreads) void okv_get_count_kernel(Params P) {
   if (blockIdx.x == 0 && threadIdx.x == 0) P.tot->val_bytes = P.vscan[P.n];
 }
 
-// One wave per found key: its value from the segment into val_arena at the scanned
-// position, 16 bytes a lane, the pad bytes zero.  Nothing is written when the values do
+// One wave per found key: its value from the segment (under the inflate arms: from the
+// inflated blocks) into val_arena at the scanned position, 16 bytes a lane, the pad bytes zero.  Nothing is written when the values do
 // not fit val_cap.
 __global__ __launch_bounds__(kThreads) void okv_get_values_kernel(Params P) {
   if (P.vscan[P.n] > P.val_cap) return;
@@ -173,9 +209,11 @@ __global__ __launch_bounds__(kThreads) void okv_get_values_kernel(Params P) {
        i += waves) {
     if (P.state[i] != OKV_GET_FOUND) continue;
     const uint32_t vl = P.val_len[i];
-    const uint64_t off = P.val_off[i];
-    copy_value(P.seg, P.seg_bytes, off, vl, reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]),
-               lane);
+    uint4* dst = reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]);
+    if (P.z.on)
+      copy_value(P.z.bytes, P.z.n_bytes, P.z.abs[i], vl, dst, lane);
+    else
+      copy_value(P.seg, P.seg_bytes, P.val_off[i], vl, dst, lane);
   }
 }
 
@@ -206,11 +244,20 @@ int run(okv_ctx* ctx, Scratch* s, const okv_index* ix, Params& P, uint64_t* val_
   const uint32_t gk = std::max(1u, std::min(ceil_div(n, kThreads), cap));
   hipLaunchKernelGGL(okv_get_locate_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
+  const ZKernels<Params> zk{okv_get_zplan_kernel, okv_get_zpack_kernel,
+                            okv_get_zsearch_kernel<kSmallCap>,
+                            okv_get_zsearch_kernel<uint32_t(kStage)>, okv_get_zglobal_kernel,
+                            ix->max_original, false};
+  if (P.z.on) {
+    if (int rc = reserve(ctx, s->z.abs, size_t(n))) return rc;
+    P.z.abs = s->z.abs.data();
+  }
   if (nt)
     if (int rc = group_and_search(ctx, s, P, n, nt, ix->max_block, ix->n_cu, okv_get_scatter_kernel,
                                   okv_get_search_kernel<kSmallCap>,
-                                  okv_get_search_kernel<uint32_t(kStage)>))
+                                  okv_get_search_kernel<uint32_t(kStage)>, P.z.on ? &zk : nullptr))
       return rc;
+  if (P.z.on) hipLaunchKernelGGL(okv_get_zfix_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   if (int rc = scan(ctx, s->tsum_in, s->tsum, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos)) return rc;
   hipLaunchKernelGGL(okv_get_count_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
@@ -263,7 +310,10 @@ int okv_index_new(okv_ctx* ctx, const okv_block_desc* descs, const uint8_t* fk_a
   std::unique_ptr<okv_index> ix(new okv_index());
   ix->ctx = ctx;
   ix->nt = im.descs.size(), ix->nf = n;
-  for (const okv_block_desc& d : im.descs) ix->max_block = std::max(ix->max_block, d.block_size);
+  for (const okv_block_desc& d : im.descs) {
+    ix->max_block = std::max(ix->max_block, d.block_size);
+    ix->max_original = std::max(ix->max_original, d.original_size);
+  }
   ix->n_cu = cu_count(ctx);
   const size_t nt = size_t(ix->nt);
   if (reserve(ctx, ix->descs, nt) || reserve(ctx, ix->file_index, nt) ||
@@ -337,6 +387,7 @@ int okv_get_rows(okv_ctx* ctx, const uint8_t* seg, uint64_t seg_bytes, const okv
     P.words = bv.words, P.mod = bloom::modulus(bv.m), P.k = uint32_t(bv.k), P.length = bv.length;
   }
   P.val_cap = out->val_cap;
+  P.z.on = (flags & OKV_F_GET_ZSTD) && compression == OKV_COMP_ZSTD;
   ctx->last_path = OKV_PATH_GET;
 
   // the per-key arrays: the caller's, or (host mode) staged behind the key arrays

@@ -122,6 +122,7 @@ struct okv_reader {
   okv_index* d_index = nullptr;
   okv_bloom* d_bloom = nullptr;
   std::vector<uint8_t> rows_bytes;  // the keys (and fallback rows) of the last batch
+  std::vector<uint8_t> rows_vals;   // a zstd segment: the value arena of the last batch
   ~okv_reader();
 };
 
@@ -568,8 +569,10 @@ int okv_reader_get_rows(okv_reader* r, const uint8_t* const* keys, const size_t*
     return OKV_R_GPU;
   };
   std::vector<uint64_t> batch;  // the keys the device takes
-  // (a zstd segment's keys would all come back FALLBACK: nothing is uploaded for it)
-  if (r->ctx && n && r->compression != OKV_COMP_ZSTD) {
+  // a zstd segment goes through OKV_F_GET_ZSTD: its touched blocks are inflated on the
+  // device and the values come back in an arena (they are not in r->data)
+  const bool zstd = r->compression == OKV_COMP_ZSTD;
+  if (r->ctx && n) {
     if (ensure_device(r)) return gpu_failed();
     if (!r->dev_bloom_refused)
       for (uint64_t i = 0; i < n; ++i)
@@ -588,7 +591,7 @@ int okv_reader_get_rows(okv_reader* r, const uint8_t* const* keys, const size_t*
     const size_t nb = batch.size();
     std::vector<int32_t> state(nb), bst(nb);
     std::vector<uint32_t> entry(nb), vlen(nb);
-    std::vector<uint64_t> voff(nb);
+    std::vector<uint64_t> voff(nb), vpos(zstd ? nb : 0);
     okv_rows kr;
     std::memset(&kr, 0, sizeof(kr));
     kr.key_arena = ka.data(), kr.key_off = ko.data(), kr.key_len = kl.data();
@@ -597,12 +600,27 @@ int okv_reader_get_rows(okv_reader* r, const uint8_t* const* keys, const size_t*
     std::memset(&o, 0, sizeof(o));
     o.state = state.data(), o.blk_status = bst.data(), o.entry = entry.data();
     o.val_off = voff.data(), o.val_len = vlen.data();
-    // index only: the values are read from the reader's own copy of the storage
-    if (okv_get_rows(r->ctx, r->d_seg, r->data.size(), r->d_index, r->d_bloom, &kr,
-                     r->compression, &o, 0) != OKV_OK)
-      return gpu_failed();
-    {
+    // index only: the values are read from the reader's own copy of the storage.  zstd:
+    // into the arena of the last batch (64 KiB at first); a second call when it is too small
+    int grc;
+    if (zstd) {
+      r->rows_vals.resize(std::max<size_t>(r->rows_vals.size(), 65536));
+      o.val_pos = vpos.data();
+      for (int pass = 0; pass < 2; ++pass) {
+        o.val_arena = r->rows_vals.data(), o.val_cap = r->rows_vals.size();
+        grc = okv_get_rows(r->ctx, r->d_seg, r->data.size(), r->d_index, r->d_bloom, &kr,
+                           r->compression, &o, OKV_F_GET_ZSTD);
+        r->io.calls++;
+        if (grc != OKV_E_CAPACITY) break;
+        r->rows_vals.resize(size_t(o.val_bytes));
+      }
+    } else {
+      grc = okv_get_rows(r->ctx, r->d_seg, r->data.size(), r->d_index, r->d_bloom, &kr,
+                         r->compression, &o, 0);
       r->io.calls++;
+    }
+    if (grc != OKV_OK) return gpu_failed();
+    {
       r->io.blocks += o.blocks_searched;
       for (size_t j = 0; j < nb; ++j) {
         const uint64_t i = batch[j];
@@ -616,7 +634,9 @@ int okv_reader_get_rows(okv_reader* r, const uint8_t* const* keys, const size_t*
             r->rows_bytes.insert(r->rows_bytes.end(), keys[i], keys[i] + klens[i]);
             rows[i].key_len = klens[i];
             rows[i].val_len = vlen[j];
-            rows[i].val = vlen[j] ? r->data.data() + voff[j] : nullptr;  // nil (Q4)
+            rows[i].val = !vlen[j] ? nullptr  // nil (Q4)
+                          : zstd   ? r->rows_vals.data() + vpos[j]
+                                   : r->data.data() + voff[j];
             break;
           case OKV_GET_BLOCK_ERROR: rcs[i] = block_rc(bst[j]); break;
           default: rcs[i] = OKV_R_NO_ROWS; break;  // bloom, no block, not in the block

@@ -20,6 +20,10 @@
 //                            first that is not ErrNoRows decides, later ones stay hidden
 //   scan + okv_snap_values_kernel
 //                            the values of the found keys, each from its own segment
+// Under OKV_F_GET_ZSTD the zstd segments' touched blocks go through the inflate arms of
+// okv_get_kernels.hpp behind the scatter (okv_snap_zplan_kernel, okv_snap_zpack_kernel, the
+// zstd stage, okv_snap_zsearch_kernel, okv_snap_zglobal_kernel), and okv_snap_zfix_kernel
+// behind the resolve turns a found value's offset into one inside its inflated block.
 //
 // Probing is speculative: a candidate is located and searched even when a newer one
 // answers.  No kernel waits for another workgroup, and every loop is bounded by an
@@ -75,6 +79,7 @@ struct Scratch {
   PinBuf<SnapTotals> h_tot;
   DevBuf<uint8_t> stage;    // host mode: key arrays and per-key outputs
   DevBuf<uint8_t> d_val;    // host mode: the value arena
+  ZScratch z;               // the inflate arms (OKV_F_GET_ZSTD)
   bool last_arena = false;  // the last call's arena and capacity (okv_snap_totals)
   uint64_t last_cap = 0;
 };
@@ -114,6 +119,7 @@ struct Params {
   uint32_t* work;
   uint64_t* vscan;
   SnapTotals* tot;
+  ZView z;  // the inflate arms (z.on: OKV_F_GET_ZSTD and a zstd segment in the snapshot)
 };
 
 namespace {
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void okv_snap_locate_kernel(Params P) {
     int32_t state, bst;
     uint32_t entry, t;
     locate_key(P.ka + P.ko[i], P.kl[i], g.filter, g.ix, g.descs, g.file_index, g.seg_bytes, g.comp,
-               state, bst, entry, t);
+               P.z.on != 0, state, bst, entry, t);
     if (t != kNone) {
       t += g.block_base;
       atomicAdd(&P.cnt[t], 1u);
@@ -181,13 +187,15 @@ struct SnapSrc {  // search_blocks over a snapshot: an item is a (key, segment) 
   uint64_t* val_off;
   uint32_t* val_len;
   __device__ __forceinline__ uint32_t touched() const { return uint32_t(P.gscan[P.nb] >> 32); }
-  __device__ __forceinline__ void block(uint32_t w, const uint8_t*& seg, int& comp, Desc& d,
+  __device__ __forceinline__ bool block(uint32_t w, const uint8_t*& seg, int& comp, Desc& d,
                                         uint32_t& k0, uint32_t& k1) const {
     const uint32_t b = P.work[w];
     const SegDev& g = P.segs[P.blk_seg[b]];
     seg = g.seg, comp = g.comp, d = g.descs[b - g.block_base];
     k0 = uint32_t(P.gscan[b]), k1 = uint32_t(P.gscan[b + 1]);
+    return comp != OKV_COMP_ZSTD;
   }
+  __device__ __forceinline__ uint32_t slot(uint32_t w) const { return P.work[w]; }
   __device__ __forceinline__ uint32_t item(uint32_t j) const { return P.list[j]; }
   __device__ __forceinline__ void key(uint32_t p, const uint8_t*& key, uint32_t& kl) const {
     const uint32_t i = P.pkey[p];
@@ -201,6 +209,39 @@ __global__ __launch_bounds__(kSearchThreads) void okv_snap_search_kernel(Params 
   __shared__ int32_t s_st;
   __shared__ uint32_t s_rows;
   search_blocks<kCap>(SnapSrc{P, P.pstate, P.pbst, P.pvoff, P.pvlen}, sm, s_st, s_rows);
+}
+
+// ---- the inflate arms (OKV_F_GET_ZSTD) ---------------------------------------------
+__global__ __launch_bounds__(kThreads) void okv_snap_zplan_kernel(Params P) {
+  zplan_blocks(SnapSrc{P, P.pstate, P.pbst, P.pvoff, P.pvlen}, P.z);
+}
+__global__ __launch_bounds__(kThreads) void okv_snap_zpack_kernel(Params P) {
+  zpack_blocks(SnapSrc{P, P.pstate, P.pbst, P.pvoff, P.pvlen}, P.z);
+}
+template <uint32_t kCap>
+__global__ __launch_bounds__(kSearchThreads) void okv_snap_zsearch_kernel(Params P) {
+  __shared__ SearchSmem<kCap> sm;
+  __shared__ int32_t s_st;
+  __shared__ uint32_t s_rows;
+  const SnapSrc src{P, P.pstate, P.pbst, P.pvoff, P.pvlen};
+  search_blocks<kCap>(ZSrc<SnapSrc>{src, P.z, P.pstate, P.pbst, P.pvoff, P.pvlen}, sm, s_st,
+                      s_rows);
+}
+__global__ __launch_bounds__(kSearchThreads) void okv_snap_zglobal_kernel(Params P) {
+  __shared__ int32_t s_st;
+  __shared__ uint32_t s_rows;
+  zglobal_blocks(SnapSrc{P, P.pstate, P.pbst, P.pvoff, P.pvlen}, P.z, s_st, s_rows);
+}
+// One lane per key, behind the resolve: the answering pair of a key found in a zstd
+// segment names the block (zfix_value).
+__global__ __launch_bounds__(kThreads) void okv_snap_zfix_kernel(Params P) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < P.n;
+       i += uint64_t(gridDim.x) * kThreads) {
+    if (P.state[i] != OKV_SNAP_FOUND) continue;
+    const uint32_t t = P.seg[i];
+    if (P.segs[t].comp != OKV_COMP_ZSTD) continue;
+    zfix_value(P.z, i, P.ptpos[P.pbase[i] + (t - P.rlo[i])], P.val_off);
+  }
 }
 
 // ---- resolve -------------------------------------------------------------------
@@ -266,8 +307,8 @@ __global__ __launch_bounds__(kThreads) void okv_snap_resolve_kernel(Params P) {
 }
 
 // ---- values ----------------------------------------------------------------------
-// One wave per found key: its value from its segment into val_arena at the scanned
-// position.  Nothing is written when the values do not fit val_cap.
+// One wave per found key: its value from its segment (a zstd segment under the inflate
+// arms: from the inflated blocks) into val_arena at the scanned position.  Nothing is written when the values do not fit val_cap.
 __global__ __launch_bounds__(kThreads) void okv_snap_values_kernel(Params P) {
   if (P.vscan[P.n] > P.val_cap) return;
   const uint32_t lane = threadIdx.x & 63;
@@ -276,8 +317,11 @@ __global__ __launch_bounds__(kThreads) void okv_snap_values_kernel(Params P) {
        i += waves) {
     if (P.state[i] != OKV_SNAP_FOUND) continue;
     const SegDev& g = P.segs[P.seg[i]];
-    copy_value(g.seg, g.seg_bytes, P.val_off[i], P.val_len[i],
-               reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]), lane);
+    uint4* dst = reinterpret_cast<uint4*>(P.val_arena + P.vscan[i]);
+    if (P.z.on && g.comp == OKV_COMP_ZSTD)
+      copy_value(P.z.bytes, P.z.n_bytes, P.z.abs[i], P.val_len[i], dst, lane);
+    else
+      copy_value(g.seg, g.seg_bytes, P.val_off[i], P.val_len[i], dst, lane);
   }
 }
 
@@ -289,6 +333,8 @@ struct okv_snap {
   okv_ctx* ctx = nullptr;
   uint32_t ns = 0, nb = 0;
   uint64_t max_block = 0;  // largest BlockSize of any index
+  uint64_t max_original = 0;  // largest OriginalSize of a zstd segment's index
+  bool zstd = false, plain = false;  // it has zstd segments / segments of another kind
   uint32_t n_cu = 0;
   okv::DevBuf<okv::snap::SegDev> segs;
   okv::DevBuf<uint32_t> by_prio, blk_seg;
@@ -348,12 +394,22 @@ int run(okv_ctx* ctx, Scratch* s, const okv_snap* sn, Params& P, uint64_t* val_p
     hipLaunchKernelGGL(okv_snap_locate_kernel, dim3(gp), dim3(kThreads), 0, ctx->stream, P);
     OKV_HIP(hipGetLastError());
   }
+  const ZKernels<Params> zk{okv_snap_zplan_kernel, okv_snap_zpack_kernel,
+                            okv_snap_zsearch_kernel<kSmallCap>,
+                            okv_snap_zsearch_kernel<uint32_t(kStage)>, okv_snap_zglobal_kernel,
+                            sn->max_original, sn->plain};
+  if (P.z.on) {
+    if (int rc = reserve(ctx, s->z.abs, size_t(n))) return rc;
+    P.z.abs = s->z.abs.data();
+  }
   if (nb)
     if (int rc = group_and_search(ctx, s, P, np_max, nb, sn->max_block, sn->n_cu,
                                   okv_snap_scatter_kernel, okv_snap_search_kernel<kSmallCap>,
-                                  okv_snap_search_kernel<uint32_t(kStage)>))
+                                  okv_snap_search_kernel<uint32_t(kStage)>,
+                                  P.z.on ? &zk : nullptr))
       return rc;
   hipLaunchKernelGGL(okv_snap_resolve_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
+  if (P.z.on) hipLaunchKernelGGL(okv_snap_zfix_kernel, dim3(gk), dim3(kThreads), 0, ctx->stream, P);
   OKV_HIP(hipGetLastError());
   if (int rc = scan(ctx, s->tsum_in, s->tsum, ValLoad{P.state, P.val_len}, n, P.vscan, val_pos))
     return rc;
@@ -417,7 +473,8 @@ int okv_snap_new(okv_ctx* ctx, const okv_snap_seg* segs, uint32_t n_segs, okv_sn
   snap_route::Image im;
   std::vector<SegDev> sd(n_segs);
   std::vector<uint32_t> by_prio(n_segs, kNone), blk_seg;
-  uint64_t nb = 0, max_block = 0;
+  uint64_t nb = 0, max_block = 0, max_original = 0;
+  bool has_zstd = false, has_plain = false;
   for (uint32_t i = 0; i < n_segs; ++i) {
     const okv_snap_seg& g = segs[i];
     if (!g.index) return set_err(ctx, OKV_E_ARG, "snap: a segment without an index");
@@ -459,11 +516,18 @@ int okv_snap_new(okv_ctx* ctx, const okv_snap_seg* segs, uint32_t n_segs, okv_sn
     if (nb >= kNone) return set_err(ctx, OKV_E_ARG, "snap: 2^32 - 1 blocks or more");
     blk_seg.insert(blk_seg.end(), size_t(ix->nt), i);
     max_block = std::max(max_block, ix->max_block);
+    if (g.compression == OKV_COMP_ZSTD) {
+      max_original = std::max(max_original, ix->max_original);
+      has_zstd = true;
+    } else {
+      has_plain = true;
+    }
   }
   OKV_HIP(hipSetDevice(ctx->device));
   std::unique_ptr<okv_snap> sn(new okv_snap());
   sn->ctx = ctx;
   sn->ns = n_segs, sn->nb = uint32_t(nb), sn->max_block = max_block;
+  sn->max_original = max_original, sn->zstd = has_zstd, sn->plain = has_plain;
   sn->n_cu = cu_count(ctx);
   if (upload(ctx, sn->segs, sd) || upload(ctx, sn->by_prio, by_prio) ||
       upload(ctx, sn->blk_seg, blk_seg) || upload(ctx, sn->arena, im.arena) ||
@@ -509,6 +573,7 @@ int okv_snap_get_rows(okv_ctx* ctx, const okv_snap* sn, const okv_rows* keys, ok
                           sn->last_prefix.data(), sn->last_off.data(), sn->last_len.data()};
   P.segs = sn->segs.data(), P.by_prio = sn->by_prio.data(), P.blk_seg = sn->blk_seg.data();
   P.val_cap = out->val_cap;
+  P.z.on = (flags & OKV_F_GET_ZSTD) && sn->zstd;
   ctx->last_path = OKV_PATH_SNAP_GET;
 
   // the per-key arrays: the caller's, or (host mode) staged behind the key arrays

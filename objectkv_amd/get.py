@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (F_ASYNC, F_DEVICE_PTRS, GET_BLOCK_ERROR, GET_BLOOM_NEGATIVE,  # noqa: F401
+from ._lib import (F_ASYNC, F_DEVICE_PTRS, F_GET_ZSTD, GET_BLOCK_ERROR, GET_BLOOM_NEGATIVE,  # noqa: F401
                    GET_FALLBACK, GET_FOUND, GET_NO_BLOCK, GET_NOT_IN_BLOCK, lib)
 from .bloom import DeviceBloom, Values, pack_keys, rows_call
 from .sst import _ptr
@@ -75,15 +75,17 @@ class GetResult(Values):
 
 def get_rows(owner, seg, seg_bytes, index: DeviceIndex, keys, bloom: DeviceBloom = None,
              compression=_lib.COMP_NONE, values=True, val_cap=None, out=None, sync=True,
-             n_rows=None, key_arena_bytes=None) -> GetResult:
+             n_rows=None, key_arena_bytes=None, zstd=False) -> GetResult:
     """okv_get_rows.  seg: a device pointer (int) or a device uint8 tensor holding the
     segment's seg_bytes bytes.  keys: a list of keys or a dict of numpy arrays key_arena /
     key_off / key_len (host mode), or a dict of device tensors (device mode; then
     ``out`` must hold device tensors state, blk_status, entry, val_off, val_len and
     optionally val_pos and val_arena, and sync=False only enqueues: totals()).
     Host mode: values=False is the index-only call; val_cap defaults to room for every
-    value (two calls: the first sizes the arena).  Raises OkvError (OKV_E_CAPACITY with
-    .result holding the totals)."""
+    value (two calls: the first sizes the arena).  zstd=True sets OKV_F_GET_ZSTD: the
+    touched blocks of a COMP_ZSTD segment are inflated on the device and searched, and
+    val_off counts inside the inflated block ``entry`` names.  Raises OkvError
+    (OKV_E_CAPACITY with .result holding the totals)."""
     segp = seg if isinstance(seg, int) or seg is None else _ptr(seg)
     bh = bloom._h if bloom is not None else None
 
@@ -93,7 +95,7 @@ def get_rows(owner, seg, seg_bytes, index: DeviceIndex, keys, bloom: DeviceBloom
                                   compression, C.byref(o), flags), o
 
     return rows_call(owner, "okv_get_rows", _OUT, call, GetResult, keys, n_rows, key_arena_bytes,
-                     values, val_cap, out, sync)
+                     values, val_cap, out, sync, F_GET_ZSTD if zstd else 0)
 
 
 def totals(owner) -> dict:

@@ -17,7 +17,7 @@ import functools
 import numpy as np
 
 from . import _lib
-from ._lib import (F_ASYNC, F_DEVICE_PTRS, SNAP_DELETED, SNAP_FALLBACK, SNAP_FOUND,  # noqa: F401
+from ._lib import (F_ASYNC, F_DEVICE_PTRS, F_GET_ZSTD, SNAP_DELETED, SNAP_FALLBACK, SNAP_FOUND,  # noqa: F401
                    SNAP_NO_ROWS, SNAP_SEG_ERROR, lib)
 from .bloom import Values, rows_call
 from .sst import _ptr
@@ -106,20 +106,21 @@ class SnapResult(Values):
 
 
 def snap_get_rows(owner, snap: DeviceSnapshot, keys, values=True, val_cap=None, out=None,
-                  sync=True, n_rows=None, key_arena_bytes=None) -> SnapResult:
+                  sync=True, n_rows=None, key_arena_bytes=None, zstd=False) -> SnapResult:
     """okv_snap_get_rows.  keys: a list of keys or a dict of numpy arrays key_arena /
     key_off / key_len (host mode), or a dict of device tensors (device mode; then ``out``
     must hold device tensors state, seg, blk_status, entry, val_off, val_len and
     optionally val_pos and val_arena, and sync=False only enqueues: totals()).
     Host mode: values=False is the index-only call; val_cap defaults to room for every
-    value (two calls: the first sizes the arena).  Raises OkvError (OKV_E_CAPACITY with
-    .result holding the totals)."""
+    value (two calls: the first sizes the arena).  zstd=True sets OKV_F_GET_ZSTD: zstd
+    candidates answer like any other (val_off then counts inside the inflated block).
+    Raises OkvError (OKV_E_CAPACITY with .result holding the totals)."""
     def call(R, ptrs, arena, cap, flags):
         o = _lib.SnapOut(*ptrs, arena, cap, 0, 0, 0, 0, 0, 0)
         return lib().okv_snap_get_rows(owner._ctx, snap._h, C.byref(R), C.byref(o), flags), o
 
     return rows_call(owner, "okv_snap_get_rows", _OUT, call, SnapResult, keys, n_rows,
-                     key_arena_bytes, values, val_cap, out, sync)
+                     key_arena_bytes, values, val_cap, out, sync, F_GET_ZSTD if zstd else 0)
 
 
 def totals(owner) -> dict:

@@ -441,8 +441,10 @@ class Reader:
     def GetRows(self, keys):
         """GetRow for every key in one device call (okv_snap_get_rows): per key the value
         GetRow returns (None for nil), or the SnapshotError / SnapshotPanic Go's GetRow
-        would give (returned, not raised).  Keys the device hands back (OKV_SNAP_FALLBACK)
-        and snapshots with a filter the device refuses go through GetRow."""
+        would give (returned, not raised).  zstd segments answer in the same call
+        (OKV_F_GET_ZSTD: their touched blocks are inflated on the device).  Keys the device
+        hands back (OKV_SNAP_FALLBACK) and snapshots with a filter the device refuses go
+        through GetRow."""
         from . import snap as S
         ks = [_b(k) for k in keys]
         if not ks:
@@ -450,7 +452,7 @@ class Reader:
         ds = self._device_snapshot()
         if ds is None:
             return [self._get_row_outcome(k) for k in ks]
-        res = S.snap_get_rows(self.decoder, ds, ks)
+        res = S.snap_get_rows(self.decoder, ds, ks, zstd=True)
         out = []
         for i, k in enumerate(ks):
             st = int(res.state[i])
@@ -771,6 +773,8 @@ def _block_error(blk_status, seg_id):
     """ReadBlockWithStat's failure (segment_reader.go:303-352) as GetRow passes it on."""
     if blk_status == _lib.BLK_PANIC:
         return SnapshotPanic(f"mustReadBytes: ErrUnexpectedBytesRead in segment {seg_id}")
+    if blk_status == _lib.BLK_ZSTD_ERROR:  # zstd.NewReader / io.Copy (:321-330)
+        return SnapshotError("ZstdError", f"inflating a block of segment {seg_id}")
     kind = "EOF" if blk_status == _lib.BLK_EOF else "ErrUnexpectedBytesRead"
     return SnapshotError(kind, f"reading a block of segment {seg_id}")
 
