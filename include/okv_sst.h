@@ -47,7 +47,10 @@ extern "C" {
                                 still 6 with the snapshot GetRows (okv_snap_*,
                                 OKV_PATH_SNAP_GET): new symbols and one path bit;
                                 still 6 with GetRows on zstd segments (OKV_F_GET_ZSTD,
-                                OKV_GET_INFLATED_MAX): one new flag bit */
+                                OKV_GET_INFLATED_MAX): one new flag bit;
+                                still 6 with Huffman literals in the device zstd encoder
+                                (OKV_F_ZSTD_HUFFMAN, OKV_PATH_ZSTD_HUF): one new flag bit and
+                                one path bit */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -133,6 +136,19 @@ extern "C" {
  * the totals.  okv_last_path gains OKV_PATH_ZSTD when blocks were inflated, and
  * OKV_PATH_ZSTD_REGROW when some outgrew their first region. */
 #define OKV_F_GET_ZSTD 128u
+/* okv_encode_rows / okv_encode_close, only together with OKV_F_ZSTD_NATIVE (and so with
+ * OKV_COMP_ZSTD); without OKV_F_ZSTD_NATIVE the call returns OKV_E_ARG.  The device zstd
+ * encoder then writes a unit's literals as a Compressed_Literals_Block (RFC 8878 3.1.1.3.1:
+ * Huffman-coded, the tree as direct 4-bit weights, code lengths at most 11, one stream up to
+ * 1 023 literals and four above) where at least two byte values occur, none is above 128 and
+ * the section is strictly smaller than the raw one; otherwise the literals stay raw and the
+ * unit's bytes are those without the flag.  The sequences are the same as without the flag.
+ * A unit without sequences may then be a Compressed_Block (its sequences section is the byte
+ * 0).  Per unit the size is never above the size without the flag, so the capacity contract
+ * and the bound of OKV_ZSTD_ENC_UNIT hold unchanged; without the flag every output byte is
+ * what it was.  Opt-in; okv_last_path gains OKV_PATH_ZSTD_HUF when a unit was written so
+ * (DESIGN.md 26). */
+#define OKV_F_ZSTD_HUFFMAN 256u
 #define OKV_GET_INFLATED_MAX (1u << 24)
 /* The most source bytes the encoder puts into one zstd block of a frame, so
  * CompressedSize <= OriginalSize + 3 * ceil(OriginalSize / OKV_ZSTD_ENC_UNIT) + 18. */
@@ -356,7 +372,8 @@ typedef struct okv_encode_out {
 /*
  * Encode rows into one segment on the GPU.  flags: OKV_F_DEVICE_PTRS (rows and
  * every output pointer are device pointers; seg must be 16-byte aligned),
- * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE, OKV_F_ZSTD_NATIVE.  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
+ * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE, OKV_F_ZSTD_NATIVE, OKV_F_ZSTD_HUFFMAN (with
+ * OKV_F_ZSTD_NATIVE only).  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
  * written: call again with seg_cap >= file_bytes and blk_cap >= n_blocks --
  * a call with zero capacities is the size query); OKV_W_INVALID_KEY (bad_row
  * set); OKV_W_NIL_WRITER (strict_go and the last row closed a block, or no
@@ -845,6 +862,8 @@ int okv_profile_read(okv_ctx *ctx, double *ms, uint64_t *calls);
                                 blocks (GetRow, GetRange) in one launch over pinned memory */
 #define OKV_PATH_GET 8192u /* okv_get_rows: okv_get_locate_kernel, the grouping and
                              okv_get_search_kernel */
+#define OKV_PATH_ZSTD_HUF 65536u /* OKV_F_ZSTD_HUFFMAN: at least one unit of the call was written
+                                    with a Compressed_Literals_Block (okv_zenc_unit_huf_kernel) */
 #define OKV_PATH_ZSTD_ENC 16384u /* okv_encode_rows compressed the blocks on the device
                                     (OKV_F_ZSTD_NATIVE: okv_zenc_unit_kernel and its placement) */
 #define OKV_PATH_SNAP_GET 32768u /* okv_snap_get_rows: route, locate, the grouping, the search

@@ -2201,7 +2201,8 @@ int enc_meta(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
 // meta block with compression byte 1.  pl leaves with the segment's sizes; e->desc and
 // e->hash with the BlockStats.
 int enc_write_zstd(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
-                   const okv_encode_opts& po, Plan* pl, uint8_t* seg, bool bloom_dev) {
+                   const okv_encode_opts& po, Plan* pl, uint8_t* seg, bool bloom_dev,
+                   bool huffman) {
   enc_mark(ctx, e, 1);
   int rc;
   if ((rc = reserve(ctx, e->zimg, pl->data_bytes + 64))) return rc;
@@ -2226,9 +2227,11 @@ int enc_write_zstd(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_enco
   if ((rc = enc_pack(ctx, e, R, po, *pl, img, pp, &hashed, &fk_done))) return rc;
   enc_mark(ctx, e, 2);
   uint64_t data_bytes = 0;
+  bool huffman_used = false;
   if ((rc = zstd_enc_run(ctx, img, pl->data_bytes, e->desc.data(), pl->nb, o.block_size, seg,
-                         e->hash.data(), &data_bytes)))
+                         e->hash.data(), &data_bytes, huffman, &huffman_used)))
     return rc;
+  if (huffman_used) ctx->last_path |= OKV_PATH_ZSTD_HUF;
   pl->data_bytes = data_bytes;
   pl->file_bytes = data_bytes + pl->meta_bytes + 25;
   enc_mark(ctx, e, 3);
@@ -2364,6 +2367,8 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   out->meta_hash = 0;
   out->bad_row = kNone;
   const bool zn = flags & OKV_F_ZSTD_NATIVE;  // the device zstd encoder (opt-in)
+  if ((flags & OKV_F_ZSTD_HUFFMAN) && !zn)
+    return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_HUFFMAN without OKV_F_ZSTD_NATIVE");
   if (zn && opts->compression != OKV_COMP_ZSTD)
     return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_NATIVE without OKV_COMP_ZSTD");
   if (opts->compression == OKV_COMP_ZSTD && !zn)
@@ -2460,7 +2465,9 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   }
   const bool bloom_dev = flags & OKV_F_BLOOM_DEVICE;
   if (zn) {
-    if ((rc = enc_write_zstd(ctx, e, R, *opts, po, &pl, seg, bloom_dev))) return rc;
+    if ((rc = enc_write_zstd(ctx, e, R, *opts, po, &pl, seg, bloom_dev,
+                             flags & OKV_F_ZSTD_HUFFMAN)))
+      return rc;
     out->data_bytes = pl.data_bytes;
     out->file_bytes = pl.file_bytes;
   } else if ((rc = enc_write(ctx, e, R, *opts, pl, seg, bloom_dev))) {
@@ -2486,6 +2493,8 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
 
 int okv_encode_close(okv_ctx* ctx, okv_encode_out* out, uint32_t flags) {
   if (!ctx || !out || !out->seg || !out->meta_bytes) return OKV_E_ARG;
+  if ((flags & OKV_F_ZSTD_HUFFMAN) && !(flags & OKV_F_ZSTD_NATIVE))
+    return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_HUFFMAN without OKV_F_ZSTD_NATIVE");
   if (out->seg_cap < out->data_bytes + out->meta_bytes + 25)
     return set_err(ctx, OKV_E_CAPACITY, "seg_cap");
   if (!(flags & OKV_F_DEVICE_PTRS)) {

@@ -39,7 +39,8 @@ static_assert((2u << kHashLog) == kUnit, "the hash table and the bitstream share
 static_assert(kUnit <= 32768, "positions, lengths and distances are kept in 16 bits");
 
 struct ZTot {
-  unsigned long long n_units, bound_bytes, data_bytes, pad;
+  unsigned long long n_units, bound_bytes, data_bytes;
+  unsigned long long huf_seen;  // OKV_F_ZSTD_HUFFMAN: a unit of the call wrote Huffman literals
 };
 
 __host__ __device__ inline uint64_t units_of(uint64_t orig) { return (orig + kUnit - 1) / kUnit; }
@@ -131,6 +132,46 @@ __device__ __forceinline__ void or_bits(uint32_t* words, uint32_t pos, uint64_t 
   if (a2 && w + 2 < kWords) atomicOr(&words[w + 2], a2);
 }
 
+// or_bits over `nw` words anywhere in LDS (the Huffman streams).
+__device__ __forceinline__ void or_bits_n(uint32_t* words, uint32_t nw, uint32_t pos, uint64_t v) {
+  const uint32_t w = pos >> 5, sh = pos & 31;
+  const uint64_t a = v << sh;
+  const uint32_t a0 = uint32_t(a), a1 = uint32_t(a >> 32), a2 = sh ? uint32_t(v >> (64 - sh)) : 0;
+  if (a0 && w < nw) atomicOr(&words[w], a0);
+  if (a1 && w + 1 < nw) atomicOr(&words[w + 1], a1);
+  if (a2 && w + 2 < nw) atomicOr(&words[w + 2], a2);
+}
+
+// Where the Huffman phases (OKV_F_ZSTD_HUFFMAN) keep their tables: words of `tab`, which is
+// dead between phase D and the point where H zeroes it.
+constexpr uint32_t kHufHist = 0;     // [256] literal histogram
+constexpr uint32_t kHufCode = 256;   // [kHufSyms] (value << 4) | length
+constexpr uint32_t kHufBits = 512;   // [kT] code bits of a thread's literals, then of the later ones
+constexpr uint32_t kHufTot = 768;    // [0..3] code bits per stream, [4] longest code, [5] largest symbol
+constexpr uint32_t kHufWorkAt = 1024;
+static_assert(kHufWorkAt + kHufWork <= kWords && kHufSyms <= 256, "the Huffman tables fit tab");
+
+// The unit's literals in order, by the whole workgroup: wave w takes the sequences of threads
+// 64w .. 64w+63 (c sequences a thread, their literal and match lengths scanned in s_lit and
+// s_ml), then all threads the tail behind the last sequence.  put(k, p): literal k of the
+// unit's literals is byte p of the unit.
+template <class Put>
+__device__ __forceinline__ void each_literal(const uint16_t* sq, const uint32_t* s_lit,
+                                             const uint32_t* s_ml, uint32_t ns, uint32_t c,
+                                             uint32_t tot_lit, uint32_t lit_tail, uint32_t n,
+                                             Put put) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, t0 = tid & ~63u;
+  const uint32_t ka = min(ns, t0 * c), kb = min(ns, (t0 + 64) * c);
+  uint32_t lp = s_lit[t0], sp = s_lit[t0] + s_ml[t0];
+  for (uint32_t k = ka; k < kb; ++k) {
+    const uint32_t ll = sq[3 * k], ml = sq[3 * k + 1];
+    for (uint32_t j = lane; j < ll; j += 64) put(lp + j, sp + j);
+    lp += ll;
+    sp += ll + ml;
+  }
+  for (uint32_t j = tid; j < n - lit_tail; j += kT) put(tot_lit + j, lit_tail + j);
+}
+
 // Z2.  The phases, each ended by a barrier:
 //  A  stage the unit (LDS DMA), copy the three encode tables, clear the hash table
 //  B  hash of every 4-byte window
@@ -143,7 +184,19 @@ __device__ __forceinline__ void or_bits(uint32_t* words, uint32_t pos, uint64_t 
 //  F  lanes 0-2: the three FSE state chains, last sequence to first
 //  G  bit counts and literal counts per thread range, their scan, Compressed or Raw
 //  H  every sequence's bits ORed into place; literals, headers and bitstream stored
-__global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
+// HUF (okv_zenc_unit_huf_kernel, OKV_F_ZSTD_HUFFMAN) adds between G and H, with the parse and
+// the sequences unchanged:
+//  L1 the literals gathered behind the sequences in `cand` (6 ns bytes of sequences, then at
+//     most n - 4 ns literals; without a sequence they are the staged unit), their histogram
+//     by LDS atomics
+//  L2 one lane: code lengths and canonical codes (okv_zstd_enc.hpp); not eligible -> raw
+//  L3 every thread sums the code bits of its contiguous literals of one stream; one lane
+//     per stream scans them; the section's size, Huffman or raw, Compressed or Raw
+//  L4 the codes ORed into the stream words behind the gathered literals (they are fewer
+//     bytes than the literals: 6 ns + 2 (n - 4 ns) <= 65 536), last literal first
+//  L5 header, tree description, jump table and streams stored
+template <bool HUF>
+__device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long long* huf_seen) {
   __shared__ UnitSmem sm;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t u = blockIdx.x;
@@ -331,7 +384,85 @@ __global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
     }
     __syncthreads();
     nlit = sm.tot_lit + (n - lit_tail);
-    csz = compressed_size(nlit, ns, uint64_t(sm.tot_bits) + 18);
+    if constexpr (!HUF) {
+      csz = compressed_size(nlit, ns, uint64_t(sm.tot_bits) + 18);
+      comp = csz < n;
+    }
+  }
+  // the Huffman phases: `huf` says the literals section is a Compressed_Literals_Block of
+  // `litsec` bytes whose streams take hb0 .. hb3 bytes
+  bool huf = false;
+  uint32_t litsec = 0, hmb = 0, hlast = 0, hsum = 0, hlo = 0, hhi = 0, hstream = 0;
+  uint32_t hb0 = 0, hb1 = 0, hb2 = 0, hb3 = 0;
+  const auto streams_before = [&](uint32_t s) {  // bytes of the streams before stream s
+    return (s > 0 ? hb0 : 0) + (s > 1 ? hb1 : 0) + (s > 2 ? hb2 : 0);
+  };
+  uint8_t* cb = reinterpret_cast<uint8_t*>(sm.cand);
+  const uint8_t* lits = sb;
+  if constexpr (HUF) {
+    uint32_t* hist = sm.tab + kHufHist;
+    uint32_t* code = sm.tab + kHufCode;
+    uint32_t* tbits = sm.tab + kHufBits;
+    uint32_t* htot = sm.tab + kHufTot;
+    // L1
+    hist[tid] = 0;
+    __syncthreads();
+    if (ns) {
+      uint8_t* lb = cb + 6 * ns;
+      each_literal(sq, sm.s_lit, sm.s_ml, ns, c, sm.tot_lit, lit_tail, n,
+                   [&](uint32_t k, uint32_t p) {
+                     const uint32_t v = sb[p];
+                     lb[k] = uint8_t(v);
+                     atomicAdd(&hist[v], 1u);
+                   });
+      lits = lb;
+    } else {
+      nlit = n;
+      for (uint32_t j = tid; j < n; j += kT) atomicAdd(&hist[sb[j]], 1u);
+    }
+    __syncthreads();
+    // L2
+    if (tid == 0) {
+      const uint32_t mb = huf_lengths(hist, code, sm.tab + kHufWorkAt);
+      htot[4] = mb;
+      htot[5] = mb ? huf_codes(code, mb, code, sm.tab + kHufWorkAt) : 0;
+    }
+    __syncthreads();
+    hmb = htot[4], hlast = htot[5];
+    litsec = lit_header_size(nlit) + nlit;
+    if (hmb) {
+      // L3: 256 threads on the one stream, or 64 on each of four
+      const uint32_t nstr = huf_streams(nlit), tps = kT / nstr;
+      hstream = tid / tps;
+      const uint32_t j = tid % tps, cnt = huf_stream_len(nlit, hstream);
+      const uint32_t first = hstream * huf_stream_len(nlit, 0), ch = (cnt + tps - 1) / tps;
+      hlo = first + min(cnt, j * ch), hhi = first + min(cnt, j * ch + ch);
+      uint32_t own = 0;
+      for (uint32_t i = hlo; i < hhi; ++i) own += code[lits[i]] & 15u;
+      tbits[tid] = own;
+      __syncthreads();
+      if (tid < nstr) {  // one lane per stream: the bits of the later literals, in place
+        uint32_t run = 0;
+        for (uint32_t k = tps; k-- > 0;) {
+          const uint32_t x = tbits[tid * tps + k];
+          tbits[tid * tps + k] = run;
+          run += x;
+        }
+        htot[tid] = run;
+      }
+      __syncthreads();
+      hb0 = huf_stream_bytes(htot[0]);
+      if (nstr == 4)
+        hb1 = huf_stream_bytes(htot[1]), hb2 = huf_stream_bytes(htot[2]),
+        hb3 = huf_stream_bytes(htot[3]);
+      hsum = hb0 + hb1 + hb2 + hb3;
+      huf = huf_wins(nlit, hlast, hsum);
+      if (huf) litsec = huf_section_size(nlit, hlast, hsum);
+    }
+    // every thread has read what decides its way from here (htot); only now may a thread
+    // that goes straight to H, or to the Raw_Block, write into tab
+    __syncthreads();
+    csz = block_content_size(litsec, ns, ns ? uint64_t(sm.tot_bits) + 18 : 0);
     comp = csz < n;
   }
   if (!comp) {  // Raw_Block
@@ -341,6 +472,59 @@ __global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
     }
     for (uint32_t j = tid; j < n; j += kT) out[3 + j] = sb[j];
     return;
+  }
+  if constexpr (HUF) {
+    if (huf) {
+      // L4: the stream words lie behind the literals (behind nothing without a sequence:
+      // the literals are then the staged unit)
+      const uint32_t hoff = ns ? (6 * ns + nlit + 3) & ~3u : 0;
+      uint32_t* hw = reinterpret_cast<uint32_t*>(cb + hoff);
+      const uint32_t nw = min((hsum + 3) / 4, (2 * kUnit - hoff) / 4);
+      const uint32_t* code = sm.tab + kHufCode;
+      for (uint32_t i = tid; i < nw; i += kT) hw[i] = 0;
+      __syncthreads();
+      uint32_t pos = 8 * streams_before(hstream) + sm.tab[kHufBits + tid], an = 0;
+      uint64_t acc = 0;
+      for (uint32_t i = hhi; i-- > hlo;) {
+        const uint32_t cd = code[lits[i]];
+        acc |= uint64_t(cd >> 4) << an;
+        an += cd & 15u;
+        if (an > 64 - kHufMaxBits) {
+          or_bits_n(hw, nw, pos, acc);
+          pos += an;
+          acc = 0, an = 0;
+        }
+      }
+      if (an) or_bits_n(hw, nw, pos, acc);
+      if (tid < huf_streams(nlit))  // the end mark of stream `tid`, above its last code
+        or_bits_n(hw, nw, 8 * streams_before(tid) + sm.tab[kHufTot + tid], 1);
+      __syncthreads();
+      // L5
+      const uint32_t hh = huf_header_size(nlit), ts = huf_tree_size(hlast);
+      const uint32_t jt = huf_streams(nlit) == 4 ? 6 : 0;
+      uint8_t* sec = out + 3;
+      if (tid == 0) {
+        huf_header(sec, nlit, ts + jt + hsum);
+        atomicOr(huf_seen, 1ull);
+      }
+      for (uint32_t k = tid; k < ts; k += kT) sec[hh + k] = huf_tree_byte(code, hmb, hlast, k);
+      if (jt && tid < 3) {
+        const uint32_t by = tid == 0 ? hb0 : tid == 1 ? hb1 : hb2;
+        sec[hh + ts + 2 * tid] = uint8_t(by);
+        sec[hh + ts + 2 * tid + 1] = uint8_t(by >> 8);
+      }
+      for (uint32_t j = tid; j < hsum; j += kT)
+        sec[hh + ts + jt + j] = uint8_t(hw[j >> 2] >> (8 * (j & 3)));
+      __syncthreads();  // the code table is read; H takes tab
+    }
+    if (!ns) {  // literals only: the sequences section is the byte 0
+      if (tid == 0) {
+        block_header(out, last, kBlockCompressed, csz);
+        out[3 + litsec] = 0;
+        P.usize[u] = 3 + csz;
+      }
+      return;
+    }
   }
   // H
   const uint32_t tot_bits = sm.tot_bits;
@@ -365,24 +549,15 @@ __global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
   }
   const uint32_t lh = lit_header_size(nlit);
   uint8_t* lit_out = out + 3 + lh;
-  {  // literals: wave w takes the sequences of threads 64w .. 64w+63
-    const uint32_t t0 = wave * 64;
-    const uint32_t ka = min(ns, t0 * c), kb = min(ns, (t0 + 64) * c);
-    uint32_t lp = sm.s_lit[t0], sp = sm.s_lit[t0] + sm.s_ml[t0];
-    for (uint32_t k = ka; k < kb; ++k) {
-      const uint32_t ll = sq[3 * k], ml = sq[3 * k + 1];
-      for (uint32_t j = lane; j < ll; j += 64) lit_out[lp + j] = sb[sp + j];
-      lp += ll;
-      sp += ll + ml;
-    }
-    for (uint32_t j = tid; j < n - lit_tail; j += kT) lit_out[sm.tot_lit + j] = sb[lit_tail + j];
-  }
+  if (!HUF || !huf)
+    each_literal(sq, sm.s_lit, sm.s_ml, ns, c, sm.tot_lit, lit_tail, n,
+                 [&](uint32_t k, uint32_t p) { lit_out[k] = sb[p]; });
   __syncthreads();  // the bitstream words are complete
-  uint8_t* seq_out = lit_out + nlit;
+  uint8_t* seq_out = HUF ? out + 3 + litsec : lit_out + nlit;
   const uint32_t sh = nseq_header_size(ns);
   if (tid == 0) {
     block_header(out, last, kBlockCompressed, csz);
-    lit_header(out + 3, nlit);
+    if (!HUF || !huf) lit_header(out + 3, nlit);
     nseq_header(seq_out, ns);
     seq_out[sh] = 0;  // Predefined_Mode x 3
     P.usize[u] = 3 + csz;
@@ -390,6 +565,16 @@ __global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
   const uint32_t nbytes = (tot_bits + 18 + 7) >> 3;
   for (uint32_t j = tid; j < nbytes; j += kT)
     seq_out[sh + 1 + j] = uint8_t(sm.tab[j >> 2] >> (8 * (j & 3)));
+}
+
+__global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
+  unit_body<false>(P, nullptr);
+}
+// The same unit with Huffman-coded literals where they are smaller; *huf_seen becomes 1 when
+// a unit of the launch wrote a Compressed_Literals_Block.
+__global__ __launch_bounds__(kT) void okv_zenc_unit_huf_kernel(UnitParams P,
+                                                               unsigned long long* huf_seen) {
+  unit_body<true>(P, huf_seen);
 }
 
 // Z4.  One workgroup; thread t owns a contiguous range of blocks.
@@ -533,7 +718,8 @@ int zstd_enc_bound(okv_ctx* ctx, const Desc* img_desc, uint64_t nb, uint64_t D,
 }
 
 int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* desc, uint64_t nb,
-                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes) {
+                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes, bool huffman,
+                 bool* huffman_used) {
   zenc::Scratch* s = ctx->zenc;
   if (!s || s->nb != nb || nb >= (uint64_t(1) << 32))
     return set_err(ctx, OKV_E_ARG, "zstd encode: no plan for these blocks");
@@ -557,8 +743,16 @@ int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* des
   up.nb = nb;
   up.ubuf = s->ubuf.data();
   up.usize = s->usize.data();
-  hipLaunchKernelGGL(zenc::okv_zenc_unit_kernel, dim3(uint32_t(nu)), dim3(zenc::kT), 0, ctx->stream,
-                     up);
+  // ZTot::huf_seen comes back with the sizes' read-back
+  unsigned long long* huf_seen = &s->d_tot.data()->huf_seen;
+  if (huffman) {
+    OKV_HIP(hipMemsetAsync(huf_seen, 0, sizeof *huf_seen, ctx->stream));
+    hipLaunchKernelGGL(zenc::okv_zenc_unit_huf_kernel, dim3(uint32_t(nu)), dim3(zenc::kT), 0,
+                       ctx->stream, up, huf_seen);
+  } else {
+    hipLaunchKernelGGL(zenc::okv_zenc_unit_kernel, dim3(uint32_t(nu)), dim3(zenc::kT), 0,
+                       ctx->stream, up);
+  }
   launch_hash(ctx->stream, img, img_bytes, s->hdesc.data(), uint32_t(nb), s->raw_hash.data());
   hipLaunchKernelGGL(zenc::okv_zenc_size_kernel, dim3(1), dim3(1024), 0, ctx->stream,
                      s->hdesc.data(), s->ubase.data(), s->usize.data(), nb, D, desc,
@@ -566,6 +760,7 @@ int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* des
   OKV_HIP(hipGetLastError());
   if ((rc = zenc::read_tot(ctx, s))) return rc;
   *data_bytes = s->h_tot->data_bytes;
+  *huffman_used = huffman && s->h_tot->huf_seen != 0;
   if (*data_bytes > s->h_tot->bound_bytes)
     return set_err(ctx, OKV_E_HIP, "zstd encode: frames larger than their bound");
   zenc::PlaceParams pp;

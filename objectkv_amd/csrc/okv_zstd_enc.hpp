@@ -8,7 +8,8 @@
 //
 // What the encoder emits and nothing else: Raw_Literals_Block, all three sequence
 // tables in Predefined_Mode, every offset as Offset_Value = offset + 3 (no repeat
-// codes), Raw_Blocks.  Huffman literals and custom FSE tables are not here.
+// codes), Raw_Blocks; and under OKV_F_ZSTD_HUFFMAN a Compressed_Literals_Block with
+// direct weights where it is smaller.  Custom FSE tables are not here.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -286,6 +287,165 @@ OKV_ZE_HD uint32_t nseq_header(uint8_t* p, uint32_t n) {
 OKV_ZE_HD uint32_t compressed_size(uint32_t nlit, uint32_t nseq, uint64_t bits) {
   return lit_header_size(nlit) + nlit + nseq_header_size(nseq) + 1 + uint32_t((bits + 7) >> 3);
 }
+// A block's size from the size of its literals section (raw or Huffman) and its sequences.
+// Without sequences the sequences section is the single byte 0.
+OKV_ZE_HD uint32_t block_content_size(uint32_t litsec, uint32_t nseq, uint64_t bits) {
+  return litsec + nseq_header_size(nseq) + (nseq ? 1 + uint32_t((bits + 7) >> 3) : 0);
+}
+
+// ---- Huffman-coded literals (OKV_F_ZSTD_HUFFMAN; RFC 8878 3.1.1.3.1, 4.2) ---------
+// A unit's literals become a Compressed_Literals_Block only if at least two byte values
+// occur, none is above kHufMaxSym (the tree description lists direct 4-bit weights: header
+// byte 127 + number of listed weights, and 255 - 127 = 128 listed weights describe the
+// symbols 0 .. 128), and the section is strictly smaller than the raw one.  Code lengths
+// are the length-limited optimum of package-merge at kHufMaxBits; weights, the canonical
+// codes and the stream split are the RFC's.  No FSE-compressed weights, no RLE and no
+// treeless literals.
+constexpr uint32_t kHufMaxBits = 11;
+constexpr uint32_t kHufMaxSym = 128;
+constexpr uint32_t kHufSyms = kHufMaxSym + 1;
+constexpr uint32_t kHufItems = 2 * kHufSyms - 2;  // items package-merge keeps per level
+// Words of work space huf_lengths needs: the sorted leaves, two item lists, one flag
+// byte per item and level.
+constexpr uint32_t kHufWork = kHufSyms + 2 * kHufItems + kHufMaxBits * kHufItems / 4;
+static_assert(kHufItems % 4 == 0, "a level's flag bytes are whole words");
+
+// Code lengths from a histogram of 256 counts (their sum below 2^23): len[s] for
+// s <= kHufMaxSym, 0 for an absent symbol.  Returns the longest length, or 0 when the
+// literals are not eligible (fewer than two distinct values, or a value above kHufMaxSym;
+// len is then not meaningful).  Package-merge (Larmore and Hirschberg): level 0 is the
+// leaves in order of (count, symbol); a level is the leaves merged with the pairs of the
+// level below, a leaf before a package of equal weight; the first 2n - 2 items of the last
+// level are taken, and going down, twice as many items as packages were taken above.  A
+// leaf's length is the number of levels that took it.
+OKV_ZE_HD uint32_t huf_lengths(const uint32_t* hist, uint32_t* len, uint32_t* work) {
+  uint32_t* key = work;                      // (count << 8) | symbol, ascending
+  uint32_t* cur = work + kHufSyms;           // item weights of the level being built
+  uint32_t* prev = cur + kHufItems;          // ... of the level below
+  uint8_t* flag = reinterpret_cast<uint8_t*>(prev + kHufItems);  // 1: the item is a package
+  uint32_t n = 0;
+  for (uint32_t s = kHufMaxSym + 1; s < 256; ++s)  // (first: the common way out)
+    if (hist[s]) return 0;
+  for (uint32_t s = 0; s <= kHufMaxSym; ++s) {
+    const uint32_t c = hist[s];
+    if (!c) continue;
+    uint32_t i = n++;  // insertion: counts ascending, equal counts by symbol
+    const uint32_t k = (c << 8) | s;
+    for (; i > 0 && key[i - 1] > k; --i) key[i] = key[i - 1];
+    key[i] = k;
+  }
+  if (n < 2) return 0;
+  const uint32_t keep = 2 * n - 2;
+  // no code of n symbols is deeper than n - 1: fewer levels give the same lengths' cost
+  const uint32_t levels = n - 1 < kHufMaxBits ? n - 1 : kHufMaxBits;
+  for (uint32_t i = 0; i < n; ++i) prev[i] = key[i] >> 8;
+  uint32_t plen = n;
+  for (uint32_t lv = 1; lv < levels; ++lv) {
+    uint8_t* fl = flag + lv * kHufItems;
+    const uint32_t np = plen / 2;
+    uint32_t i = 0, j = 0, cnt = 0;
+    while (cnt < keep && (i < n || j < np)) {
+      const uint32_t wl = i < n ? key[i] >> 8 : 0xFFFFFFFFu;
+      const uint32_t wp = j < np ? prev[2 * j] + prev[2 * j + 1] : 0xFFFFFFFFu;
+      const bool leaf = i < n && wl <= wp;
+      cur[cnt] = leaf ? wl : wp;
+      fl[cnt] = leaf ? 0 : 1;
+      i += leaf ? 1 : 0;
+      j += leaf ? 0 : 1;
+      ++cnt;
+    }
+    plen = cnt;
+    uint32_t* t = cur;
+    cur = prev;
+    prev = t;
+  }
+  // (a complete code of n <= 2^levels leaves exists: the last level holds `keep` items)
+  uint32_t* depth = cur;  // per sorted leaf; the item lists are done with
+  for (uint32_t i = 0; i < n; ++i) depth[i] = 0;
+  uint32_t take = keep < plen ? keep : plen;
+  for (uint32_t lv = levels; lv-- > 0 && take;) {
+    uint32_t packs = 0;
+    if (lv) {
+      const uint8_t* fl = flag + lv * kHufItems;
+      for (uint32_t i = 0; i < take; ++i) packs += fl[i];
+    }
+    const uint32_t leaves = take - packs;
+    for (uint32_t i = 0; i < leaves; ++i) depth[i] += 1;
+    take = 2 * packs;
+  }
+  for (uint32_t s = 0; s < kHufSyms; ++s) len[s] = 0;
+  for (uint32_t i = 0; i < n; ++i) len[key[i] & 255u] = depth[i];
+  return depth[0];
+}
+
+// The canonical codes (RFC 8878 4.2.1.3, HUF_buildCTable's order): the longest codes start
+// at 0 and count up by symbol value; a shorter length starts at half of where the longer
+// ones ended.  code[s] = (value << 4) | length, 0 for an absent symbol; `len` and `code`
+// may be the same array.  Returns the largest present symbol.  work: 32 words.
+OKV_ZE_HD uint32_t huf_codes(const uint32_t* len, uint32_t max_bits, uint32_t* code,
+                             uint32_t* work) {
+  uint32_t* per = work;       // symbols per length
+  uint32_t* val = work + 16;  // next value per length
+  for (uint32_t b = 0; b < 16; ++b) per[b] = 0;
+  uint32_t last = 0;
+  for (uint32_t s = 0; s < kHufSyms; ++s)
+    if (len[s]) per[len[s]] += 1, last = s;
+  uint32_t min = 0;
+  for (uint32_t b = max_bits; b > 0; --b) {
+    val[b] = min;
+    min = (min + per[b]) >> 1;
+  }
+  for (uint32_t s = 0; s < kHufSyms; ++s) {
+    const uint32_t b = len[s];
+    code[s] = b ? ((val[b]++) << 4) | b : 0;
+  }
+  return last;
+}
+// The weight the tree description lists for a code of `bits` bits (0: absent).
+OKV_ZE_HD uint32_t huf_weight(uint32_t bits, uint32_t max_bits) {
+  return bits ? max_bits + 1 - bits : 0;
+}
+// Tree description: header byte, then the weights of the symbols below `last` (the
+// largest present one, whose weight is implied), two a byte, high nibble first.
+OKV_ZE_HD uint32_t huf_tree_size(uint32_t last) { return 1 + (last + 1) / 2; }
+OKV_ZE_HD uint8_t huf_tree_byte(const uint32_t* code, uint32_t max_bits, uint32_t last,
+                                uint32_t k) {  // byte k of the description, k < huf_tree_size
+  if (k == 0) return uint8_t(127 + last);
+  const uint32_t s = 2 * (k - 1);
+  const uint32_t hi = huf_weight(code[s] & 15u, max_bits);
+  const uint32_t lo = s + 1 < last ? huf_weight(code[s + 1] & 15u, max_bits) : 0;
+  return uint8_t((hi << 4) | lo);
+}
+// One stream up to 1 023 literals, else four: the first three of (nlit + 3) / 4 literals.
+OKV_ZE_HD uint32_t huf_streams(uint32_t nlit) { return nlit <= 1023 ? 1u : 4u; }
+OKV_ZE_HD uint32_t huf_stream_len(uint32_t nlit, uint32_t s) {
+  if (nlit <= 1023) return nlit;
+  const uint32_t seg = (nlit + 3) / 4;
+  return s < 3 ? seg : nlit - 3 * seg;
+}
+// A stream of `bits` code bits: the end mark, padded to a byte.
+OKV_ZE_HD uint32_t huf_stream_bytes(uint32_t bits) { return (bits + 1 + 7) >> 3; }
+// Compressed_Literals_Block header: Size_Format 00 (one stream, 10-bit sizes), 10 (14 bits)
+// or 11 (18 bits); 01 is never written.  `comp` counts the tree description, the jump
+// table and the streams.
+OKV_ZE_HD uint32_t huf_header_size(uint32_t nlit) { return nlit <= 1023 ? 3 : nlit <= 16383 ? 4 : 5; }
+OKV_ZE_HD uint32_t huf_header(uint8_t* p, uint32_t nlit, uint32_t comp) {
+  const uint32_t hs = huf_header_size(nlit);
+  const uint32_t sf = hs == 3 ? 0 : hs == 4 ? 2 : 3, sb = hs == 3 ? 10 : hs == 4 ? 14 : 18;
+  const uint64_t v = 2u | (sf << 2) | (uint64_t(nlit) << 4) | (uint64_t(comp) << (4 + sb));
+  for (uint32_t i = 0; i < hs; ++i) p[i] = uint8_t(v >> (8 * i));
+  return hs;
+}
+// The section's size from the sum of its streams' bytes.
+OKV_ZE_HD uint32_t huf_section_size(uint32_t nlit, uint32_t last, uint32_t stream_bytes) {
+  return huf_header_size(nlit) + huf_tree_size(last) + (huf_streams(nlit) == 4 ? 6 : 0) +
+         stream_bytes;
+}
+// The rule: Huffman only when strictly smaller than the raw section.
+OKV_ZE_HD bool huf_wins(uint32_t nlit, uint32_t last, uint32_t stream_bytes) {
+  return huf_section_size(nlit, last, stream_bytes) < lit_header_size(nlit) + nlit;
+}
+
 // Upper bound of a frame for `orig` raw bytes: every unit a Raw_Block.
 OKV_ZE_HD uint64_t frame_bound(uint64_t orig) {
   const uint64_t units = orig ? (orig + kUnit - 1) / kUnit : 1;

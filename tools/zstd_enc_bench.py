@@ -17,7 +17,15 @@ checksums, sizes, placement, block hashes | meta block).
 Reported: GiB/s of raw bytes, output ratio (sum of CompressedSize / sum of OriginalSize),
 and the uncompressed encode of the same rows beside it.
 
-Run from the repository root:  python tools/zstd_enc_bench.py [--blocks N] [--log PATH]
+--huffman adds the encoder with Huffman-coded literals (OKV_F_ZSTD_HUFFMAN) as
+a third arm beside the other two, in the same session, and a third row set:
+  (c) 400 000 text rows (ASCII keys, JSON-like values: no byte above 128, which the
+      Huffman arm needs; the keys of (a) and the values of (b) hold random bytes) at
+      T = 57 344, D = 65 536
+--no-cpu leaves the libzstd runs out.
+
+Run from the repository root:  python tools/zstd_enc_bench.py [--blocks N] [--huffman]
+                                      [--no-cpu] [--log PATH]
 """
 from __future__ import annotations
 
@@ -78,6 +86,32 @@ def cz_rows(nblocks, seed=5, threshold=57344):
     return r, blocks
 
 
+def text_rows(n):
+    """ASCII keys and JSON-like values as SoA arrays, and the raw bytes of blocks cut at 57 344."""
+    keys = [b"key%09d" % (3 * i) for i in range(n)]
+    vals = [b'{"id":%d,"name":"user%d","score":%d,"active":%s,"note":"%s"}' %
+            (100000 + 7 * i, 5000 + i, (i * 37) % 1000, b"true" if i % 3 else b"false",
+             b"lorem ipsum dolor sit amet "[:i % 28]) for i in range(n)]
+    kl = np.array([len(k) for k in keys], np.uint16)
+    vl = np.array([len(v) for v in vals], np.uint32)
+    ko, vo = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    ko[1:] = np.cumsum(kl[:-1], dtype=np.uint64)
+    vo[1:] = np.cumsum(vl[:-1], dtype=np.uint64)
+    r = dict(key_arena=np.frombuffer(b"".join(keys) + bytes(16), np.uint8), key_off=ko, key_len=kl,
+             val_arena=np.frombuffer(b"".join(vals) + bytes(16), np.uint8), val_off=vo, val_len=vl)
+    blocks, cur = [], []
+    size = 0
+    for k, v in zip(keys, vals):
+        cur.append(len(k).to_bytes(2, "little") + len(v).to_bytes(4, "little") + k + v)
+        size += 6 + len(k) + len(v)
+        if size >= 57344:
+            blocks.append(b"".join(cur))
+            cur, size = [], 0
+    if cur:
+        blocks.append(b"".join(cur))
+    return r, blocks
+
+
 def to_dev(r):
     signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint16): np.int16,
               np.dtype(np.uint32): np.int32}
@@ -102,11 +136,16 @@ def timed(enc, fn, warm=2, reps=5):
     return ms
 
 
-def device_case(enc, tag, t, n, T, D, kab, vab):
-    kw = dict(key_arena_bytes=kab, val_arena_bytes=vab)
+def device_case(enc, tag, t, n, T, D, kab, vab, huffman=False):
     res = {}
-    for name, comp, zn in (("uncompressed", okv.sst.COMP_NONE, False),
-                           ("zstd_native", okv.sst.COMP_ZSTD, True)):
+    arms = [("uncompressed", okv.sst.COMP_NONE, False, False),
+            ("zstd_native", okv.sst.COMP_ZSTD, True, False)]
+    if huffman:
+        arms.append(("zstd_native+huffman", okv.sst.COMP_ZSTD, True, True))
+    for name, comp, zn, zh in arms:
+        kw = dict(key_arena_bytes=kab, val_arena_bytes=vab)
+        if zh:  # (named only here: the tool also times builds from before the flag)
+            kw["zstd_huffman"] = True
         try:
             enc.encode_device(t, n, {}, T, D, comp, False, zstd_native=zn, **kw)
         except okv.OkvError as e:
@@ -161,6 +200,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=16384)
     ap.add_argument("--cpu-blocks", type=int, default=2048)
+    ap.add_argument("--huffman", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -171,8 +212,9 @@ def main():
     r, blocks = cz_rows(a.blocks)
     t = to_dev(r)
     device_case(enc, f"(a) CZ rows x{a.blocks}", t, int(r["key_len"].size), 57344, 65536,
-                int(r["key_arena"].size), int(r["val_arena"].size))
-    cpu_case("(a)", blocks[:a.cpu_blocks])
+                int(r["key_arena"].size), int(r["val_arena"].size), a.huffman)
+    if not a.no_cpu:
+        cpu_case("(a)", blocks[:a.cpu_blocks])
     del t, r
     # ---- (b) ----
     n = 100_000
@@ -183,11 +225,21 @@ def main():
              val_off=torch.empty(n, dtype=torch.int64, device="cuda"),
              val_len=torch.empty(n, dtype=torch.int32, device="cuda"))
     enc.synth_fixed_device(1, 0, n, 16, 64, t)
-    device_case(enc, "(b) 100 000 fixed rows", t, n, 3584, 4096, n * 16, n * 64)
-    ka, va = t["key_arena"].cpu().numpy(), t["val_arena"].cpu().numpy()
-    recs = [b"\x10\x00\x40\x00\x00\x00" + ka[16 * i:16 * i + 16].tobytes() +
-            va[64 * i:64 * i + 64].tobytes() for i in range(n)]
-    cpu_case("(b)", [b"".join(recs[i:i + 42]) for i in range(0, n, 42)])
+    device_case(enc, "(b) 100 000 fixed rows", t, n, 3584, 4096, n * 16, n * 64, a.huffman)
+    if not a.no_cpu:
+        ka, va = t["key_arena"].cpu().numpy(), t["val_arena"].cpu().numpy()
+        recs = [b"\x10\x00\x40\x00\x00\x00" + ka[16 * i:16 * i + 16].tobytes() +
+                va[64 * i:64 * i + 64].tobytes() for i in range(n)]
+        cpu_case("(b)", [b"".join(recs[i:i + 42]) for i in range(0, n, 42)])
+    # ---- (c) ----
+    if a.huffman:
+        del t
+        r, blocks = text_rows(400_000)
+        t = to_dev(r)
+        device_case(enc, "(c) 400 000 text rows", t, int(r["key_len"].size), 57344, 65536,
+                    int(r["key_arena"].size), int(r["val_arena"].size), True)
+        if not a.no_cpu:
+            cpu_case("(c)", blocks[:a.cpu_blocks])
     enc.close()
     if a.log:
         os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
