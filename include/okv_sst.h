@@ -50,7 +50,10 @@ extern "C" {
                                 OKV_GET_INFLATED_MAX): one new flag bit;
                                 still 6 with Huffman literals in the device zstd encoder
                                 (OKV_F_ZSTD_HUFFMAN, OKV_PATH_ZSTD_HUF): one new flag bit and
-                                one path bit */
+                                one path bit;
+                                still 6 with FSE-compressed Huffman weights there
+                                (OKV_F_ZSTD_HUF_FSE, OKV_PATH_ZSTD_HUF_FSE): one new flag bit
+                                and one path bit */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -149,6 +152,16 @@ extern "C" {
  * what it was.  Opt-in; okv_last_path gains OKV_PATH_ZSTD_HUF when a unit was written so
  * (DESIGN.md 26). */
 #define OKV_F_ZSTD_HUFFMAN 256u
+/* okv_encode_rows / okv_encode_close, only together with OKV_F_ZSTD_HUFFMAN (and so with
+ * OKV_F_ZSTD_NATIVE); otherwise the call returns OKV_E_ARG.  Literals with byte values above
+ * 128 may then be Huffman-coded too: code lengths are computed over all 256 values, and the
+ * tree is described by FSE-compressed weights (RFC 8878 4.2.1.2, accuracy log 5 or 6) where
+ * that description exists and is strictly smaller than the direct one, or the direct one
+ * cannot list the weights (a value above 128).  Per unit the size is never above the size
+ * under OKV_F_ZSTD_HUFFMAN alone, so the capacity contract and the bound are unchanged;
+ * without this flag every output byte is what it was.  Opt-in; okv_last_path gains
+ * OKV_PATH_ZSTD_HUF_FSE when a unit was written so. */
+#define OKV_F_ZSTD_HUF_FSE 512u
 #define OKV_GET_INFLATED_MAX (1u << 24)
 /* The most source bytes the encoder puts into one zstd block of a frame, so
  * CompressedSize <= OriginalSize + 3 * ceil(OriginalSize / OKV_ZSTD_ENC_UNIT) + 18. */
@@ -373,7 +386,7 @@ typedef struct okv_encode_out {
  * Encode rows into one segment on the GPU.  flags: OKV_F_DEVICE_PTRS (rows and
  * every output pointer are device pointers; seg must be 16-byte aligned),
  * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE, OKV_F_ZSTD_NATIVE, OKV_F_ZSTD_HUFFMAN (with
- * OKV_F_ZSTD_NATIVE only).  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
+ * OKV_F_ZSTD_NATIVE only), OKV_F_ZSTD_HUF_FSE (with OKV_F_ZSTD_HUFFMAN only).  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
  * written: call again with seg_cap >= file_bytes and blk_cap >= n_blocks --
  * a call with zero capacities is the size query); OKV_W_INVALID_KEY (bad_row
  * set); OKV_W_NIL_WRITER (strict_go and the last row closed a block, or no
@@ -863,7 +876,11 @@ int okv_profile_read(okv_ctx *ctx, double *ms, uint64_t *calls);
 #define OKV_PATH_GET 8192u /* okv_get_rows: okv_get_locate_kernel, the grouping and
                              okv_get_search_kernel */
 #define OKV_PATH_ZSTD_HUF 65536u /* OKV_F_ZSTD_HUFFMAN: at least one unit of the call was written
-                                    with a Compressed_Literals_Block (okv_zenc_unit_huf_kernel) */
+                                    with a Compressed_Literals_Block (okv_zenc_unit_huf_kernel),
+                                    whichever way its tree is described */
+#define OKV_PATH_ZSTD_HUF_FSE 131072u /* OKV_F_ZSTD_HUF_FSE: at least one unit of the call was
+                                         written with an FSE-compressed tree description
+                                         (okv_zenc_unit_fse_kernel) */
 #define OKV_PATH_ZSTD_ENC 16384u /* okv_encode_rows compressed the blocks on the device
                                     (OKV_F_ZSTD_NATIVE: okv_zenc_unit_kernel and its placement) */
 #define OKV_PATH_SNAP_GET 32768u /* okv_snap_get_rows: route, locate, the grouping, the search

@@ -31,6 +31,7 @@ F_DEVICE_PTRS, F_INDEX_ONLY, F_ASYNC, F_NO_CLOSE = 1, 2, 4, 8
 F_BLOOM_DEVICE = 16
 F_ZSTD_NATIVE = 64  # okv_encode_rows with COMP_ZSTD: the device zstd encoder (opt-in)
 F_ZSTD_HUFFMAN = 256  # with F_ZSTD_NATIVE: Huffman-coded literals where they are smaller (opt-in)
+F_ZSTD_HUF_FSE = 512  # with F_ZSTD_HUFFMAN: all byte values, FSE-compressed weights where smaller
 F_GET_ZSTD = 128  # okv_get_rows / okv_snap_get_rows: zstd floor blocks inflated on the device
 GET_INFLATED_MAX = 1 << 24  # OKV_GET_INFLATED_MAX: a longer inflated block is FALLBACK
 ZSTD_ENC_UNIT = 32768  # OKV_ZSTD_ENC_UNIT: most source bytes in one zstd block of a frame
@@ -46,6 +47,7 @@ PATH_GET = 8192
 PATH_ZSTD_ENC = 16384
 PATH_SNAP_GET = 32768
 PATH_ZSTD_HUF = 65536  # F_ZSTD_HUFFMAN: a unit of the call was written with Huffman literals
+PATH_ZSTD_HUF_FSE = 131072  # F_ZSTD_HUF_FSE: a unit was written with FSE-compressed weights
 # okv_get_out.state (include/okv_sst.h OKV_GET_*)
 GET_FOUND, GET_BLOOM_NEGATIVE, GET_NO_BLOCK, GET_NOT_IN_BLOCK = 0, 1, 2, 3
 GET_BLOCK_ERROR, GET_FALLBACK = 4, 5

@@ -83,16 +83,19 @@ void zstd_release(okv_ctx* ctx);
 // zstd_enc_bound computes the units and *bound_bytes, the data bytes when every block is
 // stored as Raw_Blocks.  zstd_enc_run then compresses those blocks, writes the padded frames
 // at DataBlockSize D into seg, the BlockStats over desc, their hashes into hash (device
-// pointers) and the actual *data_bytes.  huffman (OKV_F_ZSTD_HUFFMAN): literals are Huffman-
-// coded where that is smaller; *huffman_used says whether a unit of the call was.
+// pointers) and the actual *data_bytes.  mode: what a unit's literals may become -- raw only,
+// Huffman with direct weights where that is smaller (OKV_F_ZSTD_HUFFMAN), or Huffman over all
+// byte values with direct or FSE-compressed weights (OKV_F_ZSTD_HUF_FSE).  *huffman_seen:
+// bit 0, a unit of the call was written with Huffman literals; bit 1, one with FSE weights.
 namespace zenc {
 struct Scratch;  // okv_zstd_enc.hip
 }
+constexpr uint32_t kZencRaw = 0, kZencHuffman = 1, kZencFse = 2;
 int zstd_enc_bound(okv_ctx* ctx, const Desc* img_desc, uint64_t nb, uint64_t D,
                    uint64_t* bound_bytes);
 int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* desc, uint64_t nb,
-                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes, bool huffman,
-                 bool* huffman_used);
+                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes, uint32_t mode,
+                 uint32_t* huffman_seen);
 void zstd_enc_release(okv_ctx* ctx);
 }  // namespace okv
 

@@ -2202,7 +2202,7 @@ int enc_meta(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
 // e->hash with the BlockStats.
 int enc_write_zstd(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
                    const okv_encode_opts& po, Plan* pl, uint8_t* seg, bool bloom_dev,
-                   bool huffman) {
+                   uint32_t zmode) {
   enc_mark(ctx, e, 1);
   int rc;
   if ((rc = reserve(ctx, e->zimg, pl->data_bytes + 64))) return rc;
@@ -2227,11 +2227,12 @@ int enc_write_zstd(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_enco
   if ((rc = enc_pack(ctx, e, R, po, *pl, img, pp, &hashed, &fk_done))) return rc;
   enc_mark(ctx, e, 2);
   uint64_t data_bytes = 0;
-  bool huffman_used = false;
+  uint32_t seen = 0;
   if ((rc = zstd_enc_run(ctx, img, pl->data_bytes, e->desc.data(), pl->nb, o.block_size, seg,
-                         e->hash.data(), &data_bytes, huffman, &huffman_used)))
+                         e->hash.data(), &data_bytes, zmode, &seen)))
     return rc;
-  if (huffman_used) ctx->last_path |= OKV_PATH_ZSTD_HUF;
+  if (seen & 1) ctx->last_path |= OKV_PATH_ZSTD_HUF;
+  if (seen & 2) ctx->last_path |= OKV_PATH_ZSTD_HUF_FSE;
   pl->data_bytes = data_bytes;
   pl->file_bytes = data_bytes + pl->meta_bytes + 25;
   enc_mark(ctx, e, 3);
@@ -2369,6 +2370,8 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   const bool zn = flags & OKV_F_ZSTD_NATIVE;  // the device zstd encoder (opt-in)
   if ((flags & OKV_F_ZSTD_HUFFMAN) && !zn)
     return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_HUFFMAN without OKV_F_ZSTD_NATIVE");
+  if ((flags & OKV_F_ZSTD_HUF_FSE) && !(flags & OKV_F_ZSTD_HUFFMAN))
+    return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_HUF_FSE without OKV_F_ZSTD_HUFFMAN");
   if (zn && opts->compression != OKV_COMP_ZSTD)
     return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_NATIVE without OKV_COMP_ZSTD");
   if (opts->compression == OKV_COMP_ZSTD && !zn)
@@ -2466,7 +2469,9 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   const bool bloom_dev = flags & OKV_F_BLOOM_DEVICE;
   if (zn) {
     if ((rc = enc_write_zstd(ctx, e, R, *opts, po, &pl, seg, bloom_dev,
-                             flags & OKV_F_ZSTD_HUFFMAN)))
+                             (flags & OKV_F_ZSTD_HUF_FSE)   ? kZencFse
+                             : (flags & OKV_F_ZSTD_HUFFMAN) ? kZencHuffman
+                                                            : kZencRaw)))
       return rc;
     out->data_bytes = pl.data_bytes;
     out->file_bytes = pl.file_bytes;
@@ -2495,6 +2500,8 @@ int okv_encode_close(okv_ctx* ctx, okv_encode_out* out, uint32_t flags) {
   if (!ctx || !out || !out->seg || !out->meta_bytes) return OKV_E_ARG;
   if ((flags & OKV_F_ZSTD_HUFFMAN) && !(flags & OKV_F_ZSTD_NATIVE))
     return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_HUFFMAN without OKV_F_ZSTD_NATIVE");
+  if ((flags & OKV_F_ZSTD_HUF_FSE) && !(flags & OKV_F_ZSTD_HUFFMAN))
+    return set_err(ctx, OKV_E_ARG, "OKV_F_ZSTD_HUF_FSE without OKV_F_ZSTD_HUFFMAN");
   if (out->seg_cap < out->data_bytes + out->meta_bytes + 25)
     return set_err(ctx, OKV_E_CAPACITY, "seg_cap");
   if (!(flags & OKV_F_DEVICE_PTRS)) {

@@ -40,7 +40,9 @@ static_assert(kUnit <= 32768, "positions, lengths and distances are kept in 16 b
 
 struct ZTot {
   unsigned long long n_units, bound_bytes, data_bytes;
-  unsigned long long huf_seen;  // OKV_F_ZSTD_HUFFMAN: a unit of the call wrote Huffman literals
+  // OKV_F_ZSTD_HUFFMAN: bit 0, a unit of the call wrote Huffman literals; bit 1
+  // (OKV_F_ZSTD_HUF_FSE), one of them with FSE-compressed weights
+  unsigned long long huf_seen;
 };
 
 __host__ __device__ inline uint64_t units_of(uint64_t orig) { return (orig + kUnit - 1) / kUnit; }
@@ -145,11 +147,19 @@ __device__ __forceinline__ void or_bits_n(uint32_t* words, uint32_t nw, uint32_t
 // Where the Huffman phases (OKV_F_ZSTD_HUFFMAN) keep their tables: words of `tab`, which is
 // dead between phase D and the point where H zeroes it.
 constexpr uint32_t kHufHist = 0;     // [256] literal histogram
-constexpr uint32_t kHufCode = 256;   // [kHufSyms] (value << 4) | length
+constexpr uint32_t kHufCode = 256;   // [kHufSyms, kHufAllSyms under kModeFse] (value << 4) | length
 constexpr uint32_t kHufBits = 512;   // [kT] code bits of a thread's literals, then of the later ones
-constexpr uint32_t kHufTot = 768;    // [0..3] code bits per stream, [4] longest code, [5] largest symbol
+constexpr uint32_t kHufTot = 768;    // [0..3] code bits per stream, [4] longest code, [5] largest symbol,
+                                     // [6] FSE description: its header bytes, then its bytes (0: none)
 constexpr uint32_t kHufWorkAt = 1024;
+constexpr uint32_t kWtAt = kHufWorkAt + kHufAllWork;  // WtWork (kModeFse)
 static_assert(kHufWorkAt + kHufWork <= kWords && kHufSyms <= 256, "the Huffman tables fit tab");
+static_assert(kHufCode + kHufAllSyms <= kHufBits && kHufBits + kT <= kHufTot &&
+                  kHufTot + 7 <= kHufWorkAt && kWtAt + sizeof(WtWork) / 4 <= kWords,
+              "the tables of all 256 symbols and the weights' description fit tab");
+// What a unit's literals may become: raw only, Huffman with direct weights (OKV_F_ZSTD_HUFFMAN),
+// or Huffman over all byte values with either description (OKV_F_ZSTD_HUF_FSE).
+constexpr uint32_t kModeRaw = 0, kModeHuf = 1, kModeFse = 2;
 
 // The unit's literals in order, by the whole workgroup: wave w takes the sequences of threads
 // 64w .. 64w+63 (c sequences a thread, their literal and match lengths scanned in s_lit and
@@ -190,13 +200,18 @@ __device__ __forceinline__ void each_literal(const uint16_t* sq, const uint32_t*
 //     most n - 4 ns literals; without a sequence they are the staged unit), their histogram
 //     by LDS atomics
 //  L2 one lane: code lengths and canonical codes (okv_zstd_enc.hpp); not eligible -> raw
+//     kModeFse (okv_zenc_unit_fse_kernel): lengths over all 256 values, the listed weights,
+//     their norm, NCount header and encode table by that lane; the two state chains on lanes
+//     0 and 1; the description's bits packed by lane 0; FSE or direct by size
 //  L3 every thread sums the code bits of its contiguous literals of one stream; one lane
 //     per stream scans them; the section's size, Huffman or raw, Compressed or Raw
 //  L4 the codes ORed into the stream words behind the gathered literals (they are fewer
 //     bytes than the literals: 6 ns + 2 (n - 4 ns) <= 65 536), last literal first
-//  L5 header, tree description, jump table and streams stored
-template <bool HUF>
+//  L5 header, tree description (direct, or the compressed size and the FSE bytes), jump table
+//     and streams stored
+template <uint32_t MODE>
 __device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long long* huf_seen) {
+  constexpr bool HUF = MODE != kModeRaw, FSE = MODE == kModeFse;
   __shared__ UnitSmem sm;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t u = blockIdx.x;
@@ -391,8 +406,8 @@ __device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long lon
   }
   // the Huffman phases: `huf` says the literals section is a Compressed_Literals_Block of
   // `litsec` bytes whose streams take hb0 .. hb3 bytes
-  bool huf = false;
-  uint32_t litsec = 0, hmb = 0, hlast = 0, hsum = 0, hlo = 0, hhi = 0, hstream = 0;
+  bool huf = false, dfse = false;
+  uint32_t litsec = 0, hmb = 0, hlast = 0, hsum = 0, hlo = 0, hhi = 0, hstream = 0, hdesc = 0;
   uint32_t hb0 = 0, hb1 = 0, hb2 = 0, hb3 = 0;
   const auto streams_before = [&](uint32_t s) {  // bytes of the streams before stream s
     return (s > 0 ? hb0 : 0) + (s > 1 ? hb1 : 0) + (s > 2 ? hb2 : 0);
@@ -422,13 +437,35 @@ __device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long lon
     }
     __syncthreads();
     // L2
+    WtWork& wt = *reinterpret_cast<WtWork*>(sm.tab + kWtAt);
     if (tid == 0) {
-      const uint32_t mb = huf_lengths(hist, code, sm.tab + kHufWorkAt);
-      htot[4] = mb;
-      htot[5] = mb ? huf_codes(code, mb, code, sm.tab + kHufWorkAt) : 0;
+      if constexpr (FSE) {
+        const uint32_t mb = huf_lengths_all(hist, code, sm.tab + kHufWorkAt);
+        const uint32_t lastsym = mb ? huf_codes_all(code, mb, code, sm.tab + kHufWorkAt) : 0;
+        for (uint32_t s = 0; s < lastsym; ++s) wt.w[s] = uint8_t(huf_weight(code[s] & 15u, mb));
+        htot[4] = mb, htot[5] = lastsym;
+        htot[6] = mb ? wt_prepare(wt, lastsym) : 0;
+      } else {
+        const uint32_t mb = huf_lengths(hist, code, sm.tab + kHufWorkAt);
+        htot[4] = mb;
+        htot[5] = mb ? huf_codes(code, mb, code, sm.tab + kHufWorkAt) : 0;
+      }
     }
     __syncthreads();
     hmb = htot[4], hlast = htot[5];
+    if constexpr (FSE) {
+      const uint32_t nc = htot[6];  // (the same for every thread)
+      if (nc) {
+        if (tid < 2) wt_chain(wt, hlast, tid);
+        __syncthreads();
+        if (tid == 0) htot[6] = wt_pack(wt, hlast, nc);
+        __syncthreads();
+      }
+      hdesc = huf_desc_size(hlast, htot[6], dfse);
+      if (!hdesc) hmb = 0;  // a value above kHufMaxSym and no FSE description: raw
+    } else {
+      hdesc = huf_tree_size(hlast);
+    }
     litsec = lit_header_size(nlit) + nlit;
     if (hmb) {
       // L3: 256 threads on the one stream, or 64 on each of four
@@ -456,8 +493,13 @@ __device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long lon
         hb1 = huf_stream_bytes(htot[1]), hb2 = huf_stream_bytes(htot[2]),
         hb3 = huf_stream_bytes(htot[3]);
       hsum = hb0 + hb1 + hb2 + hb3;
-      huf = huf_wins(nlit, hlast, hsum);
-      if (huf) litsec = huf_section_size(nlit, hlast, hsum);
+      if constexpr (FSE) {
+        huf = huf_wins_d(nlit, hdesc, hsum);
+        if (huf) litsec = huf_section_size_d(nlit, hdesc, hsum);
+      } else {
+        huf = huf_wins(nlit, hlast, hsum);
+        if (huf) litsec = huf_section_size(nlit, hlast, hsum);
+      }
     }
     // every thread has read what decides its way from here (htot); only now may a thread
     // that goes straight to H, or to the Raw_Block, write into tab
@@ -500,14 +542,19 @@ __device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long lon
         or_bits_n(hw, nw, 8 * streams_before(tid) + sm.tab[kHufTot + tid], 1);
       __syncthreads();
       // L5
-      const uint32_t hh = huf_header_size(nlit), ts = huf_tree_size(hlast);
+      const uint32_t hh = huf_header_size(nlit), ts = hdesc;
       const uint32_t jt = huf_streams(nlit) == 4 ? 6 : 0;
       uint8_t* sec = out + 3;
       if (tid == 0) {
         huf_header(sec, nlit, ts + jt + hsum);
-        atomicOr(huf_seen, 1ull);
+        atomicOr(huf_seen, dfse ? 3ull : 1ull);
       }
-      for (uint32_t k = tid; k < ts; k += kT) sec[hh + k] = huf_tree_byte(code, hmb, hlast, k);
+      if (FSE && dfse) {
+        const uint8_t* fo = reinterpret_cast<const WtWork*>(sm.tab + kWtAt)->out;
+        for (uint32_t k = tid; k < ts; k += kT) sec[hh + k] = k ? fo[k - 1] : uint8_t(ts - 1);
+      } else {
+        for (uint32_t k = tid; k < ts; k += kT) sec[hh + k] = huf_tree_byte(code, hmb, hlast, k);
+      }
       if (jt && tid < 3) {
         const uint32_t by = tid == 0 ? hb0 : tid == 1 ? hb1 : hb2;
         sec[hh + ts + 2 * tid] = uint8_t(by);
@@ -568,13 +615,19 @@ __device__ __forceinline__ void unit_body(const UnitParams& P, unsigned long lon
 }
 
 __global__ __launch_bounds__(kT) void okv_zenc_unit_kernel(UnitParams P) {
-  unit_body<false>(P, nullptr);
+  unit_body<kModeRaw>(P, nullptr);
 }
 // The same unit with Huffman-coded literals where they are smaller; *huf_seen becomes 1 when
 // a unit of the launch wrote a Compressed_Literals_Block.
 __global__ __launch_bounds__(kT) void okv_zenc_unit_huf_kernel(UnitParams P,
                                                                unsigned long long* huf_seen) {
-  unit_body<true>(P, huf_seen);
+  unit_body<kModeHuf>(P, huf_seen);
+}
+// The same over all 256 byte values, the tree described by direct or by FSE-compressed weights,
+// whichever is smaller (OKV_F_ZSTD_HUF_FSE); *huf_seen gains bit 1 when a unit wrote the latter.
+__global__ __launch_bounds__(kT) void okv_zenc_unit_fse_kernel(UnitParams P,
+                                                               unsigned long long* huf_seen) {
+  unit_body<kModeFse>(P, huf_seen);
 }
 
 // Z4.  One workgroup; thread t owns a contiguous range of blocks.
@@ -718,8 +771,8 @@ int zstd_enc_bound(okv_ctx* ctx, const Desc* img_desc, uint64_t nb, uint64_t D,
 }
 
 int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* desc, uint64_t nb,
-                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes, bool huffman,
-                 bool* huffman_used) {
+                 uint64_t D, uint8_t* seg, uint64_t* hash, uint64_t* data_bytes, uint32_t mode,
+                 uint32_t* huffman_seen) {
   zenc::Scratch* s = ctx->zenc;
   if (!s || s->nb != nb || nb >= (uint64_t(1) << 32))
     return set_err(ctx, OKV_E_ARG, "zstd encode: no plan for these blocks");
@@ -745,7 +798,11 @@ int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* des
   up.usize = s->usize.data();
   // ZTot::huf_seen comes back with the sizes' read-back
   unsigned long long* huf_seen = &s->d_tot.data()->huf_seen;
-  if (huffman) {
+  if (mode == kZencFse) {
+    OKV_HIP(hipMemsetAsync(huf_seen, 0, sizeof *huf_seen, ctx->stream));
+    hipLaunchKernelGGL(zenc::okv_zenc_unit_fse_kernel, dim3(uint32_t(nu)), dim3(zenc::kT), 0,
+                       ctx->stream, up, huf_seen);
+  } else if (mode == kZencHuffman) {
     OKV_HIP(hipMemsetAsync(huf_seen, 0, sizeof *huf_seen, ctx->stream));
     hipLaunchKernelGGL(zenc::okv_zenc_unit_huf_kernel, dim3(uint32_t(nu)), dim3(zenc::kT), 0,
                        ctx->stream, up, huf_seen);
@@ -760,7 +817,7 @@ int zstd_enc_run(okv_ctx* ctx, const uint8_t* img, uint64_t img_bytes, Desc* des
   OKV_HIP(hipGetLastError());
   if ((rc = zenc::read_tot(ctx, s))) return rc;
   *data_bytes = s->h_tot->data_bytes;
-  *huffman_used = huffman && s->h_tot->huf_seen != 0;
+  *huffman_seen = mode == kZencRaw ? 0 : uint32_t(s->h_tot->huf_seen);
   if (*data_bytes > s->h_tot->bound_bytes)
     return set_err(ctx, OKV_E_HIP, "zstd encode: frames larger than their bound");
   zenc::PlaceParams pp;

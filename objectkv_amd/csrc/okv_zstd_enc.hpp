@@ -9,7 +9,8 @@
 // What the encoder emits and nothing else: Raw_Literals_Block, all three sequence
 // tables in Predefined_Mode, every offset as Offset_Value = offset + 3 (no repeat
 // codes), Raw_Blocks; and under OKV_F_ZSTD_HUFFMAN a Compressed_Literals_Block with
-// direct weights where it is smaller.  Custom FSE tables are not here.
+// direct weights where it is smaller, under OKV_F_ZSTD_HUF_FSE with FSE-compressed weights
+// too.  Custom FSE tables for the sequences are not here.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -62,15 +63,17 @@ struct CTable {
   uint32_t log;
 };
 
-OKV_ZE_HD void build_ctable(CTable& ct, uint32_t t) {
-  const uint32_t log = table_log(t), nsym = table_syms(t), size = 1u << log, mask = size - 1;
+// From a normalised distribution `norm` of nsym symbols at accuracy `log` (-1: "less than
+// one", 0: absent).  sym_at: 2^log bytes, cumul: nsym + 1 entries; the caller says where they
+// live (the device passes LDS).
+OKV_ZE_HD void build_ctable_norm(CTable& ct, const int32_t* norm, uint32_t nsym, uint32_t log,
+                                 uint8_t* sym_at, uint16_t* cumul) {
+  const uint32_t size = 1u << log, mask = size - 1;
   const uint32_t step = (size >> 1) + (size >> 3) + 3;
-  uint8_t sym_at[64];
-  uint16_t cumul[kMaxSyms + 1];
   uint32_t high = size - 1;
   cumul[0] = 0;
   for (uint32_t s = 0; s < nsym; ++s) {
-    const int nrm = predefined_norm(t, s);
+    const int nrm = norm[s];
     if (nrm == -1) {
       cumul[s + 1] = uint16_t(cumul[s] + 1);
       sym_at[high--] = uint8_t(s);
@@ -80,7 +83,7 @@ OKV_ZE_HD void build_ctable(CTable& ct, uint32_t t) {
   }
   uint32_t pos = 0;
   for (uint32_t s = 0; s < nsym; ++s) {
-    const int nrm = predefined_norm(t, s);
+    const int nrm = norm[s];
     for (int i = 0; i < nrm; ++i) {
       sym_at[pos] = uint8_t(s);
       pos = (pos + step) & mask;
@@ -90,12 +93,15 @@ OKV_ZE_HD void build_ctable(CTable& ct, uint32_t t) {
   for (uint32_t u = 0; u < size; ++u) ct.state[cumul[sym_at[u]]++] = uint16_t(size + u);
   uint32_t total = 0;
   for (uint32_t s = 0; s < nsym; ++s) {
-    const int nrm = predefined_norm(t, s);
-    if (nrm == -1 || nrm == 1) {
+    const int nrm = norm[s];
+    if (nrm == 0) {  // never coded
+      ct.dnb[s] = ((log + 1) << 16) - size;
+      ct.dfs[s] = 0;
+    } else if (nrm == -1 || nrm == 1) {
       ct.dnb[s] = (log << 16) - size;
       ct.dfs[s] = int32_t(total) - 1;
       total += 1;
-    } else {  // (no predefined symbol has probability 0)
+    } else {
       const uint32_t max_bits = log - highbit(uint32_t(nrm) - 1);
       ct.dnb[s] = (max_bits << 16) - (uint32_t(nrm) << max_bits);
       ct.dfs[s] = int32_t(total) - nrm;
@@ -103,6 +109,15 @@ OKV_ZE_HD void build_ctable(CTable& ct, uint32_t t) {
     }
   }
   ct.log = log;
+}
+// The predefined table t.
+OKV_ZE_HD void build_ctable(CTable& ct, uint32_t t) {
+  int32_t norm[kMaxSyms];
+  uint8_t sym_at[64];
+  uint16_t cumul[kMaxSyms + 1];
+  const uint32_t nsym = table_syms(t);
+  for (uint32_t s = 0; s < nsym; ++s) norm[s] = predefined_norm(t, s);
+  build_ctable_norm(ct, norm, nsym, table_log(t), sym_at, cumul);
 }
 
 // The state a chain starts in (FSE_initCState2): the symbol of the LAST sequence.
@@ -299,8 +314,8 @@ OKV_ZE_HD uint32_t block_content_size(uint32_t litsec, uint32_t nseq, uint64_t b
 // byte 127 + number of listed weights, and 255 - 127 = 128 listed weights describe the
 // symbols 0 .. 128), and the section is strictly smaller than the raw one.  Code lengths
 // are the length-limited optimum of package-merge at kHufMaxBits; weights, the canonical
-// codes and the stream split are the RFC's.  No FSE-compressed weights, no RLE and no
-// treeless literals.
+// codes and the stream split are the RFC's.  FSE-compressed weights and values above
+// kHufMaxSym come with OKV_F_ZSTD_HUF_FSE (below); no RLE and no treeless literals.
 constexpr uint32_t kHufMaxBits = 11;
 constexpr uint32_t kHufMaxSym = 128;
 constexpr uint32_t kHufSyms = kHufMaxSym + 1;
@@ -309,6 +324,19 @@ constexpr uint32_t kHufItems = 2 * kHufSyms - 2;  // items package-merge keeps p
 // byte per item and level.
 constexpr uint32_t kHufWork = kHufSyms + 2 * kHufItems + kHufMaxBits * kHufItems / 4;
 static_assert(kHufItems % 4 == 0, "a level's flag bytes are whole words");
+// The same sizes for any symbol limit: the item lists and a level's flag bytes keep a stride
+// of whole words (2 * 256 - 2 = 510 items are padded to 512).
+template <uint32_t MAXSYM>
+struct HufDim {
+  static constexpr uint32_t syms = MAXSYM + 1;
+  static constexpr uint32_t items = 2 * syms - 2;
+  static constexpr uint32_t stride = (items + 3) & ~3u;
+  static constexpr uint32_t work = syms + 2 * stride + kHufMaxBits * stride / 4;
+};
+constexpr uint32_t kHufAllSyms = 256;  // OKV_F_ZSTD_HUF_FSE: every byte value may have a code
+constexpr uint32_t kHufAllWork = HufDim<kHufAllSyms - 1>::work;
+static_assert(HufDim<kHufMaxSym>::work == kHufWork && HufDim<kHufMaxSym>::stride == kHufItems,
+              "the direct-weights instance is the one stated above");
 
 // Code lengths from a histogram of 256 counts (their sum below 2^23): len[s] for
 // s <= kHufMaxSym, 0 for an absent symbol.  Returns the longest length, or 0 when the
@@ -318,15 +346,17 @@ static_assert(kHufItems % 4 == 0, "a level's flag bytes are whole words");
 // level below, a leaf before a package of equal weight; the first 2n - 2 items of the last
 // level are taken, and going down, twice as many items as packages were taken above.  A
 // leaf's length is the number of levels that took it.
-OKV_ZE_HD uint32_t huf_lengths(const uint32_t* hist, uint32_t* len, uint32_t* work) {
-  uint32_t* key = work;                      // (count << 8) | symbol, ascending
-  uint32_t* cur = work + kHufSyms;           // item weights of the level being built
-  uint32_t* prev = cur + kHufItems;          // ... of the level below
-  uint8_t* flag = reinterpret_cast<uint8_t*>(prev + kHufItems);  // 1: the item is a package
+template <uint32_t MAXSYM>
+OKV_ZE_HD uint32_t huf_lengths_n(const uint32_t* hist, uint32_t* len, uint32_t* work) {
+  constexpr uint32_t kSyms = HufDim<MAXSYM>::syms, kStride = HufDim<MAXSYM>::stride;
+  uint32_t* key = work;                    // (count << 8) | symbol, ascending
+  uint32_t* cur = work + kSyms;            // item weights of the level being built
+  uint32_t* prev = cur + kStride;          // ... of the level below
+  uint8_t* flag = reinterpret_cast<uint8_t*>(prev + kStride);  // 1: the item is a package
   uint32_t n = 0;
-  for (uint32_t s = kHufMaxSym + 1; s < 256; ++s)  // (first: the common way out)
+  for (uint32_t s = kSyms; s < 256; ++s)  // (first: the common way out)
     if (hist[s]) return 0;
-  for (uint32_t s = 0; s <= kHufMaxSym; ++s) {
+  for (uint32_t s = 0; s < kSyms; ++s) {
     const uint32_t c = hist[s];
     if (!c) continue;
     uint32_t i = n++;  // insertion: counts ascending, equal counts by symbol
@@ -341,7 +371,7 @@ OKV_ZE_HD uint32_t huf_lengths(const uint32_t* hist, uint32_t* len, uint32_t* wo
   for (uint32_t i = 0; i < n; ++i) prev[i] = key[i] >> 8;
   uint32_t plen = n;
   for (uint32_t lv = 1; lv < levels; ++lv) {
-    uint8_t* fl = flag + lv * kHufItems;
+    uint8_t* fl = flag + lv * kStride;
     const uint32_t np = plen / 2;
     uint32_t i = 0, j = 0, cnt = 0;
     while (cnt < keep && (i < n || j < np)) {
@@ -366,40 +396,57 @@ OKV_ZE_HD uint32_t huf_lengths(const uint32_t* hist, uint32_t* len, uint32_t* wo
   for (uint32_t lv = levels; lv-- > 0 && take;) {
     uint32_t packs = 0;
     if (lv) {
-      const uint8_t* fl = flag + lv * kHufItems;
+      const uint8_t* fl = flag + lv * kStride;
       for (uint32_t i = 0; i < take; ++i) packs += fl[i];
     }
     const uint32_t leaves = take - packs;
     for (uint32_t i = 0; i < leaves; ++i) depth[i] += 1;
     take = 2 * packs;
   }
-  for (uint32_t s = 0; s < kHufSyms; ++s) len[s] = 0;
+  for (uint32_t s = 0; s < kSyms; ++s) len[s] = 0;
   for (uint32_t i = 0; i < n; ++i) len[key[i] & 255u] = depth[i];
   return depth[0];
+}
+OKV_ZE_HD uint32_t huf_lengths(const uint32_t* hist, uint32_t* len, uint32_t* work) {
+  return huf_lengths_n<kHufMaxSym>(hist, len, work);
+}
+// The same over all 256 byte values (OKV_F_ZSTD_HUF_FSE); work: kHufAllWork words.  Without a
+// value above kHufMaxSym the keys, their order and so the lengths are huf_lengths'.
+OKV_ZE_HD uint32_t huf_lengths_all(const uint32_t* hist, uint32_t* len, uint32_t* work) {
+  return huf_lengths_n<kHufAllSyms - 1>(hist, len, work);
 }
 
 // The canonical codes (RFC 8878 4.2.1.3, HUF_buildCTable's order): the longest codes start
 // at 0 and count up by symbol value; a shorter length starts at half of where the longer
 // ones ended.  code[s] = (value << 4) | length, 0 for an absent symbol; `len` and `code`
 // may be the same array.  Returns the largest present symbol.  work: 32 words.
-OKV_ZE_HD uint32_t huf_codes(const uint32_t* len, uint32_t max_bits, uint32_t* code,
-                             uint32_t* work) {
+template <uint32_t NSYM>
+OKV_ZE_HD uint32_t huf_codes_n(const uint32_t* len, uint32_t max_bits, uint32_t* code,
+                               uint32_t* work) {
   uint32_t* per = work;       // symbols per length
   uint32_t* val = work + 16;  // next value per length
   for (uint32_t b = 0; b < 16; ++b) per[b] = 0;
   uint32_t last = 0;
-  for (uint32_t s = 0; s < kHufSyms; ++s)
+  for (uint32_t s = 0; s < NSYM; ++s)
     if (len[s]) per[len[s]] += 1, last = s;
   uint32_t min = 0;
   for (uint32_t b = max_bits; b > 0; --b) {
     val[b] = min;
     min = (min + per[b]) >> 1;
   }
-  for (uint32_t s = 0; s < kHufSyms; ++s) {
+  for (uint32_t s = 0; s < NSYM; ++s) {
     const uint32_t b = len[s];
     code[s] = b ? ((val[b]++) << 4) | b : 0;
   }
   return last;
+}
+OKV_ZE_HD uint32_t huf_codes(const uint32_t* len, uint32_t max_bits, uint32_t* code,
+                             uint32_t* work) {
+  return huf_codes_n<kHufSyms>(len, max_bits, code, work);
+}
+OKV_ZE_HD uint32_t huf_codes_all(const uint32_t* len, uint32_t max_bits, uint32_t* code,
+                                 uint32_t* work) {
+  return huf_codes_n<kHufAllSyms>(len, max_bits, code, work);
 }
 // The weight the tree description lists for a code of `bits` bits (0: absent).
 OKV_ZE_HD uint32_t huf_weight(uint32_t bits, uint32_t max_bits) {
@@ -444,6 +491,161 @@ OKV_ZE_HD uint32_t huf_section_size(uint32_t nlit, uint32_t last, uint32_t strea
 // The rule: Huffman only when strictly smaller than the raw section.
 OKV_ZE_HD bool huf_wins(uint32_t nlit, uint32_t last, uint32_t stream_bytes) {
   return huf_section_size(nlit, last, stream_bytes) < lit_header_size(nlit) + nlit;
+}
+
+// ---- FSE-compressed weights (OKV_F_ZSTD_HUF_FSE; RFC 8878 4.2.1.2) -----------------
+// The second form of the tree description: header byte = its compressed size (< 128), an
+// NCount header, and the weights of the symbols 0 .. last-1 (values 0 .. kHufMaxBits)
+// through two interleaved FSE states, written backwards.  It exists when there are at least
+// two listed weights, they are not all one value and it takes at most kWtMaxBytes bytes.
+// It is used iff it exists and is strictly smaller than the direct one, or the direct one
+// does not exist (last > kHufMaxSym); a tie goes to direct.
+constexpr uint32_t kWtSyms = kHufMaxBits + 1;  // weight values
+constexpr uint32_t kWtMaxBytes = 127;
+// The accuracy log (the decoders take 5 or 6): 6 from 128 listed weights on, else 5.  A
+// finer table pays only when many weights share its header.
+OKV_ZE_HD uint32_t wt_log(uint32_t listed) { return listed >= 128 ? 6u : 5u; }
+
+// Everything the description needs besides registers; the device keeps it in LDS.
+struct WtWork {
+  CTable ct;
+  int32_t norm[kWtSyms];
+  uint32_t cnt[kWtSyms];
+  uint16_t cumul[kWtSyms + 2];
+  uint8_t sym_at[64];
+  uint8_t w[256];    // the listed weights
+  uint8_t st[256];   // per weight: (1 << nb) | bits of its state step
+  uint8_t out[128];  // NCount header, then the stream
+  uint32_t fin[2];   // the chains' final states
+};
+static_assert(sizeof(WtWork) % 4 == 0, "whole words of LDS");
+
+// Normalised counts summing to 2^log: each present value gets its share rounded to nearest,
+// at least 1; what is missing goes to the most frequent value (the lowest on a tie), what is
+// too much is taken one at a time from the value that holds most.  Returns the number of
+// values up to the largest present one, or 0 when all weights are one value.
+OKV_ZE_HD uint32_t wt_normalise(const uint32_t* cnt, uint32_t total, uint32_t log, int32_t* norm) {
+  const uint32_t size = 1u << log;
+  uint32_t nsym = 0, sum = 0, big = 0;
+  for (uint32_t s = 0; s < kWtSyms; ++s) {
+    const uint32_t c = cnt[s];
+    if (c == total) return 0;
+    uint32_t p = c ? (c * size + total / 2) / total : 0;
+    if (c && !p) p = 1;
+    norm[s] = int32_t(p);
+    sum += p;
+    if (c) nsym = s + 1;
+    if (cnt[s] > cnt[big]) big = s;
+  }
+  if (sum <= size) {
+    norm[big] += int32_t(size - sum);
+  } else {
+    for (uint32_t over = sum - size; over; --over) {  // (at most kWtSyms: each rounds up < 1)
+      uint32_t m = 0;
+      for (uint32_t s = 1; s < kWtSyms; ++s)
+        if (norm[s] > norm[m]) m = s;
+      norm[m] -= 1;  // (it holds at least 3: more than 2^log >= 32 is spread over 12 values)
+    }
+  }
+  return nsym;
+}
+
+// The NCount header (RFC 8878 4.1.1) of norm[0 .. nsym): 4 bits of log - 5, then every count
+// as count + 1 in the fewest bits the rest still to give allows (the low values of the range
+// take one bit less), and after a zero the number of further zeros in 2-bit groups.  Bits go
+// low first.  At most 4 + 12 * 7 + 12 bits.  Returns its bytes.
+OKV_ZE_HD uint32_t wt_ncount(const int32_t* norm, uint32_t nsym, uint32_t log, uint8_t* out) {
+  SeqBits b = {0, 0, 0};
+  bits_push(b, log - 5, 4);
+  int32_t remaining = int32_t(1u << log) + 1, threshold = int32_t(1u << log);
+  uint32_t nb = log + 1, s = 0;
+  bool zero = false;
+  while (s < nsym && remaining > 1) {
+    if (zero) {
+      uint32_t start = s;
+      while (s < nsym && !norm[s]) ++s;  // (norm[nsym - 1] is not 0)
+      for (; s >= start + 3; start += 3) bits_push(b, 3, 2);
+      bits_push(b, s - start, 2);
+    }
+    int32_t v = norm[s++];
+    const int32_t max = 2 * threshold - 1 - remaining;
+    remaining -= v;
+    v += 1;
+    if (v >= threshold) v += max;
+    bits_push(b, uint32_t(v), nb - (v < max ? 1u : 0u));
+    zero = v == 1;
+    while (remaining < threshold && threshold > 1) --nb, threshold >>= 1;
+  }
+  const uint32_t bytes = (b.nb + 7) >> 3;
+  for (uint32_t i = 0; i < bytes; ++i)
+    out[i] = uint8_t(i < 8 ? b.lo >> (8 * i) : b.hi >> (8 * (i - 8)));
+  return bytes;
+}
+
+// Step one, by one lane: the histogram of the n listed weights w.w[0 .. n), their norm, the
+// header into w.out and the encode table.  Returns the header's bytes, 0 when there is no
+// FSE description.
+OKV_ZE_HD uint32_t wt_prepare(WtWork& w, uint32_t n) {
+  if (n < 2) return 0;
+  for (uint32_t s = 0; s < kWtSyms; ++s) w.cnt[s] = 0;
+  for (uint32_t i = 0; i < n; ++i) w.cnt[w.w[i]] += 1;
+  const uint32_t log = wt_log(n);
+  const uint32_t nsym = wt_normalise(w.cnt, n, log, w.norm);
+  if (!nsym) return 0;
+  build_ctable_norm(w.ct, w.norm, nsym, log, w.sym_at, w.cumul);
+  return wt_ncount(w.norm, nsym, log, w.out);
+}
+// Step two, chain p of two (they are independent): the weights at the indices of parity p,
+// last to first.  The last such weight starts the state and costs no bits.  Weight 0 is the
+// first symbol the decoder reads, from the state that is flushed last: chain 0.
+OKV_ZE_HD void wt_chain(WtWork& w, uint32_t n, uint32_t p) {
+  uint32_t i = n - 1 - ((n - 1 - p) & 1u);
+  uint32_t state = fse_init(w.ct, w.w[i]);
+  w.st[i] = 1;
+  while (i >= 2) {
+    i -= 2;
+    uint32_t nb, bits;
+    state = fse_step(w.ct, state, w.w[i], nb, bits);
+    w.st[i] = uint8_t((1u << nb) | bits);
+  }
+  w.fin[p] = state;
+}
+// Step three: the steps' bits from the last weight to the first, the final states (chain 1,
+// then chain 0, log bits each) and the end mark, behind the `nc` header bytes.  Returns the
+// description's bytes without its header byte, 0 when they are more than kWtMaxBytes.
+OKV_ZE_HD uint32_t wt_pack(WtWork& w, uint32_t n, uint32_t nc) {
+  const uint32_t log = w.ct.log, mask = (1u << log) - 1;
+  uint64_t acc = 0;
+  uint32_t an = 0, at = nc;
+  const auto add = [&](uint32_t v, uint32_t nb) {
+    acc |= uint64_t(v) << an;
+    an += nb;
+    for (; an >= 8; an -= 8, acc >>= 8, ++at)
+      if (at < kWtMaxBytes) w.out[at] = uint8_t(acc);
+  };
+  for (uint32_t i = n; i-- > 0;) {
+    const uint32_t e = w.st[i], nb = highbit(e);
+    add(e - (1u << nb), nb);
+  }
+  add(w.fin[1] & mask, log);
+  add(w.fin[0] & mask, log);
+  add(1, 8 - an % 8);  // (the end mark and zeros up to the byte)
+  return at <= kWtMaxBytes ? at : 0;
+}
+
+// Which description: its bytes with the header byte, 0 when there is none (the literals stay
+// raw).  fse_bytes: wt_pack's result.
+OKV_ZE_HD uint32_t huf_desc_size(uint32_t last, uint32_t fse_bytes, bool& fse) {
+  const uint32_t direct = last <= kHufMaxSym ? huf_tree_size(last) : 0;
+  fse = fse_bytes && (!direct || 1 + fse_bytes < direct);
+  return fse ? 1 + fse_bytes : direct;
+}
+// huf_section_size and huf_wins from the description's bytes.
+OKV_ZE_HD uint32_t huf_section_size_d(uint32_t nlit, uint32_t desc, uint32_t stream_bytes) {
+  return huf_header_size(nlit) + desc + (huf_streams(nlit) == 4 ? 6 : 0) + stream_bytes;
+}
+OKV_ZE_HD bool huf_wins_d(uint32_t nlit, uint32_t desc, uint32_t stream_bytes) {
+  return huf_section_size_d(nlit, desc, stream_bytes) < lit_header_size(nlit) + nlit;
 }
 
 // Upper bound of a frame for `orig` raw bytes: every unit a Raw_Block.

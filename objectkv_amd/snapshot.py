@@ -840,13 +840,15 @@ class Iter:
 
 
 def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, block_size=4096,
-            direction=DirectionAscending, zstd=False, zstd_huffman=False):
+            direction=DirectionAscending, zstd=False, zstd_huffman=False,
+            zstd_huffman_fse=False):
     """Merge resident segments (DeviceSegment, level) in priority order (newest
     first) into one new segment, on the GPU: every key's owning row (GetRange's
     rule, :294-331), L0 tombstones dropped when drop_tombstones.  zstd: write the
     output segment zstd-compressed with the device encoder (OKV_F_ZSTD_NATIVE:
     its own frames, blocks cut on raw lengths); zstd_huffman: with zstd, Huffman-coded
-    literals where they are smaller (OKV_F_ZSTD_HUFFMAN).  Returns the Compacted result
+    literals where they are smaller (OKV_F_ZSTD_HUFFMAN); zstd_huffman_fse: with
+    zstd_huffman, FSE-compressed weights (OKV_F_ZSTD_HUF_FSE).  Returns the Compacted result
     (segment bytes + block index)."""
     import torch
     srcs = [(ds.t, 0, ds.n, lvl) for ds, lvl in segments]
@@ -871,7 +873,7 @@ def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, bl
     try:  # size query (zero capacities; with zstd file_bytes is an upper bound)
         encoder.encode_device(rows, n, {}, threshold, block_size, comp, False,
                               key_arena_bytes=kspan, val_arena_bytes=vspan, zstd_native=zstd,
-                              zstd_huffman=zstd_huffman)
+                              zstd_huffman=zstd_huffman, zstd_huffman_fse=zstd_huffman_fse)
         raise AssertionError("size query must report OKV_E_CAPACITY")
     except OkvError as e:
         if e.code != _lib.OKV_E_CAPACITY:
@@ -884,7 +886,7 @@ def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, bl
             "hash": torch.empty(nb, dtype=torch.int64, device=dev)}
     eo = encoder.encode_device(rows, n, eout, threshold, block_size, comp, False,
                                key_arena_bytes=kspan, val_arena_bytes=vspan, zstd_native=zstd,
-                               zstd_huffman=zstd_huffman)
+                               zstd_huffman=zstd_huffman, zstd_huffman_fse=zstd_huffman_fse)
     return Compacted(eout["seg"][:int(eo.file_bytes)].cpu().numpy(), int(eo.file_bytes), n,
                      int(eo.n_blocks), eout, eo)
 

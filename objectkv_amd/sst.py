@@ -517,7 +517,8 @@ class Encoder(Decoder):
         return o
 
     def encode(self, rows, threshold=3584, block_size=4096, compression=COMP_NONE,
-               strict_go=True, bloom=None, zstd_native=False, zstd_huffman=False) -> Encoded:
+               strict_go=True, bloom=None, zstd_native=False, zstd_huffman=False,
+               zstd_huffman_fse=False) -> Encoded:
         """Host-buffer encode: rows is a list of (key, value) pairs or the dict
         of SoA arrays from pack_rows().  bloom: the filter's WriteTo bytes, or a
         DeviceBloom (the rows are added to it on the device).  zstd_native: with
@@ -525,14 +526,18 @@ class Encoder(Decoder):
         cut on raw lengths); the first call then returns a size bound and the
         segment is trimmed to the actual file_bytes.  zstd_huffman: with zstd_native,
         literals are Huffman-coded where that is smaller (OKV_F_ZSTD_HUFFMAN); it
-        implies nothing else, and without zstd_native the call raises OKV_E_ARG."""
+        implies nothing else, and without zstd_native the call raises OKV_E_ARG.
+        zstd_huffman_fse: with zstd_huffman, byte values above 128 may be coded too and
+        the tree is described by FSE-compressed weights where that is smaller
+        (OKV_F_ZSTD_HUF_FSE); without zstd_huffman the call raises OKV_E_ARG."""
         r = rows if isinstance(rows, dict) else pack_rows(rows)
         n = int(r["key_len"].size)
         R = _lib.Rows(_ptr(r["key_arena"]), _ptr(r["key_off"]), _ptr(r["key_len"]),
                       _ptr(r["val_arena"]), _ptr(r["val_off"]), _ptr(r["val_len"]), n,
                       int(r["key_arena"].size), int(r["val_arena"].size))
         flags = self._device_bloom(bloom, r) | (_lib.F_ZSTD_NATIVE if zstd_native else 0) | \
-            (_lib.F_ZSTD_HUFFMAN if zstd_huffman else 0)
+            (_lib.F_ZSTD_HUFFMAN if zstd_huffman else 0) | \
+            (_lib.F_ZSTD_HUF_FSE if zstd_huffman_fse else 0)
         o = self._opts(threshold, block_size, compression, strict_go, bloom)
         out = _lib.EncodeOut()
         rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(out), flags)
@@ -553,14 +558,14 @@ class Encoder(Decoder):
     def encode_device(self, rows: dict, n_rows: int, out: dict, threshold=3584,
                       block_size=4096, compression=COMP_NONE, strict_go=True, close=True,
                       key_arena_bytes=0, val_arena_bytes=0, bloom=None, zstd_native=False,
-                      zstd_huffman=False):
+                      zstd_huffman=False, zstd_huffman_fse=False):
         """Device-resident encode.  rows: torch tensors key_arena, key_off,
         key_len, val_arena, val_off, val_len; out: torch tensors seg (uint8),
         optional first_row, desc (int64 [cap, 4]), hash.  Returns the filled
         okv_encode_out (raises OkvError, e.g. OKV_E_CAPACITY with sizes in
         .out).  zstd_native: as for encode(); seg must hold the bound that
         OKV_E_CAPACITY reports, the returned file_bytes is the actual size.
-        zstd_huffman: as for encode()."""
+        zstd_huffman, zstd_huffman_fse: as for encode()."""
         R = _lib.Rows(_ptr(rows["key_arena"]), _ptr(rows["key_off"]), _ptr(rows["key_len"]),
                       _ptr(rows["val_arena"]), _ptr(rows["val_off"]), _ptr(rows["val_len"]),
                       n_rows, key_arena_bytes, val_arena_bytes)
@@ -575,7 +580,8 @@ class Encoder(Decoder):
                             _ptr(g("first_row")), _ptr(g("desc")), _ptr(g("hash")), blk_cap)
         flags = F_DEVICE_PTRS | (0 if close else _lib.F_NO_CLOSE) | bflag | \
             (_lib.F_ZSTD_NATIVE if zstd_native else 0) | \
-            (_lib.F_ZSTD_HUFFMAN if zstd_huffman else 0)
+            (_lib.F_ZSTD_HUFFMAN if zstd_huffman else 0) | \
+            (_lib.F_ZSTD_HUF_FSE if zstd_huffman_fse else 0)
         rc = lib().okv_encode_rows(self._ctx, C.byref(R), C.byref(o), C.byref(eo), flags)
         if rc:
             err = OkvError(rc, f"okv_encode_rows(device): {self.error()}")
@@ -609,17 +615,20 @@ class GpuSegmentWriter:
     device encoder: its frames and its cut differ from the Go writer's, so it is
     opt-in); without it Close raises OKV_W_UNSUPPORTED.  zstd_huffman: Huffman-coded
     literals in those frames (OKV_F_ZSTD_HUFFMAN); without zstd_native Close raises
-    OKV_E_ARG."""
+    OKV_E_ARG.  zstd_huffman_fse: FSE-compressed weights for those literals
+    (OKV_F_ZSTD_HUF_FSE); without zstd_huffman Close raises OKV_E_ARG."""
 
     def __init__(self, encoder: Encoder, threshold=3584, block_size=4096, zstd_level=0,
-                 lz4=False, strict_go=True, bloom=None, zstd_native=False, zstd_huffman=False):
+                 lz4=False, strict_go=True, bloom=None, zstd_native=False, zstd_huffman=False,
+                 zstd_huffman_fse=False):
         self._enc = encoder
         self.bloom = bloom
         self._opts = dict(threshold=threshold, block_size=block_size,
                           compression=COMP_ZSTD if zstd_level > 0 else
                           (COMP_LZ4 if lz4 else COMP_NONE), strict_go=strict_go,
                           zstd_native=bool(zstd_native and zstd_level > 0),
-                          zstd_huffman=bool(zstd_huffman))
+                          zstd_huffman=bool(zstd_huffman),
+                          zstd_huffman_fse=bool(zstd_huffman_fse))
         self._rows = []
         self._closed = False
         self.result = None

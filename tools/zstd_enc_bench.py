@@ -22,10 +22,12 @@ a third arm beside the other two, in the same session, and a third row set:
   (c) 400 000 text rows (ASCII keys, JSON-like values: no byte above 128, which the
       Huffman arm needs; the keys of (a) and the values of (b) hold random bytes) at
       T = 57 344, D = 65 536
+--huffman-fse adds the encoder with FSE-compressed Huffman weights (OKV_F_ZSTD_HUF_FSE,
+DESIGN.md 27) as a further arm, and row set (c) too.
 --no-cpu leaves the libzstd runs out.
 
 Run from the repository root:  python tools/zstd_enc_bench.py [--blocks N] [--huffman]
-                                      [--no-cpu] [--log PATH]
+                                      [--huffman-fse] [--no-cpu] [--log PATH]
 """
 from __future__ import annotations
 
@@ -136,16 +138,20 @@ def timed(enc, fn, warm=2, reps=5):
     return ms
 
 
-def device_case(enc, tag, t, n, T, D, kab, vab, huffman=False):
+def device_case(enc, tag, t, n, T, D, kab, vab, huffman=False, huffman_fse=False):
     res = {}
-    arms = [("uncompressed", okv.sst.COMP_NONE, False, False),
-            ("zstd_native", okv.sst.COMP_ZSTD, True, False)]
+    arms = [("uncompressed", okv.sst.COMP_NONE, False, False, False),
+            ("zstd_native", okv.sst.COMP_ZSTD, True, False, False)]
     if huffman:
-        arms.append(("zstd_native+huffman", okv.sst.COMP_ZSTD, True, True))
-    for name, comp, zn, zh in arms:
+        arms.append(("zstd_native+huffman", okv.sst.COMP_ZSTD, True, True, False))
+    if huffman_fse:
+        arms.append(("zstd_native+huffman+fse", okv.sst.COMP_ZSTD, True, True, True))
+    for name, comp, zn, zh, zf in arms:
         kw = dict(key_arena_bytes=kab, val_arena_bytes=vab)
         if zh:  # (named only here: the tool also times builds from before the flag)
             kw["zstd_huffman"] = True
+        if zf:
+            kw["zstd_huffman_fse"] = True
         try:
             enc.encode_device(t, n, {}, T, D, comp, False, zstd_native=zn, **kw)
         except okv.OkvError as e:
@@ -201,6 +207,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=16384)
     ap.add_argument("--cpu-blocks", type=int, default=2048)
     ap.add_argument("--huffman", action="store_true")
+    ap.add_argument("--huffman-fse", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
@@ -212,7 +219,7 @@ def main():
     r, blocks = cz_rows(a.blocks)
     t = to_dev(r)
     device_case(enc, f"(a) CZ rows x{a.blocks}", t, int(r["key_len"].size), 57344, 65536,
-                int(r["key_arena"].size), int(r["val_arena"].size), a.huffman)
+                int(r["key_arena"].size), int(r["val_arena"].size), a.huffman, a.huffman_fse)
     if not a.no_cpu:
         cpu_case("(a)", blocks[:a.cpu_blocks])
     del t, r
@@ -225,19 +232,20 @@ def main():
              val_off=torch.empty(n, dtype=torch.int64, device="cuda"),
              val_len=torch.empty(n, dtype=torch.int32, device="cuda"))
     enc.synth_fixed_device(1, 0, n, 16, 64, t)
-    device_case(enc, "(b) 100 000 fixed rows", t, n, 3584, 4096, n * 16, n * 64, a.huffman)
+    device_case(enc, "(b) 100 000 fixed rows", t, n, 3584, 4096, n * 16, n * 64, a.huffman,
+                a.huffman_fse)
     if not a.no_cpu:
         ka, va = t["key_arena"].cpu().numpy(), t["val_arena"].cpu().numpy()
         recs = [b"\x10\x00\x40\x00\x00\x00" + ka[16 * i:16 * i + 16].tobytes() +
                 va[64 * i:64 * i + 64].tobytes() for i in range(n)]
         cpu_case("(b)", [b"".join(recs[i:i + 42]) for i in range(0, n, 42)])
     # ---- (c) ----
-    if a.huffman:
+    if a.huffman or a.huffman_fse:
         del t
         r, blocks = text_rows(400_000)
         t = to_dev(r)
         device_case(enc, "(c) 400 000 text rows", t, int(r["key_len"].size), 57344, 65536,
-                    int(r["key_arena"].size), int(r["val_arena"].size), True)
+                    int(r["key_arena"].size), int(r["val_arena"].size), a.huffman, a.huffman_fse)
         if not a.no_cpu:
             cpu_case("(c)", blocks[:a.cpu_blocks])
     enc.close()
