@@ -53,7 +53,9 @@ extern "C" {
                                 one path bit;
                                 still 6 with FSE-compressed Huffman weights there
                                 (OKV_F_ZSTD_HUF_FSE, OKV_PATH_ZSTD_HUF_FSE): one new flag bit
-                                and one path bit */
+                                and one path bit;
+                                still 6 with the range-split encode (okv_encode_split,
+                                okv_split_*): new symbols only */
 
 /* ---- return codes (int) -------------------------------------------------- */
 #define OKV_OK 0
@@ -400,6 +402,69 @@ int okv_encode_rows(okv_ctx *ctx, const okv_rows *rows, const okv_encode_opts *o
  * sequential hash, segment_writer.go:248) and the trailer written into seg.
  * flags: OKV_F_DEVICE_PTRS as given to okv_encode_rows. */
 int okv_encode_close(okv_ctx *ctx, okv_encode_out *out, uint32_t flags);
+
+/* ---- range-split encode ---------------------------------------------------
+ * A compaction's output segments from one call (sst/COMPACTION.md: "Ranges should be split by
+ * size at compaction time"; sst/compaction_range.go: rangeSplitThresholdBytes 1_000_000,
+ * rangeSplitThresholdRows 100_000).  The rows are cut into blocks exactly as okv_encode_rows
+ * cuts them (one greedy chain over the whole row list); a segment is a run of consecutive
+ * blocks of that chain.  The segment starting at block i ends with the first block j >= i for
+ * which sum BlockSize[i..j] >= split_bytes (split_bytes != 0) or rows(i..j) >= split_rows
+ * (split_rows != 0); if neither holds before the last block it ends with the last block.  Both
+ * zero: one segment.  This is what a Go caller gets by watching the writer's flushed bytes and
+ * rows after each WriteRow and closing right after a flush.  Closing right after a flush is
+ * reference quirk Q1 (Go's Close panics on a nil block writer), so the call has strict_go == 0
+ * semantics only: opts->strict_go != 0 is OKV_E_ARG. */
+typedef struct okv_split_opts {
+  uint64_t split_bytes, split_rows; /* 0: no limit */
+  uint64_t bloom_m, bloom_k;        /* bloom_k == 0: BloomFilter nil; else one bloom.New(m, k)
+                                       per segment (max(1, m), max(1, k) as Go), Add for each of
+                                       its keys; bloom_k > 4096: OKV_E_ARG */
+} okv_split_opts;
+
+typedef struct okv_split_seg { /* one output segment */
+  uint64_t first_row, n_rows, first_block, n_blocks;
+  uint64_t data_off, data_bytes; /* into out->data */
+  uint64_t meta_off, meta_bytes; /* into out->meta; the 25-byte trailer follows the meta block */
+  uint64_t meta_hash, file_bytes; /* file = data span ++ meta span ++ trailer */
+} okv_split_seg;
+
+/* File s is data[data_off, +data_bytes) ++ meta[meta_off, +meta_bytes + 25): two spans, ready
+ * for a vectored write or a multipart upload.  The data blocks of all segments, end to end,
+ * are byte for byte okv_encode_rows' data blocks of the same rows. */
+typedef struct okv_split_out {
+  uint8_t *data;            /* every data block, in row order */
+  uint64_t data_cap;
+  uint8_t *meta;            /* per segment its meta block and trailer, at 16-byte-aligned
+                               meta_off (a device meta must be 16-byte aligned itself) */
+  uint64_t meta_cap;
+  okv_split_seg *segs;      /* [seg_cap] */
+  uint64_t seg_cap;
+  uint64_t *blk_first_row;  /* [blk_cap + 1], optional, as in okv_encode_out */
+  okv_block_desc *blk_desc; /* [blk_cap], optional; Offset is relative to the block's segment */
+  uint64_t *blk_hash;       /* [blk_cap], optional */
+  uint64_t blk_cap;
+  /* filled on return (also with OKV_E_CAPACITY): */
+  uint64_t n_segments;
+  uint64_t n_blocks;
+  uint64_t data_bytes;
+  uint64_t meta_arena_bytes; /* sum over segments of round16(meta_bytes + 25) */
+  uint64_t bad_row;          /* OKV_W_INVALID_KEY: the first row with an empty key */
+} okv_split_out;
+
+/*
+ * flags: OKV_F_DEVICE_PTRS (rows and every output pointer are device pointers; data and meta
+ * 16-byte aligned) or none (host memory, staged); OKV_F_ZSTD_* and OKV_F_NO_CLOSE are
+ * OKV_E_ARG.  opts->bloom must be NULL (the filters are the call's own), opts->compression
+ * OKV_COMP_NONE or OKV_COMP_LZ4 (Q7).  Returns OKV_OK; OKV_E_CAPACITY (the sizes in out set,
+ * nothing written: a call with zero capacities is the size query; a following call needs
+ * data_cap >= data_bytes, meta_cap >= meta_arena_bytes, seg_cap >= n_segments and, with any
+ * blk_* array, blk_cap >= n_blocks); OKV_W_INVALID_KEY (bad_row set); OKV_W_NO_ROWS; row
+ * limits and validation as okv_encode_rows.  Every meta hash and trailer is computed on the
+ * device; the number of host synchronisations does not depend on the number of segments.
+ */
+int okv_encode_split(okv_ctx *ctx, const okv_rows *rows, const okv_encode_opts *opts,
+                     const okv_split_opts *split, okv_split_out *out, uint32_t flags);
 
 /* Per-phase encode timing (HIP events on the ctx stream, enabled by
  * okv_profile(ctx, 1)): ms[4] = cut (E1-E9), pack, block hash, meta block,

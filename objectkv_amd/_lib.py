@@ -73,6 +73,7 @@ SYMBOLS = [
     "okv_host_free", "okv_memcpy", "okv_profile", "okv_profile_read", "okv_last_path",
     "okv_decode_chain",
     "okv_encode_rows", "okv_encode_close", "okv_encode_profile_read", "okv_encode_profile_reset",
+    "okv_encode_split",
     "okv_synth_rows_fixed", "okv_merge_rows",
     "okv_bloom_estimate", "okv_bloom_new", "okv_bloom_read_from", "okv_bloom_free",
     "okv_bloom_info", "okv_bloom_clear", "okv_bloom_add_rows", "okv_bloom_test_rows",
@@ -147,6 +148,30 @@ class EncodeOut(C.Structure):
                 ("n_blocks", C.c_uint64), ("data_bytes", C.c_uint64),
                 ("meta_bytes", C.c_uint64), ("file_bytes", C.c_uint64),
                 ("meta_hash", C.c_uint64), ("bad_row", C.c_uint64)]
+
+
+class SplitOpts(C.Structure):
+    """okv_split_opts (include/okv_sst.h)."""
+    _fields_ = [("split_bytes", C.c_uint64), ("split_rows", C.c_uint64),
+                ("bloom_m", C.c_uint64), ("bloom_k", C.c_uint64)]
+
+
+class SplitSeg(C.Structure):
+    """okv_split_seg (include/okv_sst.h): one output segment of okv_encode_split."""
+    _fields_ = [("first_row", C.c_uint64), ("n_rows", C.c_uint64), ("first_block", C.c_uint64),
+                ("n_blocks", C.c_uint64), ("data_off", C.c_uint64), ("data_bytes", C.c_uint64),
+                ("meta_off", C.c_uint64), ("meta_bytes", C.c_uint64), ("meta_hash", C.c_uint64),
+                ("file_bytes", C.c_uint64)]
+
+
+class SplitOut(C.Structure):
+    """okv_split_out (include/okv_sst.h)."""
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("meta", C.c_void_p),
+                ("meta_cap", C.c_uint64), ("segs", C.c_void_p), ("seg_cap", C.c_uint64),
+                ("blk_first_row", C.c_void_p), ("blk_desc", C.c_void_p), ("blk_hash", C.c_void_p),
+                ("blk_cap", C.c_uint64), ("n_segments", C.c_uint64), ("n_blocks", C.c_uint64),
+                ("data_bytes", C.c_uint64), ("meta_arena_bytes", C.c_uint64),
+                ("bad_row", C.c_uint64)]
 
 
 class GetOut(C.Structure):
@@ -283,6 +308,8 @@ def lib():
         "okv_encode_rows": (i32, [p, C.POINTER(Rows), C.POINTER(EncodeOpts),
                                   C.POINTER(EncodeOut), u32]),
         "okv_encode_close": (i32, [p, C.POINTER(EncodeOut), u32]),
+        "okv_encode_split": (i32, [p, C.POINTER(Rows), C.POINTER(EncodeOpts),
+                                   C.POINTER(SplitOpts), C.POINTER(SplitOut), u32]),
         "okv_encode_profile_read": (i32, [p, C.POINTER(C.c_double), C.POINTER(u64)]),
         "okv_encode_profile_reset": (i32, [p]),
         "okv_synth_rows_fixed": (i32, [p, u64, u64, u64, u32, u32, p, p, p, p, p, p]),

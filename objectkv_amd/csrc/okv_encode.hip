@@ -119,6 +119,24 @@ struct EncScratch {
   DevBuf<uint8_t> d_in;
   DevBuf<uint8_t> d_outseg;
   DevBuf<uint8_t> zimg;          // zstd encode: the blocks' raw records, 16-byte padding unit
+  // range-split encode (okv_split.inc): grouping, per-segment layout, filters, Close
+  DevBuf<uint32_t> sp_j[2];      // [nb+1] J_k = next^(2^k), double-buffered
+  DevBuf<uint32_t> sp_mark;      // [nb+1] 1: the block starts a segment
+  DevBuf<uint32_t> sp_xl;        // [nb] tile-local exclusive scan of the marks
+  DevBuf<uint64_t> sp_ttot;      // [nbt] marks per tile
+  DevBuf<uint64_t> sp_tpre;      // [nbt]
+  DevBuf<uint32_t> sp_fb;        // [S+1] first block of each segment; entry S = nb
+  DevBuf<okv_split_seg> sp_segs; // [S]
+  DevBuf<uint64_t> sp_msz;       // [S] round16(meta_bytes + 25)
+  DevBuf<uint64_t> sp_moff;      // [S] meta_off
+  DevBuf<uint64_t> sp_head;      // [S] meta head bytes
+  DevBuf<uint64_t> sp_mhash;     // [S]
+  DevBuf<Desc> sp_hdesc;         // [S] the meta blocks as hash descriptors
+  DevBuf<Desc> sp_rdesc;         // [nb] BlockStats with Offset relative to the segment
+  DevBuf<uint64_t> sp_words;     // [S][words(m)] the segments' filters
+  DevBuf<uint8_t> sp_meta;       // host mode: the meta arena
+  DevBuf<unsigned long long> sp_dtot;  // [2] segments, meta arena bytes
+  PinBuf<unsigned long long> sp_htot;
   PinBuf<uint8_t> close_buf[2];  // D2H chunks of the meta block (Close)
   hipEvent_t close_ev[2] = {nullptr, nullptr};
   // profiling (okv_encode_profile_read): cut, pack, hash, meta
@@ -2115,10 +2133,8 @@ int enc_meta(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opt
              const Plan& pl, uint8_t* seg, bool bloom_dev, int comp_byte, bool from_seg,
              bool fk_done, bool meta_done);
 
-// Data blocks, block hashes and the meta block into seg (E10-E12).
-int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
-              const Plan& pl, uint8_t* seg, bool bloom_dev) {
-  enc_mark(ctx, e, 1);
+// The pack kernels' view of the rows, the plan in e and the segment (okv_split.inc too).
+PackParams pack_params(EncScratch* e, const DevRows& R, uint8_t* seg) {
   PackParams pp;
   pp.key_arena = R.ka;
   pp.key_off = R.ko;
@@ -2135,6 +2151,14 @@ int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_op
   pp.meta = nullptr;
   pp.moff = e->moff.data();
   pp.fk = e->fk.data();
+  return pp;
+}
+
+// Data blocks, block hashes and the meta block into seg (E10-E12).
+int enc_write(okv_ctx* ctx, EncScratch* e, const DevRows& R, const okv_encode_opts& o,
+              const Plan& pl, uint8_t* seg, bool bloom_dev) {
+  enc_mark(ctx, e, 1);
+  PackParams pp = pack_params(e, R, seg);  // (the ablation arms set pp.meta)
   bool hashed = false, meta_done = false, fk_done = false;
   int rc;
 #ifdef OKV_ABLATE
@@ -2351,6 +2375,45 @@ void close_host(okv_encode_out* out) {
   out->file_bytes = out->data_bytes + out->meta_bytes + 25;
 }
 
+// The rows as device arrays: the caller's own (dev), or staged in one device buffer on the
+// context stream.  R->n is set by the caller.
+int rows_on_device(okv_ctx* ctx, EncScratch* e, const okv_rows* rows, bool dev, DevRows* Rp) {
+  DevRows& R = *Rp;
+  const uint64_t n = R.n;
+  int rc;
+  if (dev) {
+    R.ka = rows->key_arena;
+    R.ko = rows->key_off;
+    R.kl = rows->key_len;
+    R.va = rows->val_arena;
+    R.vo = rows->val_off;
+    R.vl = rows->val_len;
+  } else {  // stage the host rows in one device buffer
+    const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+    const size_t oka = 0, ova = oka + al(rows->key_arena_bytes),
+                 oko = ova + al(rows->val_arena_bytes), okl = oko + al(n * 8),
+                 ovo = okl + al(n * 2), ovl = ovo + al(n * 8), end = ovl + al(n * 4);
+    if ((rc = reserve(ctx, e->d_in, end + 64))) return rc;
+    uint8_t* b = e->d_in.data();
+    const hipMemcpyKind h2d = hipMemcpyHostToDevice;
+    if (rows->key_arena_bytes)
+      OKV_HIP(hipMemcpyAsync(b + oka, rows->key_arena, rows->key_arena_bytes, h2d, ctx->stream));
+    if (rows->val_arena_bytes)
+      OKV_HIP(hipMemcpyAsync(b + ova, rows->val_arena, rows->val_arena_bytes, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(b + oko, rows->key_off, n * 8, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(b + okl, rows->key_len, n * 2, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(b + ovo, rows->val_off, n * 8, h2d, ctx->stream));
+    OKV_HIP(hipMemcpyAsync(b + ovl, rows->val_len, n * 4, h2d, ctx->stream));
+    R.ka = b + oka;
+    R.va = b + ova;
+    R.ko = reinterpret_cast<const uint64_t*>(b + oko);
+    R.kl = reinterpret_cast<const uint16_t*>(b + okl);
+    R.vo = reinterpret_cast<const uint64_t*>(b + ovo);
+    R.vl = reinterpret_cast<const uint32_t*>(b + ovl);
+  }
+  return OKV_OK;
+}
+
 }  // namespace
 }  // namespace okv
 
@@ -2394,36 +2457,7 @@ int okv_encode_rows(okv_ctx* ctx, const okv_rows* rows, const okv_encode_opts* o
   const bool dev = flags & OKV_F_DEVICE_PTRS;
   DevRows R;
   R.n = n;
-  if (dev) {
-    R.ka = rows->key_arena;
-    R.ko = rows->key_off;
-    R.kl = rows->key_len;
-    R.va = rows->val_arena;
-    R.vo = rows->val_off;
-    R.vl = rows->val_len;
-  } else {  // stage the host rows in one device buffer
-    const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t oka = 0, ova = oka + al(rows->key_arena_bytes),
-                 oko = ova + al(rows->val_arena_bytes), okl = oko + al(n * 8),
-                 ovo = okl + al(n * 2), ovl = ovo + al(n * 8), end = ovl + al(n * 4);
-    if ((rc = reserve(ctx, e->d_in, end + 64))) return rc;
-    uint8_t* b = e->d_in.data();
-    const hipMemcpyKind h2d = hipMemcpyHostToDevice;
-    if (rows->key_arena_bytes)
-      OKV_HIP(hipMemcpyAsync(b + oka, rows->key_arena, rows->key_arena_bytes, h2d, ctx->stream));
-    if (rows->val_arena_bytes)
-      OKV_HIP(hipMemcpyAsync(b + ova, rows->val_arena, rows->val_arena_bytes, h2d, ctx->stream));
-    OKV_HIP(hipMemcpyAsync(b + oko, rows->key_off, n * 8, h2d, ctx->stream));
-    OKV_HIP(hipMemcpyAsync(b + okl, rows->key_len, n * 2, h2d, ctx->stream));
-    OKV_HIP(hipMemcpyAsync(b + ovo, rows->val_off, n * 8, h2d, ctx->stream));
-    OKV_HIP(hipMemcpyAsync(b + ovl, rows->val_len, n * 4, h2d, ctx->stream));
-    R.ka = b + oka;
-    R.va = b + ova;
-    R.ko = reinterpret_cast<const uint64_t*>(b + oko);
-    R.kl = reinterpret_cast<const uint16_t*>(b + okl);
-    R.vo = reinterpret_cast<const uint64_t*>(b + ovo);
-    R.vl = reinterpret_cast<const uint32_t*>(b + ovl);
-  }
+  if ((rc = rows_on_device(ctx, e, rows, dev, &R))) return rc;
   Plan pl;
   uint64_t bad = kNone;
   // the cut, sizes and offsets: E1-E9 (pointer doubling over chunks)
@@ -2563,3 +2597,6 @@ int okv_synth_rows_fixed(okv_ctx* ctx, uint64_t seed, uint64_t first_row, uint64
 }
 
 }  // extern "C"
+
+// okv_encode_split (include/okv_sst.h): the range-split encode, on this file's plan and pack
+#include "okv_split.inc"

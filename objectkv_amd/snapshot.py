@@ -839,17 +839,9 @@ class Iter:
 # ---- compaction: decode -> merge -> encode on the device ---------------------------------
 
 
-def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, block_size=4096,
-            direction=DirectionAscending, zstd=False, zstd_huffman=False,
-            zstd_huffman_fse=False):
-    """Merge resident segments (DeviceSegment, level) in priority order (newest
-    first) into one new segment, on the GPU: every key's owning row (GetRange's
-    rule, :294-331), L0 tombstones dropped when drop_tombstones.  zstd: write the
-    output segment zstd-compressed with the device encoder (OKV_F_ZSTD_NATIVE:
-    its own frames, blocks cut on raw lengths); zstd_huffman: with zstd, Huffman-coded
-    literals where they are smaller (OKV_F_ZSTD_HUFFMAN); zstd_huffman_fse: with
-    zstd_huffman, FSE-compressed weights (OKV_F_ZSTD_HUF_FSE).  Returns the Compacted result
-    (segment bytes + block index)."""
+def _merge_all(segments, encoder, drop_tombstones, direction):
+    """compact()'s merge step: every key's owning row of the resident segments, as device
+    row arrays over the inputs' arenas.  -> (rows, n_rows, key span, value span, device)."""
     import torch
     srcs = [(ds.t, 0, ds.n, lvl) for ds, lvl in segments]
     dev = torch.device("cuda", encoder.device)
@@ -869,6 +861,22 @@ def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, bl
                 for ds, _ in segments) - vb
     rows = {"key_arena": _Addr(kb), "key_off": out["key_off"], "key_len": out["key_len"],
             "val_arena": _Addr(vb), "val_off": out["val_off"], "val_len": out["val_len"]}
+    return rows, n, kspan, vspan, dev
+
+
+def compact(segments, encoder: Encoder, drop_tombstones=True, threshold=3584, block_size=4096,
+            direction=DirectionAscending, zstd=False, zstd_huffman=False,
+            zstd_huffman_fse=False):
+    """Merge resident segments (DeviceSegment, level) in priority order (newest
+    first) into one new segment, on the GPU: every key's owning row (GetRange's
+    rule, :294-331), L0 tombstones dropped when drop_tombstones.  zstd: write the
+    output segment zstd-compressed with the device encoder (OKV_F_ZSTD_NATIVE:
+    its own frames, blocks cut on raw lengths); zstd_huffman: with zstd, Huffman-coded
+    literals where they are smaller (OKV_F_ZSTD_HUFFMAN); zstd_huffman_fse: with
+    zstd_huffman, FSE-compressed weights (OKV_F_ZSTD_HUF_FSE).  Returns the Compacted result
+    (segment bytes + block index)."""
+    import torch
+    rows, n, kspan, vspan, dev = _merge_all(segments, encoder, drop_tombstones, direction)
     comp = _lib.COMP_ZSTD if zstd else COMP_NONE
     try:  # size query (zero capacities; with zstd file_bytes is an upper bound)
         encoder.encode_device(rows, n, {}, threshold, block_size, comp, False,
@@ -908,3 +916,39 @@ class Compacted:
     def __init__(self, seg, file_bytes, n_rows, n_blocks, dev_out, eo):
         self.seg, self.file_bytes, self.n_rows, self.n_blocks = seg, file_bytes, n_rows, n_blocks
         self.dev_out, self.eo = dev_out, eo
+
+
+class CompactedSegment:
+    """One output segment of compact_split(): the file's bytes (host), its rows and blocks,
+    and FirstKey / LastKey for its SegmentRecord."""
+
+    def __init__(self, seg, n_rows, n_blocks, FirstKey, LastKey):
+        self.seg, self.file_bytes = seg, int(seg.size)
+        self.n_rows, self.n_blocks = n_rows, n_blocks
+        self.FirstKey, self.LastKey = FirstKey, LastKey
+
+    def record(self, ID: str, Level: int = 1) -> SegmentRecord:
+        return SegmentRecord(ID, Level, self.FirstKey, self.LastKey)
+
+
+def compact_split(segments, encoder: Encoder, drop_tombstones=True, threshold=3584,
+                  block_size=4096, split_bytes=1_000_000, split_rows=100_000, bloom=None):
+    """compact()'s merge, then the range-split encode (okv_encode_split): the output is cut
+    into segments by the reference's thresholds (sst/compaction_range.go: 1 000 000 bytes,
+    100 000 rows), every segment with its own meta block, trailer and -- bloom=(m, k) -- its
+    own filter, from one device call.  Returns the list of CompactedSegment, in key order
+    (empty when no row survives the merge)."""
+    rows, n, kspan, vspan, _dev = _merge_all(segments, encoder, drop_tombstones,
+                                             DirectionAscending)
+    if n == 0:
+        return []
+    res = encoder.encode_split_device(rows, n, {}, threshold, block_size,
+                                      key_arena_bytes=kspan, val_arena_bytes=vspan,
+                                      split_bytes=split_bytes, split_rows=split_rows,
+                                      bloom=bloom)
+    out = []
+    for s, g in enumerate(res.segments):
+        fk, lk = res.record(s)
+        out.append(CompactedSegment(np.frombuffer(res.file(s), np.uint8), g.n_rows, g.n_blocks,
+                                    fk, lk))
+    return out

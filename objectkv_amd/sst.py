@@ -456,6 +456,56 @@ class Encoded:
         return self.seg[self.data_bytes:self.data_bytes + self.meta_bytes].tobytes()
 
 
+@dataclass
+class SplitSegment:
+    """okv_split_seg: one output segment of the range-split encode."""
+    first_row: int
+    n_rows: int
+    first_block: int
+    n_blocks: int
+    data_off: int
+    data_bytes: int
+    meta_off: int
+    meta_bytes: int
+    meta_hash: int
+    file_bytes: int
+
+
+@dataclass
+class SplitEncoded:
+    """Result of Encoder.encode_split_device: the segment records and the two device
+    arenas.  File s is data[data_off, +data_bytes) ++ meta[meta_off, +meta_bytes + 25)."""
+    segments: list           # [SplitSegment]
+    data: object             # torch uint8: every data block, in row order
+    meta: object             # torch uint8: per segment its meta block and trailer
+    n_blocks: int
+    data_bytes: int
+    meta_arena_bytes: int
+    first_row: object        # torch int64 [n_blocks + 1]
+    desc: object             # torch int64 [n_blocks, 4]; Offset relative to the segment
+    hash: object             # torch int64 [n_blocks]
+
+    def _meta(self, s) -> bytes:
+        g = self.segments[s]
+        return self.meta[g.meta_off:g.meta_off + g.meta_bytes + 25].cpu().numpy().tobytes()
+
+    def file(self, s) -> bytes:
+        """Host bytes of file s: its two spans, copied back and joined."""
+        g = self.segments[s]
+        return self.data[g.data_off:g.data_off + g.data_bytes].cpu().numpy().tobytes() + \
+            self._meta(s)
+
+    def record(self, s):
+        """-> (FirstKey, LastKey) of segment s, for its SegmentRecord."""
+        g = self.segments[s]
+        # the head holds both keys: at most 2 x (2 + 65535) bytes
+        n = min(g.meta_bytes, 2 * 65537)
+        m = self.meta[g.meta_off:g.meta_off + n].cpu().numpy().tobytes()
+        k0 = int.from_bytes(m[:2], "little")
+        kz = int.from_bytes(m[2 + k0:4 + k0], "little")
+        return m[2:2 + k0], m[4 + k0:4 + k0 + kz]
+
+
 def _is_device_bloom(bloom) -> bool:
     from .bloom import DeviceBloom  # (bloom.py imports this module)
     return isinstance(bloom, DeviceBloom)
@@ -588,6 +638,65 @@ class Encoder(Decoder):
             err.out = eo
             raise err
         return eo
+
+    def encode_split_device(self, rows: dict, n_rows: int, out: dict | None = None,
+                            threshold=3584, block_size=4096, compression=COMP_NONE,
+                            key_arena_bytes=0, val_arena_bytes=0, split_bytes=1_000_000,
+                            split_rows=100_000, bloom=None) -> "SplitEncoded":
+        """Device-resident range-split encode (okv_encode_split): the rows cut into blocks
+        as encode_device cuts them, and the blocks into segments by split_bytes /
+        split_rows (0: no limit), every segment with its own meta block and trailer.
+        bloom: None (BloomFilter nil) or (m, k), one bloom.New(m, k) per segment.  rows:
+        torch tensors as for encode_device.  The call does the size query, allocates what
+        `out` (a dict of torch tensors data, meta, segs, first_row, desc, hash; may be
+        empty or None) lacks or holds too small, and encodes; the tensors used are left in
+        `out` and in the result."""
+        import torch
+        R = _lib.Rows(_ptr(rows["key_arena"]), _ptr(rows["key_off"]), _ptr(rows["key_len"]),
+                      _ptr(rows["val_arena"]), _ptr(rows["val_off"]), _ptr(rows["val_len"]),
+                      n_rows, key_arena_bytes, val_arena_bytes)
+        o = _lib.EncodeOpts(threshold, block_size, compression, 0, None, 0)
+        m, k = bloom if bloom is not None else (0, 0)
+        so = _lib.SplitOpts(split_bytes, split_rows, m, k)
+        q = _lib.SplitOut()
+        rc = lib().okv_encode_split(self._ctx, C.byref(R), C.byref(o), C.byref(so), C.byref(q),
+                                    F_DEVICE_PTRS)
+        if rc != OKV_E_CAPACITY:
+            err = OkvError(rc, f"okv_encode_split(size): {self.error()}")
+            err.out = q
+            raise err
+        out = out if out is not None else {}
+        dev = torch.device("cuda", self.device)
+        nb, ns = int(q.n_blocks), int(q.n_segments)
+        nseg_words = ns * (C.sizeof(_lib.SplitSeg) // 8)
+
+        def room(name, n, dtype, shape=None):
+            t = out.get(name)
+            if t is None or t.numel() < n:
+                t = out[name] = torch.empty(shape or n, dtype=dtype, device=dev)
+            return t
+
+        data = room("data", int(q.data_bytes), torch.uint8)
+        meta = room("meta", int(q.meta_arena_bytes), torch.uint8)
+        segs = room("segs", nseg_words, torch.int64)
+        first = room("first_row", nb + 1, torch.int64)
+        desc = room("desc", nb * 4, torch.int64, (nb, 4))
+        hsh = room("hash", nb, torch.int64)
+        so_out = _lib.SplitOut(_ptr(data), data.numel(), _ptr(meta), meta.numel(), _ptr(segs),
+                               segs.numel() // (C.sizeof(_lib.SplitSeg) // 8), _ptr(first),
+                               _ptr(desc), _ptr(hsh), min(first.numel() - 1, desc.numel() // 4,
+                                                          hsh.numel()))
+        rc = lib().okv_encode_split(self._ctx, C.byref(R), C.byref(o), C.byref(so), C.byref(so_out),
+                                    F_DEVICE_PTRS)
+        if rc:
+            err = OkvError(rc, f"okv_encode_split(device): {self.error()}")
+            err.out = so_out
+            raise err
+        host = segs[:nseg_words].cpu().numpy().view(np.uint64).reshape(ns, -1)
+        names = [f[0] for f in _lib.SplitSeg._fields_]
+        records = [SplitSegment(**{nm: int(v) for nm, v in zip(names, row)}) for row in host]
+        return SplitEncoded(records, data, meta, nb, int(so_out.data_bytes),
+                            int(so_out.meta_arena_bytes), first, desc, hsh)
 
     def close_device(self, eo):
         """okv_encode_close on a device segment (meta XXH64 on the host)."""
