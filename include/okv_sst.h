@@ -386,7 +386,8 @@ typedef struct okv_encode_out {
 
 /*
  * Encode rows into one segment on the GPU.  flags: OKV_F_DEVICE_PTRS (rows and
- * every output pointer are device pointers; seg must be 16-byte aligned),
+ * every output pointer are device pointers; seg should be 16-byte aligned: a seg that is
+ * not is accepted and written by the slower byte-store pack kernels, same bytes),
  * OKV_F_NO_CLOSE, OKV_F_BLOOM_DEVICE, OKV_F_ZSTD_NATIVE, OKV_F_ZSTD_HUFFMAN (with
  * OKV_F_ZSTD_NATIVE only), OKV_F_ZSTD_HUF_FSE (with OKV_F_ZSTD_HUFFMAN only).  Returns OKV_OK; OKV_E_CAPACITY (sizes in out set, nothing
  * written: call again with seg_cap >= file_bytes and blk_cap >= n_blocks --
@@ -453,8 +454,9 @@ typedef struct okv_split_out {
 } okv_split_out;
 
 /*
- * flags: OKV_F_DEVICE_PTRS (rows and every output pointer are device pointers; data and meta
- * 16-byte aligned) or none (host memory, staged); OKV_F_ZSTD_* and OKV_F_NO_CLOSE are
+ * flags: OKV_F_DEVICE_PTRS (rows and every output pointer are device pointers; meta must be
+ * 16-byte aligned, else OKV_E_ARG; data should be, as seg of okv_encode_rows) or none (host
+ * memory, staged); OKV_F_ZSTD_* and OKV_F_NO_CLOSE are
  * OKV_E_ARG.  opts->bloom must be NULL (the filters are the call's own), opts->compression
  * OKV_COMP_NONE or OKV_COMP_LZ4 (Q7).  Returns OKV_OK; OKV_E_CAPACITY (the sizes in out set,
  * nothing written: a call with zero capacities is the size query; a following call needs

@@ -11,6 +11,7 @@ import pytest
 import objectkv_amd as okv
 from objectkv_amd import _lib
 from oracle import coracle as CO
+from tests import guarded as G
 from tests import staged_cases as SC
 from tests.conftest import descs_of, rowval, unpack
 
@@ -655,16 +656,20 @@ def _device_decode(dec, seg, d, comp=_lib.COMP_NONE, index_only=False, sync=True
     seg_t = torch.from_numpy(s.copy()).to(dev)
     d_t = torch.from_numpy(d.view(np.int64).copy()).to(dev)
     rows, kb, vb = dec.plan_device(seg_t, s.size, d_t, n, comp, index_only)
-    out = {k: torch.zeros(m, dtype=t, device=dev) for k, m, t in [
-        ("row_start", n + 1, torch.int64), ("key_base", n, torch.int64),
-        ("val_base", n, torch.int64), ("status", max(n, 1), torch.int32),
-        ("key_off", rows, torch.int64), ("key_len", rows, torch.int16),
-        ("val_off", rows, torch.int64), ("val_len", rows, torch.int32),
-        ("key_arena", kb, torch.uint8), ("val_arena", vb, torch.uint8)]}
+    # every output is a poisoned frame of exactly the planned size (tests/guarded.py)
+    frames = {k: G.frame(m, t, device=dev) for k, m, t in [
+        ("row_start", n + 1, np.uint64), ("key_base", n, np.uint64),
+        ("val_base", n, np.uint64), ("status", max(n, 1), np.int32),
+        ("key_off", rows, np.uint64), ("key_len", rows, np.uint16),
+        ("val_off", rows, np.uint64), ("val_len", rows, np.uint32),
+        ("key_arena", kb, np.uint8), ("val_arena", vb, np.uint8)]}
+    out = {k: f.view for k, f in frames.items()}
     o = dec.decode_device(seg_t, s.size, d_t, n, out, comp, index_only=index_only, sync=sync)
 
     def fetch():
-        h = {k: v.cpu().numpy() for k, v in out.items()}
+        for k, f in frames.items():
+            f.check(k)
+        h = {k: f.host() for k, f in frames.items()}
         full = not index_only
         return okv.Decoded(
             status=h["status"][:n], row_start=h["row_start"].view(np.uint64),

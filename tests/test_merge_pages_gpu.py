@@ -55,15 +55,23 @@ def _layout(caps, slice_order):
     return at, pos
 
 
-def run_pages(dec, streams, specs, slice_order=None, device_mode=False):
+def run_pages(dec, streams, specs, slice_order=None, device_mode=False, base16=False):
     """One okv_merge_pages call over `streams` (the call's sources, MG.Stream) and `specs`
-    -> [PageResult] in specs order, with the raw arrays on result[0].raw."""
+    -> [PageResult] in specs order, with the raw arrays on result[0].raw.  base16: src and
+    row start 16 bytes into a 128-byte line (inside a larger tensor of FILL)."""
     dev = torch.device("cuda", 0)
     caps = [sum(s.hi - s.lo for s in streams[p.src_at:p.src_at + p.nsrc]) if p.cap is None
             else p.cap for p in specs]
     at, total = _layout(caps, slice_order or range(len(specs)))
     out = {"src": torch.full((total,), FILL, dtype=torch.int32, device=dev),
            "row": torch.full((total,), FILL, dtype=torch.int64, device=dev)}
+    if base16:
+        whole = {"src": torch.full((total + 64,), FILL, dtype=torch.int32, device=dev),
+                 "row": torch.full((total + 32,), FILL, dtype=torch.int64, device=dev)}
+        for k, t in whole.items():
+            skip = ((16 - t.data_ptr()) % 128) // t.element_size()
+            out[k] = t[skip:skip + total]
+            assert out[k].data_ptr() % 128 == 16
     bounds, pages = b"", []
     for p, a, cap in zip(specs, at, caps):
         pages.append(L.Page(p.limit, a, cap, p.src_at, p.nsrc, len(bounds), len(p.bound),
@@ -99,6 +107,10 @@ def run_pages(dec, streams, specs, slice_order=None, device_mode=False):
     # guard slots: everything outside the slices
     assert (src[~in_slice] == FILL).all() and (row[~in_slice] == FILL).all()
     assert int((~in_slice).sum()) == GUARD * (len(specs) + 1)
+    if base16:  # nothing outside the arrays either
+        for t in whole.values():
+            assert int((t != FILL).sum()) == int((out["src" if t.dtype == torch.int32
+                                                      else "row"] != FILL).sum())
     if res:
         res[0].raw = (src, row, np.asarray(n_rows), np.asarray(n_unique), np.asarray(status))
     return res
@@ -169,6 +181,15 @@ def test_termination_ties_one_call(decoder):
     for r, p, want in zip(res, specs, wants):
         assert check_page(r, streams, p, want) == want[1]
     assert {r.status for r in res} == {0, L.M_EOF}
+
+
+def test_termination_ties_src_and_row_at_base_16(decoder):
+    """The same pages with src and row 16 bytes into a 128-byte line: the contract for
+    device pointers is their natural alignment, not a line."""
+    streams, specs, wants = _tie_pages()
+    res = run_pages(decoder, streams, specs, base16=True)
+    for r, p, want in zip(res, specs, wants):
+        assert check_page(r, streams, p, want) == want[1]
 
 
 def test_device_mode_equals_host_mode(decoder):

@@ -8,6 +8,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from tests import guarded as G
 from tests.test_decode_gpu import _assert_same_as_oracle
 
 pytestmark = pytest.mark.gpu
@@ -219,21 +220,21 @@ def test_capacity_statuses_device(decoder):
     d_t = torch.from_numpy(d.view(np.int64)).to(dev)
     rows, kb, vb = decoder.plan_device(seg_t, seg.size, d_t, 64)
     for cut in ("val", "key", "rows"):
-        out = dict(row_start=torch.zeros(65, dtype=torch.int64, device=dev),
-                   key_base=torch.zeros(64, dtype=torch.int64, device=dev),
-                   val_base=torch.zeros(64, dtype=torch.int64, device=dev),
-                   status=torch.zeros(64, dtype=torch.int32, device=dev),
-                   key_off=torch.zeros(rows // 2 if cut == "rows" else rows, dtype=torch.int64,
-                                       device=dev),
-                   key_len=torch.zeros(rows, dtype=torch.int16, device=dev),
-                   val_off=torch.zeros(rows, dtype=torch.int64, device=dev),
-                   val_len=torch.zeros(rows, dtype=torch.int32, device=dev),
-                   key_arena=torch.zeros(kb // 2 if cut == "key" else kb, dtype=torch.uint8,
-                                         device=dev),
-                   val_arena=torch.zeros(vb // 2 if cut == "val" else vb, dtype=torch.uint8,
-                                         device=dev))
+        frames = dict(row_start=G.frame(65, np.uint64, device=dev),
+                      key_base=G.frame(64, np.uint64, device=dev),
+                      val_base=G.frame(64, np.uint64, device=dev),
+                      status=G.frame(64, np.int32, device=dev),
+                      key_off=G.frame(rows // 2 if cut == "rows" else rows, np.uint64, device=dev),
+                      key_len=G.frame(rows, np.uint16, device=dev),
+                      val_off=G.frame(rows, np.uint64, device=dev),
+                      val_len=G.frame(rows, np.uint32, device=dev),
+                      key_arena=G.frame(kb // 2 if cut == "key" else kb, np.uint8, device=dev),
+                      val_arena=G.frame(vb // 2 if cut == "val" else vb, np.uint8, device=dev))
+        out = {k: f.view for k, f in frames.items()}
         with pytest.raises(Exception):
             decoder.decode_device(seg_t, seg.size, d_t, 64, out, sync=True)
+        for k, f in frames.items():
+            f.check(k)
         st = out["status"].cpu().numpy()
         assert (st == 5).any() and (st == 0).any(), cut
         first_bad = int(np.argmax(st != 0))
